@@ -10,13 +10,19 @@ synthetic input: one 224x224 image per GPU per iteration (the reference's operat
 fp32 accumulation.  One step = forward + backward + gradient all-reduce (N > 1) + fused SGD step.
 Inputs are generated once and are resident in HBM before the timed region starts.
 
-Prints ONE JSON line (rank 0) with
+Prints ONE JSON line (rank 0) with `value` (images/sec), `ms_per_step` (one timed step) and
   `roofline`          dominant kernel's launch in the step: the fc6 forward launch of gemm_nt256_kernel, issued eagerly in
                       front of the replayed heads graph and bracketed by HIP events on its stream INSIDE the timed region
   `roofline_launches` the same for every launch of that kernel in the step (fc6 forward + the fc6 dW row slabs)
   `roofline_step`     the whole step: algorithmic FLOPs x steps / timed wall time against the bf16 MFMA peak
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything that takes work of its own moves behind
+--full (off by default):
   `roofline_hbm`      the two HBM-bound kernels (ROIPool+A^T, fused SGD on the run's live arena), timed after the region
-  `cpu_baseline`      the oracle - a port - timed on this box's host cores on the same workload."""
+  `cpu_baseline`      the oracle - a port - timed on this box's host cores on the same workload (not with --no-cpu-baseline)
+  `side_*`, `roofline_trunk`  further steps of the same run, the trunk at a real image size, other configs in child
+                      processes (not with --no-side); N > 1: the step without the exchange and the other exchange.
+--dump-outputs DIR writes what the last timed step computed (its losses, the updated trainable parameters: a fixed seeded
+sample of the large ones) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs."""
 import argparse
 import json
 import math
@@ -129,6 +135,28 @@ def assert_sane_losses(losses, where):
     if bad:
         raise RuntimeError("%s: degenerate losses %s - the timing would be taken on saturated values" % (where, vals))
     return vals
+
+
+def dump_outputs(out_dir, model, losses, sample=1 << 19, limit=64 << 20):
+    """What the last timed step computed, as out_dir/<name>.npy in float32: each loss it returned, and every trainable
+    parameter after its update (the frozen trunk does not change) - whole up to `sample` elements, else `sample` elements
+    at fixed indices drawn from a generator seeded with the parameter's size, so that two runs pick the same ones."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().reshape(-1) for k, v in losses.items()}
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            flat = p.detach().reshape(-1)
+            if flat.numel() > sample:
+                idx = np.sort(np.random.default_rng(flat.numel()).choice(flat.numel(), sample, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arrays[name] = flat.float()
+    total = sum(a.numel() * 4 for a in arrays.values())
+    if total > limit:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, limit))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 def synthetic_batches(n_batches, R, K, device, rank, pkg, ims=1):
@@ -358,9 +386,14 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--proposals", type=int, default=2000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the HBM-bound kernels timed on their own, the CPU baseline, further steps of the "
+                         "same run and the side measurements (each can be left out with the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses and the updated trainable parameters of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side measurements of the default run (trunk at 800x1216 for the C4 and the shipped DC5 recipe; child "
+                    help="with --full: skip the side measurements (trunk at 800x1216 for the C4 and the shipped DC5 recipe; child "
                          "processes: the 4-images-per-GPU step, BASELINE's other configs on one GPU, the eager real-shape rotation)")
     ap.add_argument("--workload", choices=["r50c4", "r50dc5", "r101c4_k80", "r50c4_fp8", "v16"], default="r50c4",
                     help="r50c4 = BASELINE configs[1], the headline metric; r50dc5 (configs[2]: WS-R50 dilated C5, use with "
@@ -427,7 +460,8 @@ def main():
                          "the optimizer traffic), all-gather of the updated bf16 rows; allreduce = DDP's all-reduce + "
                          "replicated update")
     ap.add_argument("--no-other-exchange", action="store_true",
-                    help="N > 1 with the K-sharded fc6: skip the 20 steps of the sharded gradient exchange timed after the headline region")
+                    help="--full, N > 1 with the K-sharded fc6: skip the 20 steps of the sharded gradient exchange timed after the "
+                         "headline region")
     ap.add_argument("--kshard-wire", choices=["fp32", "bf16"], default="bf16",
                     help="--exchange fc6_kshard: dtype of the partial fc6 pre-activations on the wire (reduce-scatter)")
     ap.add_argument("--comm-dtype", choices=["bf16", "fp32"], default=None,
@@ -669,22 +703,34 @@ def main():
         return dt_, t_enq_, tim, hbm, last_
 
     other_exchange = None
+    host_unblocked = sustained = local_ms = None
     if use_graph:
         dt, t_enq, timing, hbm_timing, last = timed_region(stepper, args.steps, not args.no_launch_timing)
+    else:
+        ops.GEMM_TIMING = timing = []
+        ops.HBM_TIMING = hbm_timing = []
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            last = step(args.warmup + i)
+        t_enq = time.perf_counter() - t0  # host time to enqueue the whole timed region (diagnostic)
+        barrier()
+        dt = time.perf_counter() - t0
+        ops.GEMM_TIMING = ops.HBM_TIMING = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)  # before any further step moves the weights
+    if use_graph and args.full:
         # pure host cost of one step: six steps enqueued right after a sync (the 8-slot label ring cannot block yet)
         th = time.perf_counter()
         for i in range(6):
             last2 = stepper.step(*window(args.warmup + args.steps + i))
         host_unblocked = (time.perf_counter() - th) / 6 * 1e3
         barrier()
-        sustained = None
         if world == 1 and not args.no_side and args.steps < 200:
             # side figure, never `value`: the same graphed step over 200 more steps (~0.26 s) - a timed region of a few dozen
             # steps is shorter than the clock / power transients of the box (one 25-ms window)
             dt_s, _, _, _, _ = timed_region(stepper, 200, False, offset=args.steps + 6)
             sustained = {"steps": 200, "value": 200 * args.ims_per_gpu / dt_s, "unit": "images/sec", "ms_per_step": dt_s / 200 * 1e3,
                          "how": "the same graphed step, 200 further steps between two syncs, no HIP events inside"}
-        local_ms = None
         if dp.exchange and getattr(opt, "_exchange_on", False):
             # what the exchange costs on the critical path: the SAME graphed step with the collectives switched off (every
             # rank updates all rows from its local gradient - the replicas diverge, the measurement above is over),
@@ -704,16 +750,6 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 local_ms = float(tt)
             opt._exchange_on = True
-    else:
-        ops.GEMM_TIMING = timing = []
-        ops.HBM_TIMING = hbm_timing = []
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            last = step(args.warmup + i)
-        t_enq = time.perf_counter() - t0  # host time to enqueue the whole timed region (diagnostic)
-        barrier()
-        dt = time.perf_counter() - t0
-        ops.GEMM_TIMING = ops.HBM_TIMING = None
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -928,7 +964,7 @@ def main():
                                             "update on every rank), max over ranks; in the sharded exchange the step WITH "
                                             "exchange updates only 1/N of the fc6 rows, so this can be negative"},
                "roofline": roof, "roofline_step": roof_step, "roofline_launches": launches}
-        if world == 1 and not dp.exchange:
+        if args.full and world == 1 and not dp.exchange:
             try:
                 out["roofline_hbm"] = hbm_rooflines(model, batches[0], R, device, ops, opt)
             except Exception as ex:  # noqa: BLE001 - supporting evidence only, never at the cost of the main line
@@ -999,7 +1035,7 @@ def main():
             roof["time_by_kernel_family"] = sorted(cands, key=lambda c: -c["us_per_step"])
         if use_graph and sustained is not None:
             out["side_sustained"] = sustained
-        if world == 1 and not args.no_side and args.workload == "r50c4" and args.ims_per_gpu == 1:
+        if args.full and world == 1 and not args.no_side and args.workload == "r50c4" and args.ims_per_gpu == 1:
             # SURVEY 8(d) side figures of the default run (never part of `value`): the trunk at a real training size - C4 and
             # the shipped DC5 recipe - and the same step with 4 images per GPU
             try:
@@ -1028,7 +1064,7 @@ def main():
                      ("side_r50c4_fp8", ["--workload", "r50c4_fp8"], "BASELINE configs[4] on one GPU: the R50-C4 trunk on the fp8 MFMA conv path")]
             for key_, extra_, what_ in sides:
                 try:
-                    j_ = child([me] + extra_ + ["--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-side"])
+                    j_ = child([me] + extra_ + ["--steps", "20", "--warmup", "3"])
                     out[key_] = {"value": j_["value"], "unit": "images/sec", "ms_per_step": j_["ms_per_step"], "steps": j_["steps"],
                                  "roofline_step_frac": j_["roofline_step"]["frac"],
                                  "how": "child process: python bench.py %s --steps 20 --warmup 3 (%s)" % (" ".join(extra_), what_)}
@@ -1049,15 +1085,15 @@ def main():
         out["timed_region_s"] = dt
         if dt < 0.2:
             out["timed_region_note"] = ("the timed region is %.0f ms (%d steps): shorter than clock / power transients; "
-                                        "`side_sustained` (200 further steps of the same run), the default run (100 steps) and "
-                                        "profiles/ hold the sustained figure" % (dt * 1e3, args.steps))
-        if world == 1 and not args.no_cpu_baseline:
+                                        "`side_sustained` (--full: 200 further steps of the same run), the default run (100 steps) "
+                                        "and profiles/ hold the sustained figure" % (dt * 1e3, args.steps))
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload in ("r50c4", "r50c4_fp8"):
                 out["cpu_baseline"] = cpu_baseline(batches)
             else:  # the oracle leg is timed on the BASELINE workload only (its config is the R50-C4 / K = 20 model)
                 out["cpu_baseline"] = None
-                out["cpu_baseline_note"] = "side workload: the CPU port is timed on the r50c4 workload only (default run)"
-    if use_graph and dp.exchange and world > 1 and exchange == "fc6_kshard" and not args.no_other_exchange:
+                out["cpu_baseline_note"] = "side workload: the CPU port is timed on the r50c4 workload only (--full run)"
+    if args.full and use_graph and dp.exchange and world > 1 and exchange == "fc6_kshard" and not args.no_other_exchange:
         # the OTHER exchange on the same job, 20 steps, AFTER everything the JSON line needs has been measured (report
         # both): the sharded gradient exchange (reduce-scatter per fc6 slab -> owned rows -> all-gather of the updated compute
         # copy).  A watchdog prints the line without it if this phase wedges - it must never cost the headline measurement.

@@ -922,6 +922,69 @@ def case_convert(name, seed):
     print("wrote", path)
 
 
+REF_YAMLS = ("PascalVOC-Detection/oicr_WSR_50_DC5_1x.yaml", "PascalVOC-Detection/oicr_WSR_18_DC5_1x.yaml",
+             "PascalVOC-Detection/oicr_WSR_101_DC5_1x.yaml", "PascalVOC-Detection/oicr_V_16_DC5_1x.yaml",
+             "COCO-Detection/oicr_WSR_50_DC5_1x.yaml", "PascalVOC-Detection/reg/oicr_WSR_50_DC5_1x.yaml",
+             "PascalVOC-Detection/pcl_WSR_50_DC5_1x.yaml", "PascalVOC-Detection/wsddn_WSR_50_DC5_1x.yaml")
+
+
+def case_ref_yaml(name):
+    """The shipped projects/WSL configs as the product's config loader reads them: get_cfg() + add_wsl_config() +
+    merge_from_file(<the unmodified yaml, with its _BASE_ chain>), recorded per file as the merged config (CfgNode.dump
+    parsed back).  tests/test_surface_cpu.py loads these records; the yaml files themselves are not stored."""
+    import json
+
+    import yaml
+
+    from __graft_entry__ import load_package
+
+    load_package()
+    from drn_wsod_pytorch_amd.config import add_wsl_config, get_cfg
+
+    out = {}
+    for rel in REF_YAMLS:
+        cfg = get_cfg()
+        add_wsl_config(cfg)
+        cfg.merge_from_file(os.path.join(rh.REF, "projects", "WSL", "configs", rel))
+        out[rel] = yaml.safe_load(cfg.dump())
+    path = os.path.join(HERE, name + ".json")
+    with open(path, "w") as f:
+        json.dump(out, f, sort_keys=True, separators=(",", ":"))
+    print("wrote", path)
+
+
+def case_roi_align_ref(name, seed):
+    """oracle/_ref (the reference's ROIAlign_cpu.cpp compiled as-is) on random maps and boxes, some reaching past the
+    map, for aligned False / True and sampling ratios 0, 1, 3: forward outputs and the backward's input gradients."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("_ob", os.path.join(rh.REPO, "oracle", "build.py"))
+    ob = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ob)
+    spec = importlib.util.spec_from_file_location("d2_roialign_ref", ob.build_ref())
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    g = torch.Generator().manual_seed(seed)
+    N, C, H, W, R = 2, 4, 19, 23, 64
+    feat = torch.randn(N, C, H, W, generator=g)
+    x0 = torch.rand(R, generator=g) * 150
+    y0 = torch.rand(R, generator=g) * 120
+    rois = torch.stack([torch.randint(0, N, (R,), generator=g).float(), x0, y0, x0 + torch.rand(R, generator=g) * 100,
+                        y0 + torch.rand(R, generator=g) * 90], 1)
+    d = {"feat": feat.numpy(), "rois": rois.numpy()}
+    for al in (False, True):
+        for sr in (0, 1, 3):
+            key = "al%d_sr%d" % (int(al), sr)
+            out = ref.roi_align_forward(feat, rois, 1 / 8.0, 7, 7, sr, al)
+            go = torch.randn(out.shape, generator=g)
+            d[key + "_out"] = out.numpy()
+            d[key + "_gout"] = go.numpy()
+            d[key + "_gin"] = ref.roi_align_backward(go, rois, 1 / 8.0, 7, 7, N, C, H, W, sr, al).numpy()
+    path = os.path.join(HERE, name + ".npz")
+    np.savez_compressed(path, **d)
+    print("wrote", path)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -1024,3 +1087,7 @@ if __name__ == "__main__":
     if "r50c4_reg" in which:
         case_full_model("model_r50c4_reg_tiny", "PascalVOC-Detection/reg/oicr_WSR_50_DC5_1x.yaml", TINY_R50 + C4, 37,
                         1, 40, 96, 96)
+    if "ref_yaml" in which:
+        case_ref_yaml("ref_yaml_cfgs")
+    if "roi_align_ref" in which:
+        case_roi_align_ref("roi_align_ref", 5)

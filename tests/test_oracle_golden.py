@@ -1,8 +1,6 @@
 """CPU tests (no GPU): pin the ORACLE against golden vectors produced by the unmodified reference
-(tests/golden/gen_golden.py) and against the reference ROIAlign C++ compiled in place (oracle/_ref).
+(tests/golden/gen_golden.py), including the outputs of the reference ROIAlign C++ compiled in place (oracle/_ref).
 fp32 everywhere; tolerances are written next to each check."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -49,34 +47,19 @@ def test_roi_align_random_fwd_bwd(al, sr):
 
 
 def test_roi_align_vs_compiled_reference():
-    """oracle/_ref = detectron2/layers/csrc/ROIAlign/ROIAlign_cpu.cpp compiled as-is."""
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("_ob", os.path.join(G.ROOT, "oracle", "build.py"))
-    ob = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ob)
-    so = ob.build_ref()
-    if so is None:
-        pytest.skip("oracle/_ref not built and /root/reference absent")
-    spec = importlib.util.spec_from_file_location("d2_roialign_ref", so)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    g = torch.Generator().manual_seed(5)
-    feat = torch.randn(2, 7, 19, 23, generator=g)
-    R = 64
-    x0 = torch.rand(R, generator=g) * 150
-    y0 = torch.rand(R, generator=g) * 120
-    rois = torch.stack([torch.randint(0, 2, (R,), generator=g).float(), x0, y0, x0 + torch.rand(R, generator=g) * 100,
-                        y0 + torch.rand(R, generator=g) * 90], 1)
+    """detectron2/layers/csrc/ROIAlign/ROIAlign_cpu.cpp compiled as-is (oracle/_ref), recorded by tests/golden/gen_golden.py
+    `roi_align_ref`: the oracle's forward bit for bit, its backward within fp32 scatter-sum order."""
+    d = G.load("roi_align_ref")
+    feat = torch.from_numpy(d["feat"])
+    rois = torch.from_numpy(d["rois"])
     for al in (False, True):
         for sr in (0, 1, 3):
+            key = "al%d_sr%d" % (int(al), sr)
             a = O.roi_align_forward(feat, rois, 7, 1 / 8.0, sr, al)
-            b = ref.roi_align_forward(feat, rois, 1 / 8.0, 7, 7, sr, al)
+            b = torch.from_numpy(d[key + "_out"])
             assert torch.equal(a, b), (al, sr, float((a - b).abs().max()))
-            go = torch.randn(a.shape, generator=g)
-            ga = O.roi_align_backward(go, rois, tuple(feat.shape), 7, 1 / 8.0, sr, al)
-            gb = ref.roi_align_backward(go, rois, 1 / 8.0, 7, 7, 2, 7, 19, 23, sr, al)
-            _close(ga, gb, rtol=1e-5, atol=1e-5)
+            ga = O.roi_align_backward(torch.from_numpy(d[key + "_gout"]), rois, tuple(feat.shape), 7, 1 / 8.0, sr, al)
+            _close(ga, d[key + "_gin"], rtol=1e-5, atol=1e-5)
 
 
 def test_iou_matcher_box2box_fbn():

@@ -1,16 +1,29 @@
-"""CPU tests of the host-side operator surface: registries, config loading of the UNMODIFIED reference yaml
-files (when /root/reference is present), state_dict keys/shapes equal to the reference's (through the
-reference-pinned oracle table), optimizer parameter groups, LR schedule, and loud failure off the path."""
+"""CPU tests of the host-side operator surface: registries, config loading of the reference's yaml files (through
+the merged configs recorded from the unmodified files, tests/golden/ref_yaml_cfgs.json), state_dict keys/shapes equal
+to the reference's (through the reference-pinned oracle table), optimizer parameter groups, LR schedule, and loud
+failure off the path."""
+import json
 import os
 
 import pytest
+import yaml
 import torch
 
 import golden_util as G
 from __graft_entry__ import load_package
 
 O = G.O
-REF_CFG = "/root/reference/projects/WSL/configs"
+REF_YAML_CFGS = os.path.join(G.GOLDEN, "ref_yaml_cfgs.json")
+
+
+def _ref_yaml(yaml_rel, tmp_path):
+    """the merged config the unmodified projects/WSL/configs/<yaml_rel> loads to (tests/golden/gen_golden.py `ref_yaml`),
+    written back as a yaml file under tmp_path -> its path"""
+    with open(REF_YAML_CFGS) as f:
+        rec = json.load(f)[yaml_rel]
+    path = tmp_path / os.path.basename(yaml_rel)
+    path.write_text(yaml.safe_dump(rec))
+    return str(path)
 
 
 @pytest.fixture(scope="module")
@@ -45,7 +58,6 @@ def test_full_size_r50_c4_shapes(pkg):
     assert model.backbone.output_shape()["res4"].stride == 16 and model.backbone.output_shape()["res4"].channels == 1024
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference yaml files only exist in the build container")
 @pytest.mark.parametrize("arch,yaml_rel", [("wsr50", "PascalVOC-Detection/oicr_WSR_50_DC5_1x.yaml"),
                                             ("wsr18", "PascalVOC-Detection/oicr_WSR_18_DC5_1x.yaml"),
                                             ("wsr101", "PascalVOC-Detection/oicr_WSR_101_DC5_1x.yaml"),
@@ -54,13 +66,11 @@ def test_full_size_r50_c4_shapes(pkg):
                                             ("wsr50", "PascalVOC-Detection/reg/oicr_WSR_50_DC5_1x.yaml"),
                                             ("wsr50", "PascalVOC-Detection/pcl_WSR_50_DC5_1x.yaml"),
                                             ("wsr50", "PascalVOC-Detection/wsddn_WSR_50_DC5_1x.yaml")])
-def test_unmodified_reference_yaml_loads(pkg, arch, yaml_rel):
+def test_unmodified_reference_yaml_loads(pkg, arch, yaml_rel, tmp_path):
     from drn_wsod_pytorch_amd.config import add_wsl_config, get_cfg
     from drn_wsod_pytorch_amd.modeling import build_model
 
-    path = os.path.join(REF_CFG, yaml_rel)
-    if not os.path.exists(path):
-        pytest.skip(yaml_rel)
+    path = _ref_yaml(yaml_rel, tmp_path)
     cfg = get_cfg()
     add_wsl_config(cfg)
     cfg.merge_from_file(path)
@@ -389,9 +399,11 @@ def test_samplers_and_batch_loader_match_reference_golden(pkg):
 
 def test_alias_layer_reference_import_names(tmp_path):
     """the reference's import lines for this path resolve to this package after aliases.install(); a model
-    builds from the reference's UNMODIFIED yaml through those names; names outside the path fail loudly."""
+    builds from the reference's yaml (its recorded merged config) through those names; names outside the path fail loudly."""
     import subprocess
     import sys
+
+    yaml_path = _ref_yaml("PascalVOC-Detection/oicr_WSR_18_DC5_1x.yaml", tmp_path)
 
     code = r'''
 import sys
@@ -415,13 +427,10 @@ import detectron2, wsl
 assert detectron2.layers.Conv2d is Conv2d and wsl.config.add_wsl_config is add_wsl_config
 assert "OICRROIHeads" in ROI_HEADS_REGISTRY and "GeneralizedRCNNWSL" in META_ARCH_REGISTRY
 assert "build_ws_resnet_backbone" in BACKBONE_REGISTRY
-import os
-yaml = "/root/reference/projects/WSL/configs/PascalVOC-Detection/oicr_WSR_18_DC5_1x.yaml"
-if os.path.exists(yaml):
-    cfg = get_cfg(); add_wsl_config(cfg); cfg.merge_from_file(yaml)
-    cfg.merge_from_list(["MODEL.DEVICE", "cpu", "MODEL.WEIGHTS", ""])
-    model = build_model(cfg)
-    assert type(model).__name__ == "GeneralizedRCNNWSL" and type(model.roi_heads).__name__ == "OICRROIHeads"
+cfg = get_cfg(); add_wsl_config(cfg); cfg.merge_from_file(%r)
+cfg.merge_from_list(["MODEL.DEVICE", "cpu", "MODEL.WEIGHTS", ""])
+model = build_model(cfg)
+assert type(model).__name__ == "GeneralizedRCNNWSL" and type(model.roi_heads).__name__ == "OICRROIHeads"
 from drn_wsod_pytorch_amd._cabi import DrnError
 import detectron2.evaluation as ev
 try:
@@ -444,6 +453,6 @@ except ImportError:
 A.uninstall()
 assert "detectron2" not in sys.modules
 print("ALIAS_OK", len(names))
-''' % (G.ROOT,)
+''' % (G.ROOT, yaml_path)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert "ALIAS_OK" in out.stdout, out.stdout + out.stderr

@@ -12,11 +12,11 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "tests rc=$?" >> $O/${tag}_tests.log
   tail -5 $O/${tag}_tests.log
 fi
-timeout 600 python bench.py ${BENCH_ARGS:-} > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+timeout 600 python bench.py --full ${BENCH_ARGS:-} > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 echo "bench rc=$?"; tail -c 600 $O/${tag}_bench.json
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   export TMPDIR=/tmp
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/${tag}_prof -- python $R/bench.py --steps 40 --no-cpu-baseline --no-side ${BENCH_ARGS:-} > $O/${tag}_prof_bench.json 2> $O/${tag}_prof.err)
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/${tag}_prof -- python $R/bench.py --full --steps 40 --no-cpu-baseline --no-side ${BENCH_ARGS:-} > $O/${tag}_prof_bench.json 2> $O/${tag}_prof.err)
   python tools/prof_summary.py $O/${tag}_prof $O/${tag}_kernel_stats.txt
   python tools/prof_timeline.py $O/${tag}_prof 2 > $O/${tag}_timeline.txt 2>&1
   rm -rf $O/${tag}_prof

@@ -11,4 +11,4 @@ done
 PROF=1 VARIANTS=1 timeout 300 python tools/pp8_probe.py fc7 res5_3x3 2>&1 | grep -v amdgpu.ids > $O/r6_05_pp8_probe.txt
 timeout 300 python tools/linear_bench.py 2>&1 | grep -v amdgpu.ids > $O/r6_05_linear.txt
 cat $O/r6_05_linear.txt
-timeout 600 python bench.py --no-side > $O/r6_05_bench.json 2> $O/r6_05_bench.err; tail -c 1500 $O/r6_05_bench.json
+timeout 600 python bench.py --full --no-side > $O/r6_05_bench.json 2> $O/r6_05_bench.err; tail -c 1500 $O/r6_05_bench.json

@@ -6,7 +6,7 @@ out=$1; n=${2:-2}
 run() {
   tag=$1; shift
   env "$@" timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus $n --steps 10 --warmup 2 --backend gloo --single-device --no-cpu-baseline > ${out}_${tag}.json 2> ${out}_${tag}.err
+    bench.py --full --gpus $n --steps 10 --warmup 2 --backend gloo --single-device --no-cpu-baseline > ${out}_${tag}.json 2> ${out}_${tag}.err
   echo "== $tag rc=$?"
   grep "\[bench\] fc6_kshard\|\[bench\] exchange" ${out}_${tag}.err | head -5
   python - <<PY
