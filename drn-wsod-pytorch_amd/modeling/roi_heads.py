@@ -32,6 +32,18 @@ from ..layers import Linear, ROIAlign, RoIPool, ShapeSpec, to_nhwc
 from ..registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from ..structures import Boxes, Instances
 
+# Counter-based dropout of the training step (drn_drop_rule, csrc/drn_common.h): fc6 draws its mask with seed + counter,
+# fc7 with seed + FC7_SEED_OFFSET + counter, and the logits pass advances the device-side counter by DROP_COUNTER_STEP.
+# (The two are the same number, so fc7's mask of one step is fc6's mask of the next wherever both layers have the same
+# width; changing either changes every step's masks.)
+FC7_SEED_OFFSET = 0x9E3779B1
+DROP_COUNTER_STEP = 0x9E3779B1
+
+
+def dropout_seeds(seed):
+    """(fc6 seed, fc7 seed) of one training step; the device-side counter is added to both inside the kernels"""
+    return seed, seed + FC7_SEED_OFFSET
+
 
 # ------------------------------------------------------------------------------------------------
 class Matcher:
@@ -225,6 +237,19 @@ class OICROutputLayers(_OutputLayersBase):
         input_size = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
         if cls_agnostic_bbox_reg:
             raise DrnError("class-agnostic box regression is not used by any DRN-WSOD config")
+        regresses = refine_reg  # cfg.WSL.REFINE_REG (one flag per branch) or this branch's flag
+        if isinstance(regresses, (list, tuple)):
+            regresses = regresses[refine_k] if refine_k is not None else any(regresses)
+        if regresses:
+            # drn_box_reg_loss computes the class-specific L1 loss (smooth-L1 with beta = 0) with weight 1, as every shipped
+            # config does (fast_rcnn.py:1146-1211); any other setting would train with the wrong loss
+            lw = loss_weight.get("loss_box_reg", 1.0) if isinstance(loss_weight, dict) else loss_weight
+            if box_reg_loss_type != "smooth_l1":
+                raise DrnError("BBOX_REG_LOSS_TYPE %r is not on the built path (only smooth_l1)" % (box_reg_loss_type,))
+            if smooth_l1_beta != 0.0:
+                raise DrnError("SMOOTH_L1_BETA %r is not on the built path (the box loss is L1: beta = 0)" % (smooth_l1_beta,))
+            if lw != 1.0:
+                raise DrnError("BBOX_REG_LOSS_WEIGHT %r is not on the built path (weight 1)" % (lw,))
         self.num_classes = num_classes
         self.cls_score = Linear(input_size, num_classes + 1)
         self.num_bbox_reg_classes = num_classes
@@ -817,20 +842,21 @@ class _HeadEngine:
             if getattr(self, "seed_dev", None) is None or self.seed_dev.device != dev:
                 self.seed_dev = torch.zeros((1,), dtype=torch.int64, device=dev)
             seed, seed_dev = torch.initial_seed() & 0xFFFFFFFFFFFF, self.seed_dev
+        seed6, seed7 = dropout_seeds(seed)
         if kshard and fc6_part is None:
             fc6_part = self._fc6_partials_kshard(pooled, M)
         if fc6_part is not None:  # the GEMM was issued by fc6_partials() (eagerly, in front of a captured graph)
-            ops.bias_act_fwd(fc6_part, M, D1, fc1.bias.data, True, masks[0] if masks else None, seed, drop_p,
+            ops.bias_act_fwd(fc6_part, M, D1, fc1.bias.data, True, masks[0] if masks else None, seed6, drop_p,
                              out=w["H1"], outT=w["H1T"] if training else None, seed_dev=seed_dev)
         else:
             self._linear_fwd(w["A"], sh["W1v"], M, D1, kp(K1), fc1.bias.data, True, w["H1"],
-                             w["H1T"] if training else None, masks[0] if masks else None, seed, drop_p, seed_dev)
+                             w["H1T"] if training else None, masks[0] if masks else None, seed6, drop_p, seed_dev)
         self._linear_fwd(w["H1"], sh["W2"], M, D2, kp(D1), fc2.bias.data, True, w["H2"], w["H2T"] if training else None,
-                         masks[1] if masks else None, seed + 0x9E3779B1, drop_p, seed_dev, fused=True)
+                         masks[1] if masks else None, seed7, drop_p, seed_dev, fused=True)
         bo, _ = self._seg[self.cols[0][0] + ".bias"]
         # (the logits pass has no dropout: given the counter it advances it - behind both dropout layers - instead of a
         # counter_add launch of its own on the heads' dependent chain)
-        logit_seed = 2654435761 if seed_dev is not None else 0
+        logit_seed = DROP_COUNTER_STEP if seed_dev is not None else 0
         # drn_mil_oicr_losses: the predictor's split-K reduce + bias, WSDDN and the refinement cascade in six launches
         # (nine as separate calls); taken when the heads are exactly cls / det / non-regressing OICR branches
         fuse_tail = (training and not csc and getattr(self, "fused_loss_tail", True) and h.refine_K > 0 and
