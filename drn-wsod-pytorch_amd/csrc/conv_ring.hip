@@ -24,34 +24,12 @@
 // Same LDS image (128-byte rows, slot ^= (row >> 1) & 7), 2 x 2 wave layout, MFMA (32x32x16 bf16) and k order per output
 // element as conv_nhwc_kernel: bit-identical to the tiled kernel for every tile shape here.
 #include "drn_common.h"
+#include "tune.h"
 #include "conv_params.h"
-
-#include <type_traits>
-#include <utility>
 
 namespace {
 
 using drn_conv::ConvParams;
-
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void tile_coords(int id, int tiles_m, int tiles_n, int& tm, int& tn, int GM) {
-  const int group_sz = GM * tiles_n;
-  const int g = id / group_sz, in_g = id - g * group_sz;
-  const int first_m = g * GM;
-  const int gm = tiles_m - first_m < GM ? tiles_m - first_m : GM;
-  tm = first_m + in_g % gm;
-  tn = in_g / gm;
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // LDS-only barrier: every LDS write / read of this wave is complete, global loads stay in flight
 #define RING_BARRIER()                                      \
@@ -256,34 +234,21 @@ int launch_ring(const ConvParams& p, hipStream_t st) {
   const int tiles = (int)((Mtot + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
   constexpr int smem = 2 * (BM + BN) * 128;
   auto k = conv_ring_kernel<BM, BN, D>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(tiles), dim3(256), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
 
-int g_conv_ring = 1;  // drn_tune(DRN_TUNE_CONV_RING = 23): 0 = off, 1 = tile by cost model, 64 / 128 pin 64x64 / 128x128
-
 }  // namespace
 
-// (hidden: called by drn_conv2d_nhwc_q / drn_tune in gemm_conv.hip)
-__attribute__((visibility("hidden"))) int drn_conv_ring_set(int v) {
-  const int old = g_conv_ring;
-  if (v == 0 || v == 1 || v == 64 || v == 128) g_conv_ring = v;
-  return old;
-}
-
+// (hidden: called by drn_conv2d_nhwc_q in gemm_conv.hip)
 // Runs the convolution on the register-ring kernels when it is in their class; DRN_ERR_UNSUPPORTED otherwise (the caller
 // then takes the kernels of gemm_conv.hip).  `cus` = compute units of the device; `tiles64_one` = 64x64 tiles of ONE image of
 // this layer: the class is decided on one image's geometry, so a layer takes the same kernel family - the same fp32 summation
 // order - whether its image runs alone or in a batch (graphed trunk groups vs eager steps, 2 ranks vs 1).
 __attribute__((visibility("hidden"))) int drn_conv_ring_try(const ConvParams& p, int dtype, int cus, long tiles64_one, hipStream_t st) {
-  if (!g_conv_ring || dtype != DRN_BF16 || p.out_dt != DRN_BF16 || (p.residual && p.res_dt != DRN_BF16)) return DRN_ERR_UNSUPPORTED;
+  if (!g_tune.conv_ring || dtype != DRN_BF16 || p.out_dt != DRN_BF16 || (p.residual && p.res_dt != DRN_BF16)) return DRN_ERR_UNSUPPORTED;
   if ((p.Cin & 63) || (p.Cout & 7) || p.KH * p.KW > 32 || (p.ldy & 7) || (p.residual && (p.ldres & 7))) return DRN_ERR_UNSUPPORTED;
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   if (!al16(p.X) || !al16(p.Wt) || !al16(p.Y) || (p.residual && !al16(p.residual)) || (p.ldw * 2) % 16 != 0) return DRN_ERR_UNSUPPORTED;
@@ -293,7 +258,7 @@ __attribute__((visibility("hidden"))) int drn_conv_ring_try(const ConvParams& p,
   // than CUs / 4 and up to ~4 rounds of 64x64 tiles per image - the res3 / res4 1x1 and 3x3 layers of a real-size image.
   // Single-slab 1x1s and the huge res2 maps are bound by their output traffic (the 128-wide tiles of gemm_conv.hip move fewer
   // operand bytes there); maps of fewer than 1024 pixels (the 224x224 benchmark image) stay in the small-map kernels' class.
-  int pick = g_conv_ring;
+  int pick = g_tune.conv_ring;
   if (pick == 1) {
     if (nslab < 4 || tiles64_one <= cus / 4 || tiles64_one > 4L * cus || (long)p.Ho * p.Wo < 1024) return DRN_ERR_UNSUPPORTED;
     pick = 64;

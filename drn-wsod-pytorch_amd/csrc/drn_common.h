@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #define DRN_OK 0
 #define DRN_ERR_ARG (-1)
 #define DRN_ERR_LAUNCH (-2)
@@ -126,3 +129,47 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + idx;
 }
+
+// byte offset of 16-byte k-slot `slot` of row `row` in an LDS image of 128-byte rows: slot ^= (row >> 1) & 7 keeps ds_read_b128
+// conflict-free (a 256-byte bank row holds two rows)
+__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
+
+// logical tile id -> (tm, tn), grouped so that a contiguous id range (one XCD's share) covers a
+// compact 2-D patch of tiles and re-reads its operand panels from that XCD's L2.
+__device__ __forceinline__ void tile_coords(int id, int tiles_m, int tiles_n, int& tm, int& tn, int GM = 4) {
+  const int group_sz = GM * tiles_n;
+  const int g = id / group_sz, in_g = id - g * group_sz;
+  const int first_m = g * GM;
+  const int gm = tiles_m - first_m < GM ? tiles_m - first_m : GM;
+  tm = first_m + in_g % gm;
+  tn = in_g / gm;
+}
+
+// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// Lets `kernel` take `bytes` of dynamic LDS (launches above the 48-KB default need the attribute raised first).  The runtime
+// call is made once per kernel: the kernels already raised are remembered in a small table (unlocked, like the launches
+// themselves: a lost race only repeats the call; a full table only stops caching).
+namespace drn_launch {
+inline bool allow_lds(const void* kernel, int bytes) {
+  struct Raised { const void* kernel; int bytes; };
+  static Raised raised[128];
+  static int n = 0;
+  for (int i = 0; i < n; ++i)
+    if (raised[i].kernel == kernel && raised[i].bytes >= bytes) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  if (n < 128) {
+    raised[n] = {kernel, bytes};
+    ++n;
+  }
+  return true;
+}
+}  // namespace drn_launch

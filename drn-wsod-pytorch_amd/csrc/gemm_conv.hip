@@ -16,10 +16,10 @@
 // F.conv2d + FrozenBatchNorm2d + relu_ + residual add (detectron2/layers/wrappers.py:94-99,
 // detectron2/layers/batch_norm.py:45-65, projects/WSL/wsl/modeling/backbone/resnet_ws.py:217-237).
 #include "drn_common.h"
+#include "tune.h"
 #include "conv_params.h"
 
-#include <type_traits>
-#include <utility>
+#include <limits.h>
 
 namespace {
 
@@ -83,9 +83,6 @@ __device__ __forceinline__ void mma_step64_fp8(f32x16_t& acc, const i32x4_t& a0,
   const i32x8_t B = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
   acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, acc, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
 }
-static int g_fp8_k64 = 1;  // drn_tune(DRN_TUNE_FP8_K64 = 13): 0 = the K = 16 non-scaled fp8 MFMA (A/B; bf16 rate)
-
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
 
 template <int ROWS>
 __device__ __forceinline__ void lds_store_tile(char* lds, const i32x4_t (&r)[ROWS / 32], int tid) {
@@ -176,16 +173,6 @@ struct ConvLoader {
 #ifndef CONV_DEPTH1
 #define CONV_DEPTH1 4  // register-ring depth of the single-LDS-stage 64x64 conv (98 VGPRs; 5 -> 114 > the 112 that co-reside with a GEMM workgroup)
 #endif
-// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // Register-staged mainloop (global -> ring of DEPTH register sets -> LDS -> MFMA).  The slab loop runs in two parts:
 // a STEADY STATE of whole groups of DEPTH slabs in which every slab issues the loads of slab i + DEPTH and stores the
 // registers of slab i + 1 unconditionally, then the last < 2 * DEPTH slabs with the bounds checks.  With the checks inside
@@ -281,17 +268,6 @@ __device__ __forceinline__ void mainloop(f32x16_t (&acc)[BM / 64][BN / 64], char
       const int i = base + decltype(dtag)::value;
       if (i < n) slab(dtag, i, std::false_type{});
     });
-}
-
-// logical tile id -> (tm, tn), grouped so that a contiguous id range (one XCD's share) covers a
-// compact 2-D patch of tiles and re-reads its operand panels from that XCD's L2.
-__device__ __forceinline__ void tile_coords(int id, int tiles_m, int tiles_n, int& tm, int& tn, int GM = 4) {
-  const int group_sz = GM * tiles_n;
-  const int g = id / group_sz, in_g = id - g * group_sz;
-  const int first_m = g * GM;
-  const int gm = tiles_m - first_m < GM ? tiles_m - first_m : GM;
-  tm = first_m + in_g % gm;
-  tn = in_g / gm;
 }
 
 template <int DT, int BM, int BN>
@@ -1331,7 +1307,6 @@ __global__ __launch_bounds__(512) void conv1x1_pp_kernel(ConvParams p) {
   }
 }
 
-static int g_conv_pp = 1;  // drn_tune(DRN_TUNE_CONV_PP = 24): 0 = never run a 1x1 conv on the 256x256 ping-pong GEMM mainloop
 
 // Epilogue of the tiled conv kernels: per-channel affine (+ residual, ReLU) and the store.  `tid` = 0..255 within the
 // four waves that own the accumulators; `active` = false for waves that only take part in the barriers (the second
@@ -2007,12 +1982,7 @@ int launch_gemm(const GemmParams& p, int splits, hipStream_t st) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   constexpr int smem = 2 * (BM + BN) * 128;
   auto k = gemm_nt_kernel<DT, BM, BN>;
-  static bool attr = false;
-  if (!attr && smem > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (smem > 48 * 1024 && !drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(tiles, splits), dim3(256), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2023,20 +1993,12 @@ int launch_gemm256(const GemmParams& p, int splits, hipStream_t st) {
   const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
   constexpr int smem = 2 * 512 * 128;
   auto k = gemm_nt256_kernel<DT, PIPE, PP, TN>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(tiles, splits), dim3(512), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
 
-static int g_pingpong = 1;  // drn_tune(DRN_TUNE_GEMM_PINGPONG = 12): bf16 256x256 GEMMs run the ping-pong mainloop
-static int g_tail_split = 1;  // drn_tune(DRN_TUNE_GEMM_TAIL_SPLIT): peel a nearly empty last round off persistent launches
-static int g_persistent = 1;  // drn_tune(DRN_TUNE_GEMM_PERSISTENT): 256x256 GEMMs with more work items than CUs loop
 
 static int cu_count() {
   static int n = 0;
@@ -2053,12 +2015,7 @@ template <int DT, int PP = 0, bool TN = false>
 int launch_gemm256p(const GemmParams& p, int nwg, hipStream_t st) {
   constexpr int smem = 2 * 512 * 128;
   auto k = gemm_nt256p_kernel<DT, PP, TN>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(nwg), dim3(512), smem, st, p, p, 0);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2067,12 +2024,7 @@ int launch_gemm256p(const GemmParams& p, int nwg, hipStream_t st) {
 static int launch_gemm256p_tn_sgdp(const GemmParams& p, int nwg, hipStream_t st) {
   constexpr int smem = 2 * 512 * 128;
   auto k = gemm_nt256p_kernel<DRN_BF16, 1, true, false, true>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(nwg), dim3(512), smem, st, p, p, 0);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2081,12 +2033,7 @@ static int launch_gemm256p_tn_sgdp(const GemmParams& p, int nwg, hipStream_t st)
 static int launch_gemm256p_pair(const GemmParams& p0, const GemmParams& p1, int nwg, int wg0, hipStream_t st) {
   constexpr int smem = 2 * 512 * 128;
   auto k = gemm_nt256p_kernel<DRN_BF16, 1, false, true>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(nwg), dim3(512), smem, st, p0, p1, wg0);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2098,27 +2045,17 @@ static int launch_gemm256p_pair(const GemmParams& p0, const GemmParams& p1, int 
 // round 2 and are WORSE: FETCH_SIZE 734 MB vs 646 MB (profiles/r2_04_pmc_fc6_dw_gm8.json vs r2_03_..._gm4.json): the
 // 8-MB A operand (dP1^T) does not stay in the 4-MB L2 between rounds and is re-read 6 times per XCD (mostly from the
 // Infinity Cache - the counter sits on the fabric side of L2, so it counts those too); step rate unchanged.  4 stays.
-static int g_group_rows = 0;  // drn_tune(DRN_TUNE_GEMM_GROUP_ROWS): 0 = default (4)
 static int gemm256_group_rows(int M, int N, int splits) {
   (void)M; (void)N; (void)splits;
-  return g_group_rows > 0 ? g_group_rows : 4;
+  return g_tune.gemm_group_rows > 0 ? g_tune.gemm_group_rows : 4;
 }
 
 // number of workgroups of the persistent launch, or 0 when the one-tile grid should be used
-static int g_sgdp_ep4 = 1;  // drn_tune(DRN_TUNE_SGDP_EPILOGUE = 20): the fused dW + SGD launch's tile epilogue reads LDS four pieces at a time
-static int g_nwg = 0;  // drn_tune(DRN_TUNE_GEMM_NWG = 18): resident workgroups of persistent launches (0 = one per CU); for launches
-                       // on a CU-masked stream (the GEMM on a subset of the CUs, an HBM-bound kernel on the others)
 static int persistent_grid(long total) {
-  if (!g_persistent) return 0;
-  const int nwg = g_nwg > 0 ? g_nwg : (cu_count() / 8) * 8;
+  if (!g_tune.gemm_persistent) return 0;
+  const int nwg = g_tune.gemm_nwg > 0 ? g_tune.gemm_nwg : (cu_count() / 8) * 8;
   return (nwg >= 8 && total > nwg) ? nwg : 0;
 }
-
-static int g_conv_ksplit = 1;  // drn_tune(DRN_TUNE_CONV_KSPLIT): 0 = never use the 32x32 wave-K-split kernel
-static int g_conv_patch = 1;  // drn_tune(DRN_TUNE_CONV_PATCH): 0 = never use conv3x3_c64_kernel; > 1 = minimum pixels per image
-static long g_conv_patch_min = 32768;
-static int g_conv_k2_tiles = -1;  // drn_tune(DRN_TUNE_CONV_K2_TILES): largest 64x64-tile count of ONE image for the two-K-group kernel (-1 = 2 x CUs, 0 = off)
-static int g_conv_ks_tiles = 0;  // drn_tune(DRN_TUNE_CONV_KS_TILES): largest 64x64-tile count of ONE image that still takes it (0 = CUs / 4)
 
 template <int DT, bool K64 = true>
 int launch_conv_ks(const ConvParams& p, hipStream_t st) {
@@ -2132,28 +2069,17 @@ int launch_conv_ks(const ConvParams& p, hipStream_t st) {
 static int launch_conv3x3_c64(const ConvParams& p, hipStream_t st) {
   const int tiles = p.Nb * ((p.Ho + P3_TH - 1) / P3_TH) * ((p.Wo + P3_TW - 1) / P3_TW);
   constexpr int smem = P3_PATCH + P3_WTS;  // 117 KB: one workgroup per CU
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)conv3x3_c64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv3x3_c64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
   const int nwg = tiles < cu_count() ? tiles : cu_count();  // persistent: one workgroup per CU walks the pixel blocks
-  if (p.residual) hipLaunchKernelGGL(conv3x3_c64_kernel<true>, dim3(nwg), dim3(256), smem, st, p);
-  else hipLaunchKernelGGL(conv3x3_c64_kernel<false>, dim3(nwg), dim3(256), smem, st, p);
+  auto k = !p.residual ? conv3x3_c64_kernel<false> : conv3x3_c64_kernel<true>;
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
+  hipLaunchKernelGGL(k, dim3(nwg), dim3(256), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
 
 template <bool RES, bool PW, bool POOL>
 static int launch_c64_variant(const ConvParams& p, int nwg, int smem, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)conv3x3_c64_kernel<RES, PW, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)conv3x3_c64_kernel<RES, PW, POOL>, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL((conv3x3_c64_kernel<RES, PW, POOL>), dim3(nwg), dim3(256), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2184,12 +2110,7 @@ static int launch_conv1x1_pp(const ConvParams& p, hipStream_t st) {
   const long Mtot = (long)p.Nb * p.Ho * p.Wo;
   const int tiles = (int)((Mtot + 255) / 256) * ((p.Cout + 255) / 256);
   constexpr int smem = 2 * 512 * 128;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)conv1x1_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)conv1x1_pp_kernel, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(conv1x1_pp_kernel, dim3(tiles), dim3(512), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2201,12 +2122,7 @@ int launch_conv(const ConvParams& p, hipStream_t st) {
   const int tiles = ((Mtot + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
   constexpr int smem = ((BM == 64 && BN == 64) ? 1 : 2) * (BM + BN) * 128;
   auto k = conv_nhwc_kernel<DT, BM, BN, K64>;
-  static bool attr = false;
-  if (!attr && smem > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (smem > 48 * 1024 && !drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(tiles), dim3(256), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
@@ -2219,7 +2135,7 @@ int launch_conv(const ConvParams& p, hipStream_t st) {
 static long tail_split_main_cols(int M, int N, int splits, int nwg) {
   const int tm = (M + 255) / 256, tn = (N + 255) / 256;
   const long wg256 = (long)tm * tn * splits, rem = wg256 % nwg;
-  if (!g_tail_split || splits != 1 || rem == 0 || rem * 8 > (long)nwg * 3) return N;
+  if (!g_tune.gemm_tail_split || splits != 1 || rem == 0 || rem * 8 > (long)nwg * 3) return N;
   int a = nwg, b = tm;
   while (b) { const int t = a % b; a = b; b = t; }
   const int step = nwg / a;                   // tile columns per exact multiple of nwg tiles
@@ -2228,107 +2144,86 @@ static long tail_split_main_cols(int M, int N, int splits, int nwg) {
   return N;
 }
 
-static int g_force_tile = 0;  // 0 = heuristic; 64 / 128 / 256 pin the tile (tuning + tests)
-
 // conv_ring.hip: the register-ring kernels (bf16, Cin % 64 == 0); DRN_ERR_UNSUPPORTED outside their class
 __attribute__((visibility("hidden"))) int drn_conv_ring_try(const ConvParams& p, int dtype, int cus, long tiles64_one, hipStream_t st);
-__attribute__((visibility("hidden"))) int drn_conv_ring_set(int v);
 // pp8.hip: the eight-wave 128x128 kernel (bf16, Cin % 64 == 0); DRN_ERR_UNSUPPORTED outside its class
 __attribute__((visibility("hidden"))) int drn_pp8_conv_try(const ConvParams& p, int dtype, int cus, hipStream_t st);
-__attribute__((visibility("hidden"))) int drn_pp8_set(int knob, int v);
+
+DrnTune g_tune;  // (tune.h)
+
+// drn_tune's knobs: {id, field of g_tune, accept}.  accept(v, cur) gives what the field holds after drn_tune(id, v) - `cur` where
+// the knob ignores v; drn_tune returns the field's previous value.  Rows without a field do all of it themselves: accept(v, 0)
+// is drn_tune's result.  The rules differ knob by knob on purpose (tests and tools rely on them): tests/test_tune_cpu.py.
+namespace {
+struct TuneRow { int id; int DrnTune::*field; int (*accept)(int v, int cur); };
+int tune_truthy(int v, int) { return v != 0; }
+template <int LO, int HI> int tune_range(int v, int cur) { return v >= LO && v <= HI ? v : cur; }
+template <int... S> int tune_one_of(int v, int cur) { return ((v == S) || ...) ? v : cur; }
+const TuneRow kTuneRows[] = {
+    {1, &DrnTune::gemm_persistent, tune_truthy},
+    {2, &DrnTune::sgd_grid, tune_range<8, 65535>},
+    {3, &DrnTune::gemm_group_rows, tune_range<0, 64>},
+    {4, &DrnTune::roi_map64, [](int v, int cur) { return v == 1 ? 512 : tune_one_of<0, 256, 512, 1024>(v, cur); }},
+    {5, &DrnTune::conv_ksplit, tune_truthy},
+    {6, &DrnTune::gemm_tail_split, tune_truthy},
+    {7, &DrnTune::conv_ks_tiles, tune_range<0, INT_MAX>},
+    {8, &DrnTune::conv_k2_tiles, [](int v, int) { return v; }},
+    {9, nullptr, [](int v, int) {  // returns the pixel threshold while the kernel is on, 0 while it is off
+       const int old = g_tune.conv_patch ? g_tune.conv_patch_min : 0;
+       g_tune.conv_patch = v != 0;
+       if (v > 1) g_tune.conv_patch_min = v;
+       return old;
+     }},
+    {10, &DrnTune::roi_cpb, [](int v, int cur) { return v >= 1 && v <= 64 && (v & (v - 1)) == 0 ? v : cur; }},
+    {11, &DrnTune::roi_prefetch, tune_truthy},
+    {12, &DrnTune::gemm_pingpong, [](int v, int) { return v < 0 ? 0 : v; }},
+    {13, &DrnTune::fp8_k64, tune_truthy},
+    {14, &DrnTune::roi_map64_a, tune_truthy},
+    {15, &DrnTune::roi_lds_kb, tune_range<60, 154>},
+    {18, &DrnTune::gemm_nwg, [](int v, int cur) { return v >= 0 && v % 8 == 0 && v <= 4096 ? v : cur; }},
+    {19, nullptr, [](int v, int) {  // 3 = setting 1 with ONE sub-group of ROIs per walking-kernel block (tests)
+       const int old = g_tune.roi_lane;
+       g_tune.roi_walk_nsg = v == 3 ? 1 : 2;
+       g_tune.roi_lane = v < 0 ? 0 : v == 3 ? 1 : v > 2 ? 2 : v;
+       return old;
+     }},
+    {20, &DrnTune::sgdp_ep4, tune_truthy},
+    {22, &DrnTune::roi_lane_reps, tune_range<0, 64>},
+    {23, &DrnTune::conv_ring, tune_one_of<0, 1, 64, 128>},
+    {24, &DrnTune::conv_pp, tune_range<0, INT_MAX>},
+    {25, &DrnTune::pp8, tune_range<0, 2>},
+    {26, &DrnTune::pp8_stages, tune_one_of<3, 4, 5>},
+    {27, &DrnTune::pp8_var, [](int v, int cur) { return v >= 0 && v <= 10 && (v & 3) != 3 ? v : cur; }},
+    {28, nullptr, [](int, int) { return drn_tune_pp8_profile_dump(); }},
+    {29, &DrnTune::pp8_wide, tune_range<0, 2>},
+    {30, &DrnTune::pp8_wvar, tune_one_of<0, 1, 4, 5, 8, 9, 13>},
+    {31, nullptr, [](int v, int) {  // 0..2 = the setting; 10 / 11 = profile builds on / off; 12 = print and clear their counters
+       const int old = g_tune.roi_st;
+       g_tune.roi_st = tune_range<0, 2>(v, old);
+       if (v == 10 || v == 11) g_tune.roi_st_prof = v == 10;
+       if (v == 12 && drn_tune_roi_st_profile_dump() != 0) return -1;
+       return old;
+     }},
+    {32, &DrnTune::msm_wave, tune_truthy},
+};
+}  // namespace
 
 extern "C" {
 
 // tuning/test hook: pin the GEMM tile (0 restores the heuristic). Returns the previous value.
 int drn_gemm_set_tile(int tile) {
-  const int old = g_force_tile;
-  if (tile == 0 || tile == 64 || tile == 128 || tile == 255 || tile == 256) g_force_tile = tile;
+  const int old = g_tune.force_tile;
+  if (tile == 0 || tile == 64 || tile == 128 || tile == 255 || tile == 256) g_tune.force_tile = tile;
   return old;
 }
 
 // tuning knobs (A/B measurements and tests; defaults are the measured best).  Returns the previous value or -1.
-__attribute__((visibility("hidden"))) int drn_sgd_set_grid(int blocks_x);  // head.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_map64(int on);        // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_chunks(int cpb);      // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_prefetch(int on);     // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_map64_a(int on);      // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_lds_kb(int kb);       // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_lane(int on);         // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_lane_reps(int reps);  // pool.hip
-__attribute__((visibility("hidden"))) int drn_roi_set_st(int on);             // pool.hip
-__attribute__((visibility("hidden"))) int drn_msm_set_wave(int on);           // head.hip
 int drn_tune(int knob, int value) {
-  if (knob == 1) {  // DRN_TUNE_GEMM_PERSISTENT
-    const int old = g_persistent;
-    g_persistent = value != 0;
-    return old;
-  }
-  if (knob == 2) return drn_sgd_set_grid(value);  // DRN_TUNE_SGD_GRID
-  if (knob == 4) return drn_roi_set_map64(value);  // DRN_TUNE_ROI_MAP64
-  if (knob == 10) return drn_roi_set_chunks(value);    // DRN_TUNE_ROI_CPB
-  if (knob == 11) return drn_roi_set_prefetch(value);  // DRN_TUNE_ROI_PREFETCH
-  if (knob == 14) return drn_roi_set_map64_a(value);   // DRN_TUNE_ROI_MAP64_A
-  if (knob == 15) return drn_roi_set_lds_kb(value);    // DRN_TUNE_ROI_LDS_KB
-  if (knob == 19) return drn_roi_set_lane(value);      // DRN_TUNE_ROI_LANE
-  if (knob == 22) return drn_roi_set_lane_reps(value);  // DRN_TUNE_ROI_LANE_REPS
-  if (knob == 31) return drn_roi_set_st(value);         // DRN_TUNE_ROI_ST
-  if (knob == 32) return drn_msm_set_wave(value);       // DRN_TUNE_MSM_WAVE
-  if (knob == 5) {  // DRN_TUNE_CONV_KSPLIT
-    const int old = g_conv_ksplit;
-    g_conv_ksplit = value != 0;
-    return old;
-  }
-  if (knob == 9) {  // DRN_TUNE_CONV_PATCH
-    const int old = g_conv_patch ? (int)g_conv_patch_min : 0;
-    g_conv_patch = value != 0;
-    if (value > 1) g_conv_patch_min = value;
-    return old;
-  }
-  if (knob == 8) {  // DRN_TUNE_CONV_K2_TILES
-    const int old = g_conv_k2_tiles;
-    g_conv_k2_tiles = value;
-    return old;
-  }
-  if (knob == 7) {  // DRN_TUNE_CONV_KS_TILES
-    const int old = g_conv_ks_tiles;
-    if (value >= 0) g_conv_ks_tiles = value;
-    return old;
-  }
-  if (knob == 6) {  // DRN_TUNE_GEMM_TAIL_SPLIT
-    const int old = g_tail_split;
-    g_tail_split = value != 0;
-    return old;
-  }
-  if (knob == 12) {  // DRN_TUNE_GEMM_PINGPONG
-    const int old = g_pingpong;
-    g_pingpong = value < 0 ? 0 : value;
-    return old;
-  }
-  if (knob == 13) {  // DRN_TUNE_FP8_K64
-    const int old = g_fp8_k64;
-    g_fp8_k64 = value != 0;
-    return old;
-  }
-  if (knob == 18) {  // DRN_TUNE_GEMM_NWG
-    const int old = g_nwg;
-    if (value >= 0 && value % 8 == 0 && value <= 4096) g_nwg = value;
-    return old;
-  }
-  if (knob == 20) {  // DRN_TUNE_SGDP_EPILOGUE
-    const int old = g_sgdp_ep4;
-    g_sgdp_ep4 = value != 0;
-    return old;
-  }
-  if (knob == 23) return drn_conv_ring_set(value);  // DRN_TUNE_CONV_RING
-  if (knob >= 25 && knob <= 30) return drn_pp8_set(knob, value);  // DRN_TUNE_PP8, _STAGES, _VARIANT, _PROFILE, _WIDE, _WIDE_VARIANT
-  if (knob == 24) {  // DRN_TUNE_CONV_PP
-    const int old = g_conv_pp;
-    if (value >= 0) g_conv_pp = value;
-    return old;
-  }
-  if (knob == 3) {  // DRN_TUNE_GEMM_GROUP_ROWS
-    const int old = g_group_rows;
-    if (value >= 0 && value <= 64) g_group_rows = value;
+  for (const TuneRow& row : kTuneRows) {
+    if (row.id != knob) continue;
+    if (!row.field) return row.accept(value, 0);
+    const int old = g_tune.*row.field;
+    g_tune.*row.field = row.accept(value, old);
     return old;
   }
   return -1;
@@ -2339,7 +2234,7 @@ int drn_tune(int knob, int value) {
 long drn_gemm_nt_main_cols(int M, int N, int splits) {
   if (M <= 0 || N <= 0 || splits < 1) return N;
   const long wg256 = (long)((M + 255) / 256) * ((N + 255) / 256) * splits;
-  if (!((g_force_tile == 256 || (g_force_tile == 0 && wg256 >= 192)))) return N;
+  if (!((g_tune.force_tile == 256 || (g_tune.force_tile == 0 && wg256 >= 192)))) return N;
   const int nwg = persistent_grid(wg256);
   return nwg ? tail_split_main_cols(M, N, splits, nwg) : N;
 }
@@ -2367,7 +2262,7 @@ int drn_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, long
   // 256x256 LDS-DMA kernel when it can put >= ~3/4 of the 256 CUs to work (1 workgroup of 128 KB LDS per CU);
   // otherwise the 128x128 / 64x64 register-staged kernels (more, smaller workgroups)
   const long wg256 = (long)((M + 255) / 256) * ((N + 255) / 256) * splits;
-  const int force = g_force_tile;
+  const int force = g_tune.force_tile;
   if (force == 255)  // the non-pipelined 256 kernel (kept for A/B comparison)
     return dtype == DRN_BF16 ? launch_gemm256<DRN_BF16, false>(p, splits, st) : launch_gemm256<DRN_F32, false>(p, splits, st);
   if ((force == 256 || (force == 0 && wg256 >= 192)) && (((uintptr_t)C) & 3) == 0) {
@@ -2393,14 +2288,14 @@ int drn_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, long
         if (rc != DRN_OK) return rc;
         p.N = (int)n0;
       }
-      if (dtype == DRN_BF16 && g_pingpong == 1) return launch_gemm256p<DRN_BF16, 1>(p, nwg, st);
-      if (dtype == DRN_BF16 && g_pingpong == 2) return launch_gemm256p<DRN_BF16, 2>(p, nwg, st);
-      if (dtype == DRN_BF16 && g_pingpong == 3) return launch_gemm256p<DRN_BF16, 3>(p, nwg, st);
+      if (dtype == DRN_BF16 && g_tune.gemm_pingpong == 1) return launch_gemm256p<DRN_BF16, 1>(p, nwg, st);
+      if (dtype == DRN_BF16 && g_tune.gemm_pingpong == 2) return launch_gemm256p<DRN_BF16, 2>(p, nwg, st);
+      if (dtype == DRN_BF16 && g_tune.gemm_pingpong == 3) return launch_gemm256p<DRN_BF16, 3>(p, nwg, st);
       return dtype == DRN_BF16 ? launch_gemm256p<DRN_BF16>(p, nwg, st) : launch_gemm256p<DRN_F32>(p, nwg, st);
     }
-    if (dtype == DRN_BF16 && g_pingpong == 1) return launch_gemm256<DRN_BF16, true, 1>(p, splits, st);
-    if (dtype == DRN_BF16 && g_pingpong == 2) return launch_gemm256<DRN_BF16, true, 2>(p, splits, st);
-    if (dtype == DRN_BF16 && g_pingpong == 3) return launch_gemm256<DRN_BF16, true, 3>(p, splits, st);
+    if (dtype == DRN_BF16 && g_tune.gemm_pingpong == 1) return launch_gemm256<DRN_BF16, true, 1>(p, splits, st);
+    if (dtype == DRN_BF16 && g_tune.gemm_pingpong == 2) return launch_gemm256<DRN_BF16, true, 2>(p, splits, st);
+    if (dtype == DRN_BF16 && g_tune.gemm_pingpong == 3) return launch_gemm256<DRN_BF16, true, 3>(p, splits, st);
     return dtype == DRN_BF16 ? launch_gemm256<DRN_BF16, true>(p, splits, st) : launch_gemm256<DRN_F32, true>(p, splits, st);
   }
   // 64x64 tiles (4x the workgroups) when 128x128 tiles would not even give every CU one workgroup: these launches are
@@ -2448,7 +2343,7 @@ int drn_gemm_nt_pair(const void* A0, const void* B0, void* C0, int M0, int N0, i
     return rc != DRN_OK ? rc
                         : drn_gemm_nt(A1, B1, C1, M1, N1, K1, lda1, ldb1, ldc1, DRN_BF16, DRN_F32, splits1, stride1, accumulate1, stream);
   };
-  if (M0 <= 0 || N0 <= 0 || M1 <= 0 || N1 <= 0 || !g_persistent || g_pingpong != 1 || g_force_tile == 64 || g_force_tile == 128)
+  if (M0 <= 0 || N0 <= 0 || M1 <= 0 || N1 <= 0 || !g_tune.gemm_persistent || g_tune.gemm_pingpong != 1 || g_tune.force_tile == 64 || g_tune.force_tile == 128)
     return two_calls();
   auto ok = [](const void* A, const void* B, void* C, int K, long lda, long ldb, int splits, int acc) {
     return A && B && C && K > 0 && (K * 2) % 128 == 0 && (lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && lda >= K && ldb >= K &&
@@ -2492,7 +2387,7 @@ int drn_gemm_tn_sgd(const void* A, const void* Bt, void* grad_bucket, int M, int
   // shape class of the pipelined update: whole K slabs (one 8-row chunk of the previous tile rides in each; with fewer than 32
   // slabs - fewer than 2048 proposals - the rest follows the mainloop, exposed), whole tiles, a bf16 shadow, 32-bit byte
   // offsets, enough tiles for the persistent grid, the ping-pong mainloop
-  if (K < 128 || (K & 63) || (M & 255) || (N & 255) || !shadow || (ldc & 7) || (ld_w & 3) || g_pingpong != 1 ||
+  if (K < 128 || (K & 63) || (M & 255) || (N & 255) || !shadow || (ldc & 7) || (ld_w & 3) || g_tune.gemm_pingpong != 1 ||
       (long)M * ld_w * 4 >= 0xFFFFFFF0L || (long)K * ldb * 2 >= 0xFFFFFFF0L)
     return DRN_ERR_UNSUPPORTED;
   const long tiles = (long)(M / 256) * (N / 256);
@@ -2501,7 +2396,7 @@ int drn_gemm_tn_sgd(const void* A, const void* Bt, void* grad_bucket, int M, int
   GemmParams p{(const char*)A, (const char*)Bt, (float*)grad_bucket, M, N, K, lda, ldb, ldc, K * 2 / 128, 0, 0,
                weights, momentum_buf, (bf16_t*)shadow, (const SgdSeg*)seg_dev, momentum, grad_scale, first_step};
   p.sgd_ld = ld_w;
-  p.c_bf16 = g_sgdp_ep4 ? 3 : 1;  // (bit 1: four-at-a-time epilogue reads)
+  p.c_bf16 = g_tune.sgdp_ep4 ? 3 : 1;  // (bit 1: four-at-a-time epilogue reads)
   p.nsplit = 1;
   p.gm = gemm256_group_rows(M, N, 1);
   p.kb_rows = kb_rows;
@@ -2519,7 +2414,7 @@ int drn_conv3x3_pw_nhwc(const void* x, const void* w2, const float* scale2, cons
                         long ldw2, long ldw3, float res_mult, int relu3, int pool, void* stream) {
   if (!x || !w2 || !y || Nb <= 0 || H <= 0 || W <= 0) return DRN_ERR_ARG;
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (!g_conv_patch || (long)H * W < g_conv_patch_min || (long)Nb * H * W * 128 >= 0xFFFFFFF0L ||
+  if (!g_tune.conv_patch || (long)H * W < g_tune.conv_patch_min || (long)Nb * H * W * 128 >= 0xFFFFFFF0L ||
       ldw2 < 9 * 64 || (w3 && ldw3 < 64) || (ldw2 * 2) % 16 != 0 || (w3 && (ldw3 * 2) % 16 != 0) || !al16(x) || !al16(w2) ||
       (w3 && !al16(w3)) || !al16(y) || (residual && !al16(residual)) || (!w3 && !pool) ||
       (pool && (!(w3 ? relu3 : relu2) || H < 2 || W < 2)))
@@ -2547,7 +2442,7 @@ int drn_conv2d_nhwc_q(const void* x, const void* w, void* y, const float* scale,
   const int Ktot = KH * KW * Cin;
   if (ldw * es < ((Ktot * es + 127) / 128) * 128) return DRN_ERR_ARG;  // weight rows zero-padded to 128-B slabs
   ConvParams p{(const char*)x, (const char*)w, (char*)y, scale, bias, (const char*)residual, Nb, H, W, Cin, Ho, Wo,
-               Cout, KH, KW, stride, pad, dil, relu, Ktot, ldw, ldy, ldres, out_dtype, res_dtype, res_mult, g_fp8_k64};
+               Cout, KH, KW, stride, pad, dil, relu, Ktot, ldw, ldy, ldres, out_dtype, res_dtype, res_mult, g_tune.fp8_k64};
   hipStream_t st = (hipStream_t)stream;
   const long Mtot = (long)Nb * Ho * Wo;
   const bool small = ((Mtot + 127) / 128) * ((Cout + 127) / 128) < 128;
@@ -2560,11 +2455,11 @@ int drn_conv2d_nhwc_q(const void* x, const void* w, void* y, const float* scale,
   const long tiles64 = (((long)Ho * Wo + 63) / 64) * ((Cout + 63) / 64);
   // (round 2, tools/conv_bench.py at 800x1216: up to one 64x64 tile per CU the 36-slab res4 3x3 still gains, 23.1 ->
   // 20.5 us, while layers with few slabs lose - the 9-slab stem 3x3 8.6 -> 9.7 us at 224x224: deep K only)
-  const long ks_max = g_conv_ks_tiles > 0 ? g_conv_ks_tiles : (nslab >= 32 ? cu_count() : cu_count() / 4);
+  const long ks_max = g_tune.conv_ks_tiles > 0 ? g_tune.conv_ks_tiles : (nslab >= 32 ? cu_count() : cu_count() / 4);
   // LDS-resident patch + weights for the 64-channel 3x3 layers of large maps (conv3x3_c64_kernel; 117 KB of LDS, so only
   // where the trunk is not meant to share CUs with the heads' GEMMs: maps of >= 32k pixels)
-  if (g_conv_patch && dtype == DRN_BF16 && out_dtype == DRN_BF16 && (!residual || res_dtype == DRN_BF16) && Cin == 64 &&
-      Cout == 64 && KH == 3 && KW == 3 && stride == 1 && dil == 1 && pad == 1 && (long)Ho * Wo >= g_conv_patch_min &&
+  if (g_tune.conv_patch && dtype == DRN_BF16 && out_dtype == DRN_BF16 && (!residual || res_dtype == DRN_BF16) && Cin == 64 &&
+      Cout == 64 && KH == 3 && KW == 3 && stride == 1 && dil == 1 && pad == 1 && (long)Ho * Wo >= g_tune.conv_patch_min &&
       (ldy & 7) == 0 && (((uintptr_t)y) & 15) == 0 && (!residual || ((ldres & 7) == 0 && (((uintptr_t)residual) & 15) == 0)) &&
       (ldw * 2) % 16 == 0 && (((uintptr_t)w) & 15) == 0)
     return launch_conv3x3_c64(p, st);
@@ -2577,18 +2472,18 @@ int drn_conv2d_nhwc_q(const void* x, const void* w, void* y, const float* scale,
   // (>= 16 slabs: 2048 -> 512 at 118 tiles 47 -> 44 us, but 128 -> 512 at 120 tiles 12 -> 15 us); at 59-60 tiles (res4 of the
   // C4 trunk, the DC5 trunk's 1x1s to 256 channels) the small tiles win; a 64-channel output wastes three quarters of the
   // tile.  Decided on ONE image's geometry; same bits as the tiled kernels either way.
-  if (drn_pp8_set(25, -1) == 2) {  // (A/B pin: every layer in the eight-wave kernel's class takes it)
+  if (g_tune.pp8 == 2) {  // (A/B pin: every layer in the eight-wave kernel's class takes it)
     const int rc = drn_pp8_conv_try(p, dtype, cu_count(), st);
     if (rc != DRN_ERR_UNSUPPORTED) return rc;
   }
-  const bool pp_ok = g_conv_pp && dtype == DRN_BF16 && out_dtype == DRN_BF16 && (!residual || res_dtype == DRN_BF16) && KH == 1 &&
+  const bool pp_ok = g_tune.conv_pp && dtype == DRN_BF16 && out_dtype == DRN_BF16 && (!residual || res_dtype == DRN_BF16) && KH == 1 &&
                      KW == 1 && stride == 1 && pad == 0 && (Cin & 63) == 0 && (Cout & 7) == 0 && (ldy & 3) == 0 &&
                      (!residual || (ldres & 3) == 0) &&
                      (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)residual) & 15) == 0 && (ldw * 2) % 16 == 0 &&
                      (long)Cout * ldw * 2 < 0xFFFFFFF0L;
   const long t256 = (((long)Ho * Wo + 255) / 256) * ((Cout + 255) / 256);
   // (1) >= 3/4 of the CUs' worth of 256x256 tiles: the ping-pong GEMM mainloop, whatever K
-  if (pp_ok && (g_conv_pp > 1 ? t256 >= g_conv_pp : (Cout >= 256 && t256 >= 192))) return launch_conv1x1_pp(p, st);
+  if (pp_ok && (g_tune.conv_pp > 1 ? t256 >= g_tune.conv_pp : (Cout >= 256 && t256 >= 192))) return launch_conv1x1_pp(p, st);
   // (2) the eight-wave 128x128 / 256x128 kernel (pp8.hip; round 6): layers with too few 256x256 tiles for (1) - the 3x3s of
   // res4 / res5, the 1x1s to 256 / 512 channels of the dilated-C5 trunk, the C4 trunk's 1x1s to 1024 channels
   {
@@ -2596,19 +2491,19 @@ int drn_conv2d_nhwc_q(const void* x, const void* w, void* y, const float* scale,
     if (rc != DRN_ERR_UNSUPPORTED) return rc;
   }
   // (3) 100-191 tiles of 256x256 with a long K loop (round 5's class; reached when (2) is switched off)
-  if (pp_ok && g_conv_pp == 1 && Cout >= 256 && t256 >= 100 && (Cin >> 6) >= 16) return launch_conv1x1_pp(p, st);
+  if (pp_ok && g_tune.conv_pp == 1 && Cout >= 256 && t256 >= 100 && (Cin >> 6) >= 16) return launch_conv1x1_pp(p, st);
   {
     const int rc = drn_conv_ring_try(p, dtype, cu_count(), tiles64, st);
     if (rc != DRN_ERR_UNSUPPORTED) return rc;
   }
   // two K-groups per 64x64 tile (conv_nhwc_k2_kernel): mid-size layers - more 64x64 tiles than the wave-K-split kernel
   // takes, at most one per CU (the kernel keeps one 512-thread workgroup per CU) - with an even slab count >= 8
-  const long k2_max = g_conv_k2_tiles >= 0 ? g_conv_k2_tiles : cu_count();
+  const long k2_max = g_tune.conv_k2_tiles >= 0 ? g_tune.conv_k2_tiles : cu_count();
   if ((nslab & 1) == 0 && nslab >= 8 && tiles64 > cu_count() / 4 && tiles64 <= k2_max && Nb <= 64)
     return dtype == DRN_BF16 ? launch_conv_k2<DRN_BF16>(p, st)
            : dtype == DRN_FP8 ? (p.fp8_k64 ? launch_conv_k2<DRN_FP8>(p, st) : launch_conv_k2<DRN_FP8, false>(p, st))
                               : launch_conv_k2<DRN_F32>(p, st);
-  if (g_conv_ksplit && tiles64 <= ks_max && nslab >= 8 && Nb <= 64)
+  if (g_tune.conv_ksplit && tiles64 <= ks_max && nslab >= 8 && Nb <= 64)
     return dtype == DRN_BF16 ? launch_conv_ks<DRN_BF16>(p, st)
            : dtype == DRN_FP8 ? (p.fp8_k64 ? launch_conv_ks<DRN_FP8>(p, st) : launch_conv_ks<DRN_FP8, false>(p, st))
                               : launch_conv_ks<DRN_F32>(p, st);

@@ -12,6 +12,7 @@
 //   apply_deltas       Box2BoxTransform.apply_deltas box_regression.py:73-110
 //   sgd_step           torch.optim.SGD as built by detectron2/solver/build.py:93-137
 #include "drn_common.h"
+#include "tune.h"
 #include <stdlib.h>
 #include <float.h>
 
@@ -1057,13 +1058,6 @@ __global__ __launch_bounds__(256) void mean_softmax_wave_kernel(const float* log
   }
 }
 
-static int g_msm_wave = 1;  // drn_tune(DRN_TUNE_MSM_WAVE = 32): 0 = the thread-per-row kernel also for C <= 64 (tests, A/B)
-extern "C" __attribute__((visibility("hidden"))) int drn_msm_set_wave(int on) {
-  const int old = g_msm_wave;
-  g_msm_wave = on != 0;
-  return old;
-}
-
 // Box2BoxTransform.apply_deltas; deltas == null means all-zero deltas (non-regressing heads)
 __global__ void apply_deltas_kernel(const float* deltas, long ld_d, const float* boxes, float* out, int M, int K,
                                     float wx, float wy, float ww, float wh, float clampv) {
@@ -1522,7 +1516,7 @@ int drn_mean_softmax(const float* logits, long ld, const int* col0s_dev, int n_h
   if (M == 0) return DRN_OK;
   if (C < 1) return DRN_ERR_ARG;
   const dim3 grid((M + MSM_THREADS - 1) / MSM_THREADS), block(MSM_THREADS);
-  if (C <= 64 && g_msm_wave)
+  if (C <= 64 && g_tune.msm_wave)
     hipLaunchKernelGGL(mean_softmax_wave_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, ld, col0s_dev, n_heads, C,
                        probs, M, bg_first);
   else if ((size_t)C * MSM_THREADS * sizeof(float) <= 64 * 1024)
@@ -1546,15 +1540,8 @@ int drn_apply_deltas(const float* deltas, long ld_d, const float* boxes, float* 
   return DRN_OK;
 }
 
-// workgroups (x) of the optimizer kernel; each runs a grid-stride loop, i.e. lives for the whole launch.  At most two
-// 256-thread workgroups (34 VGPRs) fit on a CU beside a resident 256x256 GEMM workgroup - see drn_tune in gemm_conv.hip
-static int g_sgd_grid_x = 512;  // measured (tools/overlap_bench.py): 512 -> 6.5 TB/s, 1024 -> 5.8, 256 -> 5.3 on the fc6 slabs
-__attribute__((visibility("hidden"))) int drn_sgd_set_grid(int blocks_x) {
-  const int old = g_sgd_grid_x;
-  if (blocks_x >= 8 && blocks_x <= 65535) g_sgd_grid_x = blocks_x;
-  return old;
-}
-
+// g_tune.sgd_grid workgroups (x) of the optimizer kernel; each runs a grid-stride loop, i.e. lives for the whole launch.  At most two
+// 256-thread workgroups (34 VGPRs) fit on a CU beside a resident 256x256 GEMM workgroup.
 // segs_dev: device array of {int64 off, int64 cnt, float lr, float wd} (24 bytes each).  shadow (optional):
 // bf16 array with the arena's flat layout, refreshed in the same pass.
 int drn_sgd_step(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
@@ -1563,7 +1550,7 @@ int drn_sgd_step(float* weights, float* momentum_buf, const void* grads, int gra
   if (!weights || !momentum_buf || !grads || !segs_dev || nseg < 1) return DRN_ERR_ARG;
   if (shadow && shadow_dtype != DRN_BF16) return DRN_ERR_ARG;
   if (grad_dtype != DRN_F32 && grad_dtype != DRN_BF16) return DRN_ERR_ARG;
-  dim3 grid(g_sgd_grid_x, nseg < 32 ? nseg : 32), block(256);
+  dim3 grid(g_tune.sgd_grid, nseg < 32 ? nseg : 32), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define SGD_LAUNCH(SH, GD)                                                                                       \
   hipLaunchKernelGGL((sgd_kernel<SH, GD>), grid, block, 0, st, weights, momentum_buf, grads, grad_off,           \
@@ -1588,7 +1575,7 @@ int drn_sgd_step_block(float* weights, float* momentum_buf, const void* grads, i
   if ((c0 & 3) || (cols & 3) || (ld & 3) || (grad_off & 3)) return DRN_ERR_UNSUPPORTED;  // (the tensor's offset: checked by the caller's table)
   if ((long)rows * (cols >> 2) >= (1L << 32)) return DRN_ERR_UNSUPPORTED;
   if (rows == 0 || cols == 0) return DRN_OK;
-  dim3 grid(g_sgd_grid_x), block(256);
+  dim3 grid(g_tune.sgd_grid), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define SGD_LAUNCH(SH, GD)                                                                                          \
   hipLaunchKernelGGL((sgd_block_kernel<SH, GD>), grid, block, 0, st, weights, momentum_buf, grads, grad_off,        \

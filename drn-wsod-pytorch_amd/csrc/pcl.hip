@@ -707,13 +707,7 @@ int drn_pcl_refine(const float* logits, int ld, const int* cols, int n_branch, i
   pcl_softmax_kernel<<<dim3((R + 255) / 256, n_branch), 256, 0, stream>>>(sp);
   DRN_CHECK_LAUNCH();
   const size_t lds = ((sizeof(PclShared) + 15) & ~size_t(15)) + 16384 + 32776 + 32768 + 32768 + 8192 + 8192 + PCL_NINV * 8;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(pcl_refine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return DRN_ERR_LAUNCH;
-    attr_set = true;
-  }
+  if (!drn_launch::allow_lds(reinterpret_cast<const void*>(pcl_refine_kernel), (int)lds)) return DRN_ERR_LAUNCH;
   pcl_refine_kernel<<<n_branch, PCL_T, lds, stream>>>(rp);
   DRN_CHECK_LAUNCH();
   return DRN_OK;

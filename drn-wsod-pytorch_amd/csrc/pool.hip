@@ -10,6 +10,7 @@
 // (detectron2/modeling/poolers.py:162-165), ROIAlign (detectron2/layers/csrc/ROIAlign/ROIAlign_cuda.cu:65-139)
 // and the objectness scaling of roi_heads_oicr.py:342-343.
 #include "drn_common.h"
+#include "tune.h"
 #include <float.h>
 
 namespace {
@@ -1755,20 +1756,18 @@ __global__ __launch_bounds__(1024) void roi_pool7_st_kernel(RoiParams p, const u
 #undef ST_CLK
 }
 
-static int g_roi_st_prof = 0;  // drn_tune(31, 10 / 11): profile builds on / off; (31, 12): print and clear the counters
-static int g_roi_st = 1;  // drn_tune(DRN_TUNE_ROI_ST = 31): 0 = off, 1 = where it is faster (default: large maps with enough ROIs), 2 = every map whose slice fits
 static size_t roi_st_align(size_t x) { return (x + 255) & ~(size_t)255; }
 // cells of VD dwords for this map under the sparse-table kernel (0: not its shape)
 static int roi_st_vd(int N, int H, int W, int C, int M) {
-  if (!g_roi_st || H < 2 || H > 255 || W < 2 || W > 255 || N < 1 || N > 10 || M < 64 || M > 16384) return 0;
+  if (!g_tune.roi_st || H < 2 || H > 255 || W < 2 || W > 255 || N < 1 || N > 10 || M < 64 || M > 16384) return 0;
   const size_t hw = (size_t)H * W;
   if (hw > 30 * 1024) return 0;
   const size_t list = (size_t)((M + 7) & ~7) * 2 + 64;  // ROI list + counters; then a 208- / 400- / 784-byte scratch per wave
   const bool fits8 = C % 8 == 0 && hw * 16 + list + 16 * 784 <= 160 * 1024, fits4 = C % 4 == 0 && hw * 8 + list + 16 * 400 <= 160 * 1024;
   // 2 channels per cell: the stride-8 maps of the largest test-time scales (1200 x 1600: 150 x 200 cells), twice the blocks
   const bool fits2 = C % 2 == 0 && hw * 4 + list + 16 * 208 <= 160 * 1024;
-  if (!fits8 && !fits4) return fits2 && (g_roi_st == 2 || M >= 400) ? 1 : 0;
-  if (g_roi_st == 2) return fits8 ? 4 : fits4 ? 2 : 0;
+  if (!fits8 && !fits4) return fits2 && (g_tune.roi_st == 2 || M >= 400) ? 1 : 0;
+  if (g_tune.roi_st == 2) return fits8 ? 4 : fits4 ? 2 : 0;
   // default: where the table's fixed cost (staging + <= 8 doubling steps per block, ~HW) is below what the window kernels spend
   // reading every ROI's cells (~M x ROI area): profiles/r6_17_roi_st.txt, r6_18 (R = 250 / 1000 / 4000)
   if (fits8) return (M >= 600 && hw >= 3000) || (M >= 1500 && hw >= 1800) ? 4 : 0;
@@ -1792,9 +1791,9 @@ static bool launch_roi_st(const RoiParams& p0, hipStream_t st, void* ws, size_t 
   else if (vd == 2) { if (sb <= 10) ST_PICK(2, 10); else if (sb <= 15) ST_PICK(2, 15); else ST_PICK(2, 20); }
   else { if (sb <= 5) ST_PICK(4, 5); else ST_PICK(4, 10); }
 #undef ST_PICK
-  if (g_roi_st_prof && vd == 2 && sb > 10 && sb <= 15) fn = (const void*)roi_pool7_st_kernel<2, 15, true>;
-  if (g_roi_st_prof && vd == 4 && sb > 5) fn = (const void*)roi_pool7_st_kernel<4, 10, true>;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+  if (g_tune.roi_st_prof && vd == 2 && sb > 10 && sb <= 15) fn = (const void*)roi_pool7_st_kernel<2, 15, true>;
+  if (g_tune.roi_st_prof && vd == 4 && sb > 5) fn = (const void*)roi_pool7_st_kernel<4, 10, true>;
+  if (!drn_launch::allow_lds(fn, 160 * 1024)) return false;
   hipLaunchKernelGGL(roi_st_prep_kernel, dim3((p.M + 3) / 4), dim3(256), 0, st, p, rec, cls);
   const dim3 cgrid((HW + 31) / 32, (nchunks + 31) / 32, p.N);
   if (vd == 1) hipLaunchKernelGGL(roi_chunk_major_vd_kernel<1>, cgrid, dim3(256), 0, st, p.feat, cm, HW, p.C);
@@ -1811,7 +1810,6 @@ static bool launch_roi_st(const RoiParams& p0, hipStream_t st, void* ws, size_t 
   return hipLaunchKernel(fn, grid, block, args, smem, st) == hipSuccess;
 }
 
-static int g_roi_lane = 1;  // drn_tune(DRN_TUNE_ROI_LANE = 19): 0 = the 64-ROI kernel writes A as before
 // A (all channels) through the lane-per-bin kernel; false when the map slice of even ONE chunk does not fit
 // chunks per block: as many as fit 38 KB (four 8-wave blocks per CU), else 76 KB (two), else one chunk in <= 154 KB; 0: none fits
 static int roi_lane_chunks(int H, int W, int C) {
@@ -1824,13 +1822,11 @@ static int roi_lane_chunks(int H, int W, int C) {
   return 0;
 }
 
-static int g_roi_walk_nsg = 2;  // sub-groups of 64 ROIs per block of the walking kernel on one-block-per-CU maps (tests: DRN_TUNE_ROI_LANE = 3 -> 1)
-static int g_roi_lane_reps = 0;  // drn_tune(DRN_TUNE_ROI_LANE_REPS = 22): groups per block on one-block-per-CU maps (0 = default: 4, fewer while < 2 rounds of blocks)
 static int cu_count_pool_fwd();
 static bool roi_walk_applies(int H, int W, int C);
 static bool launch_roi_lane(const RoiParams& p0, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
   RoiParams p = p0;
-  if (!g_roi_lane || p.C % 8) return false;
+  if (!g_tune.roi_lane || p.C % 8) return false;
   size_t per_chunk = (size_t)p.H * p.W * 16;
   int nck = roi_lane_chunks(p.H, p.W, p.C);
   int vd = 4;
@@ -1842,19 +1838,15 @@ static bool launch_roi_lane(const RoiParams& p0, hipStream_t st, void* ws = null
   if (launch_roi_st(p, st, ws, ws_bytes)) return true;  // large maps: four table cells per bin instead of the window's ~77
   if (!nck) return false;
   const size_t smem = per_chunk * nck;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<1, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_lane_kernel<1, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess)
-      return false;
-    attr = true;
-  }
-  if (nck == 1 && vd == 4 && g_roi_lane != 2 && roi_walk_applies(p.H, p.W, p.C)) {
+  const bool big = smem > 76 * 1024;  // one block per CU: 16 waves
+  const void* lane_fn = vd == 4 ? (nck == 8   ? (const void*)roi_pool7_lane_kernel<8>
+                                   : nck == 4 ? (const void*)roi_pool7_lane_kernel<4>
+                                   : nck == 2 ? (const void*)roi_pool7_lane_kernel<2>
+                                   : !big     ? (const void*)roi_pool7_lane_kernel<1>
+                                              : (const void*)roi_pool7_lane_kernel<1, 16>)
+                        : big   ? (const void*)roi_pool7_lane_kernel<1, 16, 2>
+                                : (const void*)roi_pool7_lane_kernel<1, 8, 2>;
+  if (nck == 1 && vd == 4 && g_tune.roi_lane != 2 && roi_walk_applies(p.H, p.W, p.C)) {
     // one chunk per block: the walking kernel
     const size_t lds_max = 160 * 1024;
     // slice + window table + counter
@@ -1862,7 +1854,7 @@ static bool launch_roi_lane(const RoiParams& p0, hipStream_t st, void* ws = null
     const bool big1 = need(1, p.W | 1) > 80 * 1024;  // one block per CU: 16 waves
     // the largest maps: first the odd pitch goes, then the second sub-group of ROIs
     // 128 ROIs per block (64 with DRN_TUNE_ROI_LANE = 3, for tests) where the table fits: half the stagings and barriers per item
-    int wp = p.W | 1, nsg = g_roi_walk_nsg == 2 && (big1 || need(2, wp) <= 80 * 1024) ? 2 : 1;
+    int wp = p.W | 1, nsg = g_tune.roi_walk_nsg == 2 && (big1 || need(2, wp) <= 80 * 1024) ? 2 : 1;
     if (need(nsg, wp) > lds_max) wp = p.W;
     if (need(nsg, wp) > lds_max) nsg = 1;
     const size_t wsmem = need(nsg, wp);
@@ -1876,10 +1868,10 @@ static bool launch_roi_lane(const RoiParams& p0, hipStream_t st, void* ws = null
     double best = -1.0;
     for (int w = 8, lg = 0; w >= 1; w >>= 1, ++lg) {
       if (nchunks % w != 0) continue;
-      if (g_roi_lane_reps > 0 && w > g_roi_lane_reps) continue;
+      if (g_tune.roi_lane_reps > 0 && w > g_tune.roi_lane_reps) continue;
       const long grid = (long)ngr * (nchunks / w);
       const double score = (double)grid / (double)((grid + slots - 1) / slots * slots) * (1.0 - 0.015 * lg);
-      if (g_roi_lane_reps > 0) { walk = w; break; }  // (knob: the largest admissible walk <= its value)
+      if (g_tune.roi_lane_reps > 0) { walk = w; break; }  // (knob: the largest admissible walk <= its value)
       if (score > best) best = score, walk = w;
     }
     p.walk = walk;
@@ -1909,7 +1901,7 @@ static bool launch_roi_lane(const RoiParams& p0, hipStream_t st, void* ws = null
       else { if (sb <= 6) WALK_PICK(16, 1, 6, 1); else WALK_PICK(16, 1, 10, 1); }
     }
 #undef WALK_PICK
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+    if (!drn_launch::allow_lds(fn, 160 * 1024)) return false;
     void* args[] = {(void*)&p};
     if (hipLaunchKernel(fn, wgrid, wblock, args, wsmem, st) != hipSuccess) return false;
     return true;
@@ -1926,25 +1918,19 @@ static bool launch_roi_lane(const RoiParams& p0, hipStream_t st, void* ws = null
     // (4-channel cells - the DC5 stride-8 map: a slice is staged 8 bytes per 4-KB pixel, i.e. a whole 128-byte line per cell from
     // the Infinity Cache: 7.9 GB per launch with 4 groups per staged slice; with all of a slice's groups on one block - still
     // two rounds of blocks - the launch went from 1242 to 948 us, profiles/r5_28_*)
-    int reps = g_roi_lane_reps > 0 ? g_roi_lane_reps : (vd == 2 ? 32 : 4);
+    int reps = g_tune.roi_lane_reps > 0 ? g_tune.roi_lane_reps : (vd == 2 ? 32 : 4);
     while (reps > 1 && blocks1 / reps < 2L * cu_count_pool_fwd()) reps >>= 1;
     p.lane_reps = reps;
     ngroups = (ngroups + reps - 1) / reps;
   }
-  const bool big = smem > 76 * 1024;  // one block per CU: 16 waves
   // (one block per CU - maps beyond ~4700 pixels: with a block per group of 64 ROIs this kernel measured 372 vs 325 us for the
   // 64-ROI kernel at 63x92 and went there only for maps that kernel stages in two row bands; with four groups per staged
   // slice it is 293 vs 330 us at 63x92 and 260 vs 368 us at 75x122 and takes every map whose chunk fits)
   const dim3 grid((unsigned)ngroups * (p.C / (2 * vd * nck))), block(big ? 1024 : 512);
   p.out_t = nullptr;  // (A only; the caller launches the 64-ROI kernel for the A^T tail chunks)
-  if (vd == 2) {
-    if (big) hipLaunchKernelGGL((roi_pool7_lane_kernel<1, 16, 2>), grid, block, smem, st, p);
-    else hipLaunchKernelGGL((roi_pool7_lane_kernel<1, 8, 2>), grid, block, smem, st, p);
-  } else if (nck == 8) hipLaunchKernelGGL(roi_pool7_lane_kernel<8>, grid, block, smem, st, p);
-  else if (nck == 4) hipLaunchKernelGGL(roi_pool7_lane_kernel<4>, grid, block, smem, st, p);
-  else if (nck == 2) hipLaunchKernelGGL(roi_pool7_lane_kernel<2>, grid, block, smem, st, p);
-  else if (big) hipLaunchKernelGGL((roi_pool7_lane_kernel<1, 16>), grid, block, smem, st, p);
-  else hipLaunchKernelGGL(roi_pool7_lane_kernel<1>, grid, block, smem, st, p);
+  if (!drn_launch::allow_lds(lane_fn, 156 * 1024)) return false;
+  void* args[] = {(void*)&p};
+  (void)hipLaunchKernel(lane_fn, grid, block, args, smem, st);
   return true;
 }
 
@@ -1957,21 +1943,15 @@ static bool launch_roi_align_lane(const RoiParams& p0, hipStream_t st) {
   // (64 fp32 accumulators per lane at 8 chunks: 4 chunks per block keep the wave under 128 registers - two blocks per CU)
   if (nck > 4) nck = 4;
   const size_t smem = (size_t)p.H * p.W * 16 * nck;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)roi_align7_lane_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_align7_lane_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_align7_lane_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess)
-      return false;
-    attr = true;
-  }
   p.lane_g = smem > 38 * 1024 ? 64 : 32;
   const int ngroups = (p.M + p.lane_g - 1) / p.lane_g;
   const dim3 grid((unsigned)ngroups * (p.C / (8 * nck))), block(512);
   p.out_t = nullptr;
-  if (nck == 4) hipLaunchKernelGGL(roi_align7_lane_kernel<4>, grid, block, smem, st, p);
-  else if (nck == 2) hipLaunchKernelGGL(roi_align7_lane_kernel<2>, grid, block, smem, st, p);
-  else hipLaunchKernelGGL(roi_align7_lane_kernel<1>, grid, block, smem, st, p);
+  auto k = roi_align7_lane_kernel<4>;
+  if (nck == 2) k = roi_align7_lane_kernel<2>;
+  if (nck == 1) k = roi_align7_lane_kernel<1>;
+  if (!drn_launch::allow_lds((const void*)k, 156 * 1024)) return false;
+  hipLaunchKernelGGL(k, grid, block, smem, st, p);
   return true;
 }
 
@@ -1994,22 +1974,17 @@ static int cu_count_pool() {
   return n;
 }
 
-// Chunks per block: stand-alone the launch gets faster with 4-8 (141 -> 117-125 us at 14x14 / R = 2000: bin bounds and item
+// Chunks per block (g_tune.roi_cpb): stand-alone the launch gets faster with 4-8 (141 -> 117-125 us at 14x14 / R = 2000: bin bounds and item
 // table once per block, next slice prefetched), but INSIDE the training step it runs beside the optimizer pass and the
 // trunk's conv chain, and 512 long-lived blocks - a static partition of the work - lose to 4096 short ones that the
 // dispatcher balances over whichever CUs are free: same-box A/B of the whole step 646 img/s (1), 643 (2), 634 (8) against
 // 646 with the previous kernel (profiles/r2_26_roi_ab.txt).  Default 1; the knob stays for stand-alone pooling (inference).
-static int g_roi_cpb = 1;  // drn_tune(DRN_TUNE_ROI_CPB): most 8-channel chunks per block of the 64-ROI kernel (power of two)
-static int g_roi_pf = 1;   // drn_tune(DRN_TUNE_ROI_PREFETCH): 0/1 - second map buffer, next chunk's slice fetched under the scan
-static int g_roi_map64 = 512;  // drn_tune(DRN_TUNE_ROI_MAP64): 0 = off, else threads per block (256 / 512 / 1024)
-
-static int g_roi_lds_kb = 154;  // drn_tune(DRN_TUNE_ROI_LDS_KB = 15)
 static bool launch_roi_map64(const RoiParams& p0, hipStream_t st) {
   RoiParams p = p0;
-  if (!g_roi_map64 || p.C % G64_CH || p.H > 255 || p.W > 255) return false;
+  if (!g_tune.roi_map64 || p.C % G64_CH || p.H > 255 || p.W > 255) return false;
   // LDS a block may take for its map slice + result tile (+ ~1.5 KB static): 154 KB = one block per CU with the whole
   // slice of maps up to ~80x80; DRN_TUNE_ROI_LDS_KB = 76 stages larger maps in bands so that TWO blocks share a CU
-  const size_t tile_b = (size_t)ROI_G64 * G64_PITCH, budget = (size_t)g_roi_lds_kb * 1024 - tile_b;
+  const size_t tile_b = (size_t)ROI_G64 * G64_PITCH, budget = (size_t)g_tune.roi_lds_kb * 1024 - tile_b;
   size_t map_b = ((size_t)p.H * p.W * 16 + 15) & ~(size_t)15;
   p.lds_px = p.H * p.W;
   if (map_b > budget) {  // bands of whole rows
@@ -2021,9 +1996,9 @@ static bool launch_roi_map64(const RoiParams& p0, hipStream_t st) {
   size_t smem = map_b + tile_b;
   {
     // prefetch mode: whole map in one band, two buffers within the same blocks-per-CU class, <= 2 pixels per thread
-    const int e = g_roi_pf;
+    const int e = g_tune.roi_prefetch;
     const size_t cls = smem <= 76 * 1024 ? 76 * 1024 : 156 * 1024;
-    const int thr = smem > 76 * 1024 && g_roi_map64 == 512 ? 1024 : g_roi_map64;
+    const int thr = smem > 76 * 1024 && g_tune.roi_map64 == 512 ? 1024 : g_tune.roi_map64;
     p.pf = e && p.lds_px == p.H * p.W && smem + map_b <= cls && p.H * p.W <= 2 * thr;
     if (p.pf) smem += map_b;
   }
@@ -2032,29 +2007,23 @@ static bool launch_roi_map64(const RoiParams& p0, hipStream_t st) {
   // these maps used to fall to re-stages it per 8 ROIs (2.9 GB through L2 per call at 63x92: 1.5 ms, half of the eager
   // step at 1000x1464, `profiles/r2_15_*`)
   if (smem > 156 * 1024) return false;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)roi_pool7_map64_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_map64_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)roi_pool7_map64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess)
-      return false;
-    attr = true;
-  }
   const int ngroups = (p.M + ROI_G64 - 1) / ROI_G64;
   // one block per CU (maps beyond ~38x38): 1024 threads - the window scans are latency-bound and eight waves per CU hide
   // little of it (63x92 map, 2000 proposals: 467 -> 394 us); two blocks per CU: the tuned 512
-  const int threads = smem > 76 * 1024 && g_roi_map64 == 512 ? 1024 : g_roi_map64;
+  const int threads = smem > 76 * 1024 && g_tune.roi_map64 == 512 ? 1024 : g_tune.roi_map64;
   // channel chunks per block (tune knob, default 1): the bin bounds of a 64-ROI group and the per-thread item table are
   // paid once per `cpb` chunks instead of once per chunk; largest power of two <= the knob that still leaves two blocks
   // for every CU
-  int cpb = g_roi_cpb;
+  int cpb = g_tune.roi_cpb;
   const int nchunks = (p.C - p.c_begin) / G64_CH;
   while (cpb > 1 && (nchunks % cpb || (long)(nchunks / cpb) * ngroups < 2L * cu_count_pool())) cpb >>= 1;
   p.cpb = cpb;
   const dim3 grid((nchunks / cpb) * ngroups), block(threads);
-  if (threads >= 1024) hipLaunchKernelGGL(roi_pool7_map64_kernel<4>, grid, block, smem, st, p);
-  else if (threads >= 512) hipLaunchKernelGGL(roi_pool7_map64_kernel<7>, grid, block, smem, st, p);
-  else hipLaunchKernelGGL(roi_pool7_map64_kernel<13>, grid, block, smem, st, p);
+  auto k = roi_pool7_map64_kernel<13>;
+  if (threads >= 512) k = roi_pool7_map64_kernel<7>;
+  if (threads >= 1024) k = roi_pool7_map64_kernel<4>;
+  if (!drn_launch::allow_lds((const void*)k, 156 * 1024)) return false;
+  hipLaunchKernelGGL(k, grid, block, smem, st, p);
   return true;
 }
 
@@ -2146,75 +2115,24 @@ static bool launch_roi_map(const RoiParams& p, hipStream_t st, size_t lds_budget
   if (q.gpw < 1) q.gpw = 1;
   const int nblk = (ngroups + q.gpw - 1) / q.gpw;
   auto k = roi_pool7_map_kernel<DT, CH>;
-  static bool attr = false;
-  if (!attr && smem > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return false;
-    attr = true;
-  }
+  if (smem > 48 * 1024 && !drn_launch::allow_lds((const void*)k, 156 * 1024)) return false;
   hipLaunchKernelGGL(k, dim3((p.C / CH) * nblk), dim3(256), smem, st, q);
   return true;
 }
 
+// DRN_TUNE_ROI_ST with value 12: print and clear the shader-clock sums the profile builds of roi_pool7_st_kernel accumulated
+__attribute__((visibility("hidden"))) int drn_tune_roi_st_profile_dump() {
+  unsigned long long h[8];
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_st_prof), sizeof(h)) != hipSuccess) return -1;
+  const double n = h[5] ? (double)h[5] : 1.0;
+  fprintf(stderr, "roi_st profile: %llu blocks, %.1f ROIs each | shader-clock cycles per block: scan %.0f  slice %.0f  row steps %.0f  column steps %.0f  pooling %.0f\n",
+          h[5], (double)h[6] / n, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n);
+  for (auto& x : h) x = 0;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_st_prof), h, sizeof(h)) != hipSuccess) return -1;
+  return 0;
+}
+
 extern "C" {
-
-__attribute__((visibility("hidden"))) int drn_roi_set_chunks(int cpb) {
-  const int old = g_roi_cpb;
-  if (cpb >= 1 && cpb <= 64 && (cpb & (cpb - 1)) == 0) g_roi_cpb = cpb;
-  return old;
-}
-
-static int g_roi_map64_a = 0;  // drn_tune(DRN_TUNE_ROI_MAP64_A = 14): 1 = the 64-ROI kernel also for A alone (no A^T)
-__attribute__((visibility("hidden"))) int drn_roi_set_map64_a(int on) {
-  const int old = g_roi_map64_a;
-  g_roi_map64_a = on != 0;
-  return old;
-}
-
-__attribute__((visibility("hidden"))) int drn_roi_set_lds_kb(int kb) {
-  const int old = g_roi_lds_kb;
-  if (kb >= 60 && kb <= 154) g_roi_lds_kb = kb;
-  return old;
-}
-
-__attribute__((visibility("hidden"))) int drn_roi_set_lane_reps(int reps) {
-  const int old = g_roi_lane_reps;
-  if (reps >= 0 && reps <= 64) g_roi_lane_reps = reps;
-  return old;
-}
-__attribute__((visibility("hidden"))) int drn_roi_set_lane(int on) {
-  const int old = g_roi_lane;
-  g_roi_walk_nsg = on == 3 ? 1 : 2;
-  g_roi_lane = on < 0 ? 0 : on == 3 ? 1 : on > 2 ? 2 : on;
-  return old;
-}
-
-__attribute__((visibility("hidden"))) int drn_roi_set_st(int on) {
-  const int old = g_roi_st;
-  if (on >= 0 && on <= 2) g_roi_st = on;
-  if (on == 10 || on == 11) g_roi_st_prof = on == 10;
-  if (on == 12) {
-    unsigned long long h[8];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_st_prof), sizeof(h)) != hipSuccess) return -1;
-    const double n = h[5] ? (double)h[5] : 1.0;
-    fprintf(stderr, "roi_st profile: %llu blocks, %.1f ROIs each | shader-clock cycles per block: scan %.0f  slice %.0f  row steps %.0f  column steps %.0f  pooling %.0f\n",
-            h[5], (double)h[6] / n, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n);
-    for (auto& x : h) x = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_st_prof), h, sizeof(h)) != hipSuccess) return -1;
-  }
-  return old;
-}
-
-__attribute__((visibility("hidden"))) int drn_roi_set_prefetch(int on) {
-  const int old = g_roi_pf;
-  g_roi_pf = on != 0;
-  return old;
-}
-
-__attribute__((visibility("hidden"))) int drn_roi_set_map64(int on) {
-  const int old = g_roi_map64;
-  g_roi_map64 = on == 1 ? 512 : (on == 0 || on == 256 || on == 512 || on == 1024) ? on : old;
-  return old;
-}
 
 int drn_resize_bilinear_u8(const void* src_hwc, int H, int W, int C, float* dst_chw, int Ho, int Wo, const int* xbounds,
                            const int* xcoef, int ksx, const int* ybounds, const int* ycoef, int ksy, int flip, void* stream) {
@@ -2396,8 +2314,8 @@ int drn_roi_pool_nhwc_t(const void* feat, const float* rois, const float* object
 long drn_roi_pool_workspace_bytes(int N, int H, int W, int C, int P, int M, int mode, int has_argmax, int in_dtype, int out_dtype) {
   if (N < 1 || H < 1 || W < 1 || C < 1) return 0;
   if (mode != 0 || P != 7 || has_argmax || in_dtype != DRN_BF16 || out_dtype != DRN_BF16 || M < ROI_G64 || C % G64_CH != 0) return 0;
-  if (g_roi_lane != 0 && roi_st_vd(N, H, W, C, M)) return (long)roi_st_ws_bytes(N, H, W, C, M);
-  return g_roi_lane != 0 && g_roi_lane != 2 && roi_walk_applies(H, W, C) ? (long)N * H * W * C * 2 : 0;
+  if (g_tune.roi_lane != 0 && roi_st_vd(N, H, W, C, M)) return (long)roi_st_ws_bytes(N, H, W, C, M);
+  return g_tune.roi_lane != 0 && g_tune.roi_lane != 2 && roi_walk_applies(H, W, C) ? (long)N * H * W * C * 2 : 0;
 }
 
 // The same with a caller-owned workspace (drn_roi_pool_workspace_bytes; null / too small: as without): maps whose 8-channel slice
@@ -2443,7 +2361,7 @@ int drn_roi_pool_nhwc_ws(const void* feat, const float* rois, const float* objec
             done = launch_roi_map64(q, st);
             if (!done) done = launch_roi_map64(p, st);  // (cannot happen for shapes the lane kernel took)
           }
-        } else if (out_t || g_roi_map64_a) {
+        } else if (out_t || g_tune.roi_map64_a) {
           done = launch_roi_map64(p, st);
         }
       }
@@ -2468,7 +2386,7 @@ int drn_roi_pool_nhwc_ws(const void* feat, const float* rois, const float* objec
     }
   }
   // ROIAlign, bf16 -> bf16, P = 7, channels in chunks of 8, a slice of the map in LDS: the lane-per-bin form
-  if (mode == 1 && P == 7 && !out_t && in_dtype == DRN_BF16 && out_dtype == DRN_BF16 && g_roi_lane && (((uintptr_t)feat) & 15) == 0 &&
+  if (mode == 1 && P == 7 && !out_t && in_dtype == DRN_BF16 && out_dtype == DRN_BF16 && g_tune.roi_lane && (((uintptr_t)feat) & 15) == 0 &&
       M >= 32 && launch_roi_align_lane(p, st)) {
     DRN_CHECK_LAUNCH();
     return DRN_OK;

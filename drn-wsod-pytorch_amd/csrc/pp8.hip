@@ -29,6 +29,7 @@
 // Same LDS image, slab order, k-steps and MFMA per output element as conv_nhwc_kernel / conv_ring_kernel / gemm_nt256 (the
 // operands are swapped in the MFMA - D^T - exactly as conv1x1_pp_kernel does): bit-identical to them.
 #include "drn_common.h"
+#include "tune.h"
 #include "conv_params.h"
 
 #include <stdio.h>
@@ -60,15 +61,6 @@ struct Pp8Params {
   const float* mask;      // fc: explicit dropout multipliers [Mtot][N] or null
   unsigned long long seed; const unsigned long long* seed_dev; float drop_p;  // fc: counter-based dropout (drn_common.h)
 };
-
-__device__ __forceinline__ void tile_coords(int id, int tiles_m, int tiles_n, int& tm, int& tn, int GM) {
-  const int group_sz = GM * tiles_n;
-  const int g = id / group_sz, in_g = id - g * group_sz;
-  const int first_m = g * GM;
-  const int gm = tiles_m - first_m < GM ? tiles_m - first_m : GM;
-  tm = first_m + in_g % gm;
-  tn = in_g / gm;
-}
 
 #define PP8_BARRIER()                    \
   do {                                   \
@@ -522,26 +514,16 @@ int launch_pp8(const Pp8Params& p, hipStream_t st) {
   const int tiles = ((p.Mtot + BM - 1) / BM) * ((p.N + 127) / 128);
   constexpr int smem = NSTG * (BM + 128) * 128;
   auto k = pp8_kernel<BM, NSTG, EPI, VAR>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return DRN_ERR_LAUNCH;
-    attr = true;
-  }
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(tiles), dim3(512), smem, st, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
 
-int g_pp8 = 1;         // drn_tune(DRN_TUNE_PP8 = 25): 0 = off, 1 = default class, 2 = every layer in the kernel's class
-int g_pp8_stages = 5;  // drn_tune(DRN_TUNE_PP8_STAGES = 26): LDS ring stages of the 128x128 form (3 / 4 / 5 = 1 / 2 / 3 slabs in flight)
-int g_pp8_var = 1;     // drn_tune(DRN_TUNE_PP8_VARIANT = 27): schedule variant (pp8_kernel VAR), A/B knob
-int g_pp8_wvar = 4;    // drn_tune(DRN_TUNE_PP8_WIDE_VARIANT = 30): VAR of the 256x128 form (1 = all DMA pieces in phase L1, 4 = no s_setprio, 8 = profile)
-int g_pp8_wide = 1;    // drn_tune(DRN_TUNE_PP8_WIDE = 29): the 256x128 form: 0 = never, 1 = where it fills the chip, 2 = always
-
 template <int EPI>
 int launch_pp8_any(const Pp8Params& p, bool wide, hipStream_t st) {
   if (wide) {  // (variants of the 256x128 form: DRN_TUNE_PP8_WIDE_VARIANT)
-    switch (g_pp8_wvar) {
+    switch (g_tune.pp8_wvar) {
       case 0: return launch_pp8<256, 3, EPI, 0>(p, st);
       case 1: return launch_pp8<256, 3, EPI, 1>(p, st);
       case 4: return launch_pp8<256, 3, EPI, 4>(p, st);
@@ -552,7 +534,7 @@ int launch_pp8_any(const Pp8Params& p, bool wide, hipStream_t st) {
       default: return launch_pp8<256, 3, EPI, 4>(p, st);
     }
   }
-#define PP8_CASE(S_, V_) if (g_pp8_stages == S_ && g_pp8_var == V_) return launch_pp8<128, S_, EPI, V_>(p, st)
+#define PP8_CASE(S_, V_) if (g_tune.pp8_stages == S_ && g_tune.pp8_var == V_) return launch_pp8<128, S_, EPI, V_>(p, st)
   PP8_CASE(3, 0);
   PP8_CASE(4, 0); PP8_CASE(4, 1); PP8_CASE(4, 5);
   PP8_CASE(5, 0); PP8_CASE(5, 1); PP8_CASE(5, 2); PP8_CASE(5, 5);
@@ -563,59 +545,34 @@ int launch_pp8_any(const Pp8Params& p, bool wide, hipStream_t st) {
 
 // the 256x128 form where one image's layer gives it at least ~5/8 of the CUs' worth of tiles (its tiles are twice the work)
 static bool pp8_wide_ok(long rows_one, int N, int cus) {
-  if (g_pp8_wide == 0) return false;
-  if (g_pp8_wide == 2) return true;
+  if (g_tune.pp8_wide == 0) return false;
+  if (g_tune.pp8_wide == 2) return true;
   const long t256 = ((rows_one + 255) / 256) * ((N + 127) / 128);
   return t256 * 8 >= 5L * cus;
 }
 
 }  // namespace
 
-// (hidden: drn_tune in gemm_conv.hip)
-__attribute__((visibility("hidden"))) int drn_pp8_set(int knob, int v) {
-  if (knob == 25) {
-    const int old = g_pp8;
-    if (v >= 0 && v <= 2) g_pp8 = v;
-    return old;
+// DRN_TUNE_PP8_PROFILE: print and clear the shader-clock split the profile variants (VAR & 8) accumulated
+__attribute__((visibility("hidden"))) int drn_tune_pp8_profile_dump() {
+  unsigned long long h[8][8];
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pp8_prof), sizeof(h)) != hipSuccess) return -1;
+  for (int w = 0; w < 8; ++w) {
+    const double nl = h[w][7] ? (double)h[w][7] : 1.0, ns = h[w][6] ? (double)h[w][6] : 1.0;
+    fprintf(stderr, "pp8 profile wave %d: %llu launches, %.1f slabs each | per slab: read+issue %.0f  mid-barrier %.0f  mfma %.0f  "
+                    "end-barrier %.0f cycles | per launch: prologue %.0f  epilogue %.0f\n",
+            w, h[w][7], ns / nl, h[w][0] / ns, h[w][1] / ns, h[w][2] / ns, h[w][3] / ns, h[w][4] / nl, h[w][5] / nl);
   }
-  if (knob == 27) {
-    const int old = g_pp8_var;
-    if (v >= 0 && v <= 10 && (v & 3) != 3) g_pp8_var = v;
-    return old;
-  }
-  if (knob == 28) {  // DRN_TUNE_PP8_PROFILE: print and clear the shader-clock split the profile variants (VAR & 8) accumulated
-    unsigned long long h[8][8];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pp8_prof), sizeof(h)) != hipSuccess) return -1;
-    for (int w = 0; w < 8; ++w) {
-      const double nl = h[w][7] ? (double)h[w][7] : 1.0, ns = h[w][6] ? (double)h[w][6] : 1.0;
-      fprintf(stderr, "pp8 profile wave %d: %llu launches, %.1f slabs each | per slab: read+issue %.0f  mid-barrier %.0f  mfma %.0f  "
-                      "end-barrier %.0f cycles | per launch: prologue %.0f  epilogue %.0f\n",
-              w, h[w][7], ns / nl, h[w][0] / ns, h[w][1] / ns, h[w][2] / ns, h[w][3] / ns, h[w][4] / nl, h[w][5] / nl);
-    }
-    memset(h, 0, sizeof(h));
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_pp8_prof), h, sizeof(h)) != hipSuccess) return -1;
-    return 0;
-  }
-  if (knob == 30) {
-    const int old = g_pp8_wvar;
-    if (v == 0 || v == 1 || v == 4 || v == 5 || v == 8 || v == 9 || v == 13) g_pp8_wvar = v;
-    return old;
-  }
-  if (knob == 29) {
-    const int old = g_pp8_wide;
-    if (v >= 0 && v <= 2) g_pp8_wide = v;
-    return old;
-  }
-  const int old = g_pp8_stages;
-  if (v == 3 || v == 4 || v == 5) g_pp8_stages = v;
-  return old;
+  memset(h, 0, sizeof(h));
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_pp8_prof), h, sizeof(h)) != hipSuccess) return -1;
+  return 0;
 }
 
 // Runs the convolution on the eight-wave kernel when it is in its class; DRN_ERR_UNSUPPORTED otherwise (drn_conv2d_nhwc_q then
 // goes on to the other kernel families).  The class is decided on ONE image's geometry (`HoWo`), so a layer takes the same
 // kernel whether its image runs alone or in a batch; every family gives the same bits anyway.
 __attribute__((visibility("hidden"))) int drn_pp8_conv_try(const ConvParams& c, int dtype, int cus, hipStream_t st) {
-  if (!g_pp8 || dtype != DRN_BF16 || c.out_dt != DRN_BF16 || (c.residual && c.res_dt != DRN_BF16)) return DRN_ERR_UNSUPPORTED;
+  if (!g_tune.pp8 || dtype != DRN_BF16 || c.out_dt != DRN_BF16 || (c.residual && c.res_dt != DRN_BF16)) return DRN_ERR_UNSUPPORTED;
   if ((c.Cin & 63) || (c.Cout & 7) || c.KH * c.KW > 32 || (c.ldy & 7) || (c.residual && (c.ldres & 7))) return DRN_ERR_UNSUPPORTED;
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   if (!al16(c.X) || !al16(c.Wt) || !al16(c.Y) || (c.residual && !al16(c.residual)) || (c.ldw * 2) % 16 != 0 ||
@@ -624,7 +581,7 @@ __attribute__((visibility("hidden"))) int drn_pp8_conv_try(const ConvParams& c, 
   if ((long)c.Cout * c.ldw * 2 >= 0xFFFFFFF0L || (long)c.Nb * c.H * c.W * c.Cin * 2 >= 0xFFFFFFF0L) return DRN_ERR_UNSUPPORTED;
   const int nslab = c.KH * c.KW * (c.Cin >> 6);
   const long t128 = (((long)c.Ho * c.Wo + 127) / 128) * ((c.Cout + 127) / 128);
-  if (g_pp8 == 1) {
+  if (g_tune.pp8 == 1) {
     // measured class (tools/conv_bench.py / tools/pp8_probe.py at 800x1216, profiles/r6_*): one image's layer offers at least
     // 5/8 of the CUs a 128x128 tile and the K loop is long enough to amortise the ring's prologue.  (1x1 layers with >= 192 tiles
     // of 256x256 never get here: drn_conv2d_nhwc_q sends them to conv1x1_pp_kernel first - its tile moves half the bytes per MFMA.)
@@ -651,7 +608,7 @@ int drn_linear_act_fwd(const void* A, const void* W, const float* bias, const fl
   if (!A || !W || !out || M < 0 || N < 0 || K <= 0 || lda < K || ldw < K || ld_out < N || (outT && ld_outT < M)) return DRN_ERR_ARG;
   if (M == 0 || N == 0) return DRN_OK;
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (!g_pp8 || (K & 63) || (N & 7) || (lda * 2) % 16 != 0 || (ldw * 2) % 16 != 0 || (ld_out & 7) || (outT && (ld_outT & 7)) ||
+  if (!g_tune.pp8 || (K & 63) || (N & 7) || (lda * 2) % 16 != 0 || (ldw * 2) % 16 != 0 || (ld_out & 7) || (outT && (ld_outT & 7)) ||
       !al16(A) || !al16(W) || !al16(out) || (outT && !al16(outT)) || (bias && !al16(bias)) || (mask && !al16(mask)) ||
       (long)M * lda * 2 >= 0xFFFFFFF0L || (long)N * ldw * 2 >= 0xFFFFFFF0L)
     return DRN_ERR_UNSUPPORTED;

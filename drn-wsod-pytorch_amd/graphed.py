@@ -6,7 +6,6 @@
   GraphedFullStep    trainable trunk: forward, losses, backward, optimizer as one graph (two with a gradient exchange between)
 
 Split out of engine.py in round 5; `engine` re-exports both names."""
-import os
 
 import torch
 import torch.distributed as dist
@@ -425,13 +424,6 @@ class GraphedTrainStep:
         P = self.RING_SLOTS if self._ring_on else 2
         losses = self._heads(eager)
         evp = None
-        probe = os.environ.get("DRN_PROBE_TAIL_FILL")  # experiment (tools/README: tail window of the fused dW launch)
-        if probe:
-            if not hasattr(self, "_probe_s"):
-                self._probe_s = torch.cuda.Stream()
-                self._probe_buf = torch.empty((int(probe) << 20,), dtype=torch.uint8, device=self.props.device)
-            pe = torch.cuda.Event()
-            pe.record(main)
         if self.split_tail:
             self.engine.run_fc1_tail()
         if ring:
@@ -440,11 +432,6 @@ class GraphedTrainStep:
                 raise DrnError("the ring schedule needs the pipelined optimizer's hook on the fc6 tail")
             self.opt.small_ready_event = None
             self._ring_evs.append(ev)
-        if probe:
-            with torch.cuda.stream(self._probe_s):
-                self._probe_s.wait_event(pe)
-                self._probe_buf.fill_(1)  # as many bytes as the pooling launch writes: does the dW launch's last round have room for them?
-            main.wait_stream(self._probe_s)
         with torch.cuda.stream(self._side):
             # proposals of batch t+1 on the side stream (behind the last reader of their staging set: the wait above, or under
             # the ring schedule the host's throttle; in front of the conv chain): three small launches that sat between the last dW slab and the

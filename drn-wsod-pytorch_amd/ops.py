@@ -1,7 +1,9 @@
 """Tensor-level wrappers over the C ABI (include/drn_wsod.h).  torch is used only to own device
 memory and streams; every computation below is a hand-written HIP kernel.  No CPU path exists:
 passing CPU tensors raises."""
+import contextlib
 import ctypes
+import functools
 import math
 
 import torch
@@ -37,19 +39,60 @@ def gemm_set_tile(tile):
     return C.lib().drn_gemm_set_tile(int(tile))
 
 
-TUNE_GEMM_PERSISTENT, TUNE_SGD_GRID, TUNE_GEMM_GROUP_ROWS, TUNE_ROI_MAP64, TUNE_CONV_KSPLIT, TUNE_GEMM_TAIL_SPLIT, TUNE_CONV_KS_TILES, TUNE_CONV_K2_TILES, TUNE_CONV_PATCH = 1, 2, 3, 4, 5, 6, 7, 8, 9
+# the knob ids of include/drn_wsod.h (#define DRN_TUNE_*), by id; tests/test_tune_cpu.py holds the two lists equal
+TUNE_GEMM_PERSISTENT = 1
+TUNE_SGD_GRID = 2
+TUNE_GEMM_GROUP_ROWS = 3
+TUNE_ROI_MAP64 = 4
+TUNE_CONV_KSPLIT = 5
+TUNE_GEMM_TAIL_SPLIT = 6
+TUNE_CONV_KS_TILES = 7
+TUNE_CONV_K2_TILES = 8
+TUNE_CONV_PATCH = 9
+TUNE_ROI_CPB = 10
+TUNE_ROI_PREFETCH = 11
+TUNE_GEMM_PINGPONG = 12
+TUNE_FP8_K64 = 13
+TUNE_ROI_MAP64_A = 14
+TUNE_ROI_LDS_KB = 15
+TUNE_GEMM_NWG = 18
+TUNE_ROI_LANE = 19
+TUNE_SGDP_EPILOGUE = 20
+TUNE_ROI_LANE_REPS = 22
 TUNE_CONV_RING = 23
+TUNE_CONV_PP = 24
+TUNE_PP8 = 25
+TUNE_PP8_STAGES = 26
+TUNE_PP8_VARIANT = 27
+TUNE_PP8_PROFILE = 28
+TUNE_PP8_WIDE = 29
+TUNE_PP8_WIDE_VARIANT = 30
 TUNE_ROI_ST = 31
 TUNE_MSM_WAVE = 32
-TUNE_ROI_LANE = 19
-TUNE_CONV_PP = 24
-TUNE_PP8, TUNE_PP8_STAGES, TUNE_PP8_VARIANT, TUNE_PP8_PROFILE, TUNE_PP8_WIDE, TUNE_PP8_WIDE_VARIANT = 25, 26, 27, 28, 29, 30
-TUNE_ROI_CPB, TUNE_ROI_PREFETCH, TUNE_GEMM_PINGPONG, TUNE_FP8_K64, TUNE_ROI_MAP64_A, TUNE_ROI_LDS_KB = 10, 11, 12, 13, 14, 15
 
 
 def tune(knob, value):
     """drn_tune: set a tuning knob (A/B measurements, tests); returns the previous value"""
     return C.lib().drn_tune(int(knob), int(value))
+
+
+@contextlib.contextmanager
+def tuned(knobs=None, tile=None):
+    """`with tuned({TUNE_PP8: 0, ...}) as prev:` sets the knobs in the dict's order, yields {knob: previous value} and on exit -
+    an exception included - sets those previous values again, last knob first.  What is restored is what drn_tune returned,
+    never a literal default.  `tile` pins the GEMM tile (gemm_set_tile) the same way; its previous value is prev["tile"]."""
+    prev, undo = {}, []
+    try:
+        if tile is not None:
+            prev["tile"] = gemm_set_tile(tile)
+            undo.append((gemm_set_tile, prev["tile"]))
+        for k, v in (knobs or {}).items():
+            prev[k] = tune(k, v)
+            undo.append((functools.partial(tune, k), prev[k]))
+        yield prev
+    finally:
+        for fn, old in reversed(undo):
+            fn(old)
 
 
 def gemm_nt(A, B, M, N, K, out=None, splits=1, accumulate=False):

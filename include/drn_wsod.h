@@ -233,39 +233,38 @@ int drn_gemm_tn_sgd(const void* A, const void* Bt, void* grad_bucket, int M, int
 int drn_gemm_set_tile(int tile);
 
 /* tuning knobs for A/B measurements and tests (defaults = the measured best); returns the previous value, -1 for an
- * unknown knob.  DRN_TUNE_GEMM_PERSISTENT (1): 0/1 - 256x256 GEMM launches with more (tile, K-split) work items than CUs
- * run as ONE resident workgroup per CU that loops over its share (default 1; same arithmetic, bit-identical results).
- * DRN_TUNE_SGD_GRID (2): workgroups (x) of the optimizer kernel (default 512).
- * DRN_TUNE_GEMM_GROUP_ROWS (3): tile rows per group of the 256x256 GEMM's XCD patch mapping (0 = heuristic). */
-#define DRN_TUNE_GEMM_PERSISTENT 1
-#define DRN_TUNE_SGD_GRID 2
-#define DRN_TUNE_GEMM_GROUP_ROWS 3
-#define DRN_TUNE_CONV_KSPLIT 5 /* 0/1: 32x32 wave-K-split conv kernel for latency-bound small-map layers (default 1) */
+ * unknown knob.  A value a knob does not take is ignored (the setting stays, and is what drn_tune returns).  The knobs, by id
+ * (the library keeps them in one table: csrc/tune.h holds the state and the defaults, drn_tune in csrc/gemm_conv.hip the rule
+ * of every knob): */
+#define DRN_TUNE_GEMM_PERSISTENT 1 /* 0/1 - 256x256 GEMM launches with more (tile, K-split) work items than CUs run as ONE resident workgroup per CU that loops over its share (default 1; same arithmetic, bit-identical results) */
+#define DRN_TUNE_SGD_GRID 2 /* workgroups (x) of the optimizer kernel (8..65535, default 512) */
+#define DRN_TUNE_GEMM_GROUP_ROWS 3 /* tile rows per group of the 256x256 GEMM's XCD patch mapping (0..64; 0 = heuristic) */
 #define DRN_TUNE_ROI_MAP64 4 /* 64-ROI x 8-channel whole-map ROIPool for the bf16 (A, A^T) pair: 0 = off, else threads per workgroup (256 / 512 / 1024, default 512) */
+#define DRN_TUNE_CONV_KSPLIT 5 /* 0/1: 32x32 wave-K-split conv kernel for latency-bound small-map layers (default 1) */
 #define DRN_TUNE_GEMM_TAIL_SPLIT 6 /* 0/1: a persistent 256x256 launch whose last round would be < 3/8 full runs an exact number of rounds; the peeled tile columns go to the small-tile kernel first (default 1; bit-identical) */
 #define DRN_TUNE_CONV_KS_TILES 7 /* largest number of 64x64 tiles of ONE image's layer that still runs on the wave-K-split conv kernel (0 = default: CUs / 4) */
 #define DRN_TUNE_CONV_K2_TILES 8 /* largest number of 64x64 tiles of ONE image's layer that runs two K-groups per tile (conv_nhwc_k2_kernel); -1 = default (2 x CUs), 0 = off */
+#define DRN_TUNE_CONV_PATCH 9 /* 0 = never use the LDS-resident-patch kernel for 3x3 / 64 -> 64 channel convs; 1 = default (maps of >= 32768 pixels); > 1 = that many pixels per image at least; drn_tune returns the pixel threshold while the kernel is on, 0 while it is off */
 #define DRN_TUNE_ROI_CPB 10 /* 64-ROI ROIPool: most 8-channel chunks one workgroup walks (power of two, default 1; halved until two workgroups per CU remain): bin bounds / item table once per workgroup - faster stand-alone (4-8), slower inside the training step */
 #define DRN_TUNE_ROI_PREFETCH 11 /* 0/1 (default 1): 64-ROI ROIPool keeps two map-slice buffers and fetches the next chunk's slice under the scan */
 #define DRN_TUNE_GEMM_PINGPONG 12 /* 0/1 (default 1): bf16 256x256 GEMMs run the ping-pong mainloop - the two waves of a SIMD half a phase apart, four [reads + DMA | 8 MFMAs] phases per K slab, half-tile LDS-DMA spread over the slab; bit-identical to the lock-step pipeline it replaces (0) */
-#define DRN_TUNE_ROI_LDS_KB 15 /* 60..154 (default 154): LDS a 64-ROI pooling block may take for map slice + tile; 76 stages larger maps in row bands so that two blocks share a CU */
-#define DRN_TUNE_ROI_MAP64_A 14 /* 0/1 (default 0): the 64-ROI ROIPool kernel also when only A is asked for (no A^T) */
 #define DRN_TUNE_FP8_K64 13 /* 0/1 (default 1): fp8 convolutions multiply with v_mfma_scale_f32_32x32x64_f8f6f4 (unit scales; the fp8 MFMA rate) instead of the K = 16 non-scaled form (bf16 rate); same exact products, another fp32 summation order */
+#define DRN_TUNE_ROI_MAP64_A 14 /* 0/1 (default 0): the 64-ROI ROIPool kernel also when only A is asked for (no A^T) */
+#define DRN_TUNE_ROI_LDS_KB 15 /* 60..154 (default 154): LDS a 64-ROI pooling block may take for map slice + tile; 76 stages larger maps in row bands so that two blocks share a CU */
 #define DRN_TUNE_GEMM_NWG 18 /* resident workgroups of persistent 256x256 launches (multiple of 8; 0 = default: one per CU) - for launches on a CU-masked stream */
+#define DRN_TUNE_ROI_LANE 19 /* 0/1 (default 1): the bf16 training operand A from the lane-per-bin ROIPool kernel (a wave per ROI, lane = bin: every channel leaves as one 98-byte run per store instruction); 0 = the 64-ROI kernel writes A; 2 = the lane kernel but never its walking form; 3 (tests) = 1 with one sub-group of 64 ROIs per block of the walking form instead of two - drn_tune then reports 1, and any other value brings the two sub-groups back */
 #define DRN_TUNE_SGDP_EPILOGUE 20 /* 0/1 (default 1): the tile epilogue of drn_gemm_tn_sgd moves the bf16 gradient tile LDS -> global four 16-byte pieces per trip instead of one (A/B knob; bit-identical) */
 #define DRN_TUNE_ROI_LANE_REPS 22 /* lane-per-bin ROIPool on maps that leave one block per CU: groups of 64 ROIs a block walks with one staged map slice (0 = default: 4, halved while fewer than two rounds of blocks would remain; 1 = a block per group) */
-#define DRN_TUNE_MSM_WAVE 32 /* 0/1 (default 1): drn_mean_softmax for heads of <= 64 columns as a wave per row / lane per class (one coalesced load per head, the denominator summed in class order: bit-identical); 0 = the thread-per-row kernel */
-#define DRN_TUNE_ROI_ST 31 /* RoIPool from a sparse table of block maxima (four table cells per bin instead of the window's cells; needs the workspace of drn_roi_pool_workspace_bytes): 0 = off, 1 (default) = where it beats the window kernels (maps of >= 1800 cells with >= 1500 ROIs, >= 3000 cells with >= 600 ROIs, and every map whose LDS slice holds only 4 channels per cell - the dilated-C5 stride-8 map of a real-size image - with >= 400 ROIs), 2 = every map whose slice fits (>= 64 ROIs) */
-#define DRN_TUNE_ROI_LANE 19 /* 0/1 (default 1): the bf16 training operand A from the lane-per-bin ROIPool kernel (a wave per ROI, lane = bin: every channel leaves as one 98-byte run per store instruction); 0 = the 64-ROI kernel writes A */
 #define DRN_TUNE_CONV_RING 23 /* register-ring conv kernels (conv_ring.hip; bf16, Cin % 64 == 0, layers beyond the latency-bound small maps): 0 = off (the tiles of gemm_conv.hip), 1 = default (64x64 tile, class by measurement), 64 / 128 = pin the 64x64 / 128x128 tile (any other value is ignored: drn_tune returns the unchanged setting); every tile gives the same bits as the 64x64 / 128x128 tiled kernel */
 #define DRN_TUNE_CONV_PP 24 /* 1x1 / stride-1 bf16 convs of large maps on the 256x256 ping-pong GEMM mainloop with the conv epilogue (conv1x1_pp_kernel): 0 = off, 1 = default (Cout >= 256 and >= 192 tiles of 256x256 per image, or >= 100 tiles with K >= 1024), n > 1 = at least n tiles, any Cout; same bits as the tiled kernels */
-#define DRN_TUNE_CONV_PATCH 9 /* 0 = never use the LDS-resident-patch kernel for 3x3 / 64 -> 64 channel convs; 1 = default (maps of >= 32768 pixels); > 1 = that many pixels per image at least */
 #define DRN_TUNE_PP8 25 /* eight-wave ping-pong kernel (pp8.hip: 128x128 or 256x128 tile, two waves per SIMD half a phase apart; bf16 convs with Cin % 64 == 0 and drn_linear_act_fwd): 0 = off, 1 = default class (measured per layer shape, see drn_pp8_conv_try), 2 = every layer in the kernel's class; same bits as the tiled kernels */
 #define DRN_TUNE_PP8_STAGES 26 /* 3 / 4 / 5 (default 5): 32-KB LDS stages of the 128x128 form's ring = 1 / 2 / 3 K slabs in flight (A/B knob; bit-identical) */
 #define DRN_TUNE_PP8_VARIANT 27 /* schedule variant of that kernel (A/B knob; bit-identical): 0 = a slab's four DMA pieces in the fragment-read phase, 1 (default) = two there and two between the MFMAs, 2 = all between the MFMAs, + 4 = no s_setprio around the MFMAs, + 8 = profile build (shader-clock split of the mainloop) */
 #define DRN_TUNE_PP8_PROFILE 28 /* any value: print (stderr) and clear the per-phase shader-clock sums the profile builds (DRN_TUNE_PP8_VARIANT + 8) accumulated for workgroup 0; returns 0 */
-#define DRN_TUNE_PP8_WIDE_VARIANT 30 /* schedule variant of the 256x128 form (A/B knob; bit-identical): bit 0 = all six DMA pieces of a slab in the second fragment-read phase (else three there, three between the MFMAs), 4 = no s_setprio, 8 = profile build; default 4 */
 #define DRN_TUNE_PP8_WIDE 29 /* the 256x128 form of that kernel (wave tile 64x64, three 48-KB stages): 0 = never, 1 = default (layers that give it >= 5/8 of the CUs' worth of tiles per image), 2 = always */
+#define DRN_TUNE_PP8_WIDE_VARIANT 30 /* schedule variant of the 256x128 form (A/B knob; bit-identical): bit 0 = all six DMA pieces of a slab in the second fragment-read phase (else three there, three between the MFMAs), 4 = no s_setprio, 8 = profile build; default 4 */
+#define DRN_TUNE_ROI_ST 31 /* RoIPool from a sparse table of block maxima (four table cells per bin instead of the window's cells; needs the workspace of drn_roi_pool_workspace_bytes): 0 = off, 1 (default) = where it beats the window kernels (maps of >= 1800 cells with >= 1500 ROIs, >= 3000 cells with >= 600 ROIs, and every map whose LDS slice holds only 4 channels per cell - the dilated-C5 stride-8 map of a real-size image - with >= 400 ROIs), 2 = every map whose slice fits (>= 64 ROIs); 10 / 11 = its profile builds on / off and 12 = print (stderr) and clear their counters - all three leave the setting */
+#define DRN_TUNE_MSM_WAVE 32 /* 0/1 (default 1): drn_mean_softmax for heads of <= 64 columns as a wave per row / lane per class (one coalesced load per head, the denominator summed in class order: bit-identical); 0 = the thread-per-row kernel */
 int drn_tune(int knob, int value);
 
 /* relu_(fc(x)) + F.dropout(p) of DiscriminativeAdaptionNeck.forward (projects/WSL/wsl/modeling/roi_heads/box_head.py:82-91)

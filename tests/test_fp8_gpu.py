@@ -54,11 +54,8 @@ def test_conv_fp8(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, k64):
     exactly, so both sit within fp32 summation order of the fp64-free reference."""
     bf_res = out == "fp8bf16res"
     out = "fp8" if bf_res else out
-    old = drn.tune(drn.TUNE_FP8_K64, k64)
-    try:
+    with drn.tuned({drn.TUNE_FP8_K64: k64}):
         _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res)
-    finally:
-        drn.tune(drn.TUNE_FP8_K64, old)
 
 
 def _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res):

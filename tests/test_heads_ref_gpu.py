@@ -357,14 +357,11 @@ def test_mean_softmax(drn, cabi, C, H):
     cd = torch.tensor(col0s, dtype=torch.int32, device=DEV)
     res = {}
     for wave in (1, 0):
-        old = drn.tune(drn.TUNE_MSM_WAVE, wave)
-        try:
+        with drn.tuned({drn.TUNE_MSM_WAVE: wave}):
             for bg in (False, True):
                 probs = torch.full((M + 1, C), NAN, device=DEV)
                 cabi.call("drn_mean_softmax", cabi.ptr(lgd), ld, cabi.ptr(cd), H, C, cabi.ptr(probs), M, int(bg), cabi.stream())
                 res[wave, bg] = probs.cpu()
-        finally:
-            drn.tune(drn.TUNE_MSM_WAVE, old)
     for (wave, bg), p in res.items():
         assert bool(torch.isnan(p[M]).all())
         ref, b = (torch.cat([p64[:, 1:], p64[:, :1]], 1), torch.cat([bnd[:, 1:], bnd[:, :1]], 1)) if bg else (p64, bnd)

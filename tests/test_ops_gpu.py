@@ -81,8 +81,7 @@ def test_gemm_nt_tile256(drn, dtype, shape):
     ref = _q(A, dtype).double() @ _q(B, dtype).double().t()
     mag = _q(A, dtype).abs().double() @ _q(B, dtype).abs().double().t()
     tol = 4 * 2.0 ** -24 * math.sqrt(K) * mag + 1e-6
-    prev = drn.gemm_set_tile(256)
-    try:
+    with drn.tuned(tile=256):
         for splits in (1, 2):
             got = drn.gemm_nt(Ad, Bd, M, N, Kp, splits=splits).sum(0).cpu().double()
             assert ((got - ref).abs() <= tol).all(), float(((got - ref).abs() / (mag + 1e-9)).max())
@@ -95,8 +94,6 @@ def test_gemm_nt_tile256(drn, dtype, shape):
         Bm = (torch.arange(n * n, dtype=torch.float32).reshape(n, n) % 251)
         Cd = drn.gemm_nt(torch.eye(n).to(DEV), Bm.to(DEV), n, n, n)
         assert torch.equal(Cd[0].cpu(), Bm.t().contiguous())
-    finally:
-        drn.gemm_set_tile(prev)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -109,9 +106,7 @@ def test_gemm_persistent_equals_one_tile_grid(drn, dtype, M, N, K, splits):
     Ad, Bd = _padded(A, dtype, drn), _padded(B, dtype, drn)
     Kp = Ad.shape[1]
     C0 = _rnd((M, N), 16).to(DEV)
-    prev_tile = drn.gemm_set_tile(256)
-    prev = drn.tune(drn.TUNE_GEMM_PERSISTENT, 0)
-    try:
+    with drn.tuned({drn.TUNE_GEMM_PERSISTENT: 0}, tile=256):
         res = []
         for persistent in (0, 1):
             drn.tune(drn.TUNE_GEMM_PERSISTENT, persistent)
@@ -130,9 +125,6 @@ def test_gemm_persistent_equals_one_tile_grid(drn, dtype, M, N, K, splits):
         mag = _q(A, dtype).abs().double() @ _q(B, dtype).abs().double().t()
         got = res[1][0].sum(0).cpu().double()
         assert ((got - ref).abs() <= 4 * 2.0 ** -24 * math.sqrt(K) * mag + 1e-6).all()
-    finally:
-        drn.tune(drn.TUNE_GEMM_PERSISTENT, prev)
-        drn.gemm_set_tile(prev_tile)
 
 
 @pytest.mark.parametrize("shapes", [((4096, 2048, 2048, 1, True), (2000, 2048, 4096, 4, False)),
@@ -145,8 +137,7 @@ def test_gemm_nt_pair_equals_two_calls(drn, shapes):
     BIT-identical - the fc7 weight-gradient / input-gradient pair of the bench shape, ragged shapes, very unequal work,
     accumulate and split-K outputs."""
     dtype = torch.bfloat16
-    prev_tile = drn.gemm_set_tile(256)
-    try:
+    with drn.tuned(tile=256):
         gs, refs = [], []
         for i, (M, N, K, splits, acc) in enumerate(shapes):
             A, B = _padded(_rnd((M, K), 41 + i), dtype, drn), _padded(_rnd((N, K), 51 + i), dtype, drn)
@@ -160,8 +151,6 @@ def test_gemm_nt_pair_equals_two_calls(drn, shapes):
         torch.cuda.synchronize()
         for g, ref in zip(gs, refs):
             assert torch.equal(g["out"], ref)
-    finally:
-        drn.gemm_set_tile(prev_tile)
 
 
 @pytest.mark.parametrize("M,N,Kb,splits", [(256, 256, 64, 1), (1024, 6400, 2000, 1), (700, 1000, 130, 1), (2048, 1024, 2000, 1),
@@ -182,10 +171,8 @@ def test_gemm_tn_equals_nt_on_the_transpose(drn, M, N, Kb, splits):
     Bd = torch.zeros((N, K), dtype=dtype, device=DEV)  # the materialised transpose, K padded with zeros
     Bd[:, :Kb] = Btd[:, :N].t()
     C0 = _rnd((M, N), 23).to(DEV)
-    prev_tile = drn.gemm_set_tile(256)
-    prev_pp = drn.tune(drn.TUNE_GEMM_PINGPONG, 1)
-    prev_ts = drn.tune(drn.TUNE_GEMM_TAIL_SPLIT, 0)  # (the NT side would peel columns into the small-tile kernel: same bits, other kernel)
-    try:
+    # (tail split off: the NT side would peel columns into the small-tile kernel: same bits, other kernel)
+    with drn.tuned({drn.TUNE_GEMM_PINGPONG: 1, drn.TUNE_GEMM_TAIL_SPLIT: 0}, tile=256):
         nt = drn.gemm_nt(Ad, Bd, M, N, K, splits=splits)
         tn = drn.gemm_tn(Ad, Btd[:, :N], M, N, K, Kb, splits=splits)
         torch.cuda.synchronize()
@@ -202,10 +189,6 @@ def test_gemm_tn_equals_nt_on_the_transpose(drn, M, N, Kb, splits):
         ref = _q(A, dtype).double() @ _q(Bt[:, :N], dtype).double()
         mag = _q(A, dtype).abs().double() @ _q(Bt[:, :N], dtype).abs().double()
         assert ((tn.sum(0).cpu().double() - ref).abs() <= 4 * 2.0 ** -24 * math.sqrt(K) * mag + 1e-6).all()
-    finally:
-        drn.tune(drn.TUNE_GEMM_TAIL_SPLIT, prev_ts)
-        drn.tune(drn.TUNE_GEMM_PINGPONG, prev_pp)
-        drn.gemm_set_tile(prev_tile)
 
 
 @pytest.mark.parametrize("M,N,K,splits", [(2000, 2048, 3136, 4), (256, 256, 64, 1), (1030, 17000, 192, 1), (300, 70000, 128, 1),
@@ -222,10 +205,7 @@ def test_gemm_pingpong_bit_identical(drn, M, N, K, splits):
     Ad, Bd = _padded(A, dtype, drn), _padded(B, dtype, drn)
     Kp = Ad.shape[1]
     C0 = _rnd((M, N), 46).to(DEV)
-    prev_tile = drn.gemm_set_tile(256)
-    prev_p = drn.tune(drn.TUNE_GEMM_PERSISTENT, 1)
-    prev = drn.tune(drn.TUNE_GEMM_PINGPONG, 1)
-    try:
+    with drn.tuned({drn.TUNE_GEMM_PERSISTENT: 1, drn.TUNE_GEMM_PINGPONG: 1}, tile=256):
         res = {}
         for persistent in (0, 1):
             drn.tune(drn.TUNE_GEMM_PERSISTENT, persistent)
@@ -249,10 +229,6 @@ def test_gemm_pingpong_bit_identical(drn, M, N, K, splits):
         mag = _q(A, dtype).abs().double() @ _q(B, dtype).abs().double().t()
         got = res[(1, 1)][0][0].sum(0).cpu().double()
         assert ((got - ref).abs() <= 4 * 2.0 ** -24 * math.sqrt(K) * mag + 1e-6).all()
-    finally:
-        drn.tune(drn.TUNE_GEMM_PINGPONG, prev)
-        drn.tune(drn.TUNE_GEMM_PERSISTENT, prev_p)
-        drn.gemm_set_tile(prev_tile)
 
 
 def test_gemm_joint_peel_of_row_slabs_bit_identical(drn):
@@ -264,8 +240,7 @@ def test_gemm_joint_peel_of_row_slabs_bit_identical(drn):
     A, B = _rnd((M, K), 34), _rnd((N, K), 35)
     Ad, Bd = _padded(A, torch.bfloat16, drn), _padded(B, torch.bfloat16, drn)
     Kp = Ad.shape[1]
-    prev_tile = drn.gemm_set_tile(0)
-    try:
+    with drn.tuned(tile=0):
         n0 = drn.gemm_nt_main_cols(M // 2, N)
         assert n0 == 64 * 256 and drn.gemm_nt_main_cols(M // 2, n0) == n0  # the main columns are not peeled again
         a = torch.zeros((M, N), dtype=torch.bfloat16, device=DEV)
@@ -279,8 +254,6 @@ def test_gemm_joint_peel_of_row_slabs_bit_identical(drn):
         assert torch.equal(a, b)
         ref = _q(A, torch.bfloat16).double() @ _q(B, torch.bfloat16).double().t()
         assert (b.cpu().double() - ref).abs().max() <= 2.0 ** -8 * ref.abs().max() + 1e-6
-    finally:
-        drn.gemm_set_tile(prev_tile)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -294,10 +267,7 @@ def test_gemm_tail_split_bit_identical(drn, dtype, M, N, K):
     Ad, Bd = _padded(A, dtype, drn), _padded(B, dtype, drn)
     Kp = Ad.shape[1]
     C0 = _rnd((M, N), 26).to(DEV)
-    prev_tile = drn.gemm_set_tile(256)
-    prev_p = drn.tune(drn.TUNE_GEMM_PERSISTENT, 1)
-    prev = drn.tune(drn.TUNE_GEMM_TAIL_SPLIT, 0)
-    try:
+    with drn.tuned({drn.TUNE_GEMM_PERSISTENT: 1, drn.TUNE_GEMM_TAIL_SPLIT: 0}, tile=256):
         res = []
         for split in (0, 1):
             drn.tune(drn.TUNE_GEMM_TAIL_SPLIT, split)
@@ -316,10 +286,6 @@ def test_gemm_tail_split_bit_identical(drn, dtype, M, N, K):
         mag = _q(A, dtype).abs().double() @ _q(B, dtype).abs().double().t()
         got = res[1][0].sum(0).cpu().double()
         assert ((got - ref).abs() <= 4 * 2.0 ** -24 * math.sqrt(K) * mag + 1e-6).all()
-    finally:
-        drn.tune(drn.TUNE_GEMM_TAIL_SPLIT, prev)
-        drn.tune(drn.TUNE_GEMM_PERSISTENT, prev_p)
-        drn.gemm_set_tile(prev_tile)
 
 
 def test_stage_heads_inputs(drn):
@@ -437,13 +403,10 @@ def test_conv3x3_c64_patch_kernel(drn, case):
     if relu:
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, 64)
-    prev = drn.tune(drn.TUNE_CONV_PATCH, 1)
-    try:
+    with drn.tuned({drn.TUNE_CONV_PATCH: 1}):
         y1 = drn.conv2d_nhwc(xd, wp, 64, 3, 3, 1, 1, 1, scale, bias, res, relu)
         drn.tune(drn.TUNE_CONV_PATCH, 0)
         y0 = drn.conv2d_nhwc(xd, wp, 64, 3, 3, 1, 1, 1, scale, bias, res, relu)
-    finally:
-        drn.tune(drn.TUNE_CONV_PATCH, prev if prev else 1)
     torch.cuda.synchronize()
     assert torch.equal(y1, y0)
     got = y1.float().cpu().permute(0, 3, 1, 2)
@@ -475,11 +438,9 @@ def test_conv2d_wave_k_split(drn, dtype, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, k, k, stride, pad, dil, scale, bias, res, relu)
-    assert drn.tune(drn.TUNE_CONV_KSPLIT, 0) == 1
-    try:
+    with drn.tuned({drn.TUNE_CONV_KSPLIT: 0}) as prev:
+        assert prev[drn.TUNE_CONV_KSPLIT] == 1
         tiled = run()
-    finally:
-        drn.tune(drn.TUNE_CONV_KSPLIT, 1)
     ys = [run() for _ in range(3)]
     for y in ys[1:]:
         assert torch.equal(y, ys[0])
@@ -526,11 +487,8 @@ def test_conv_ring_kernels(drn, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, k, k, stride, pad, dil, scale, bias, res, relu)
-    assert drn.tune(drn.TUNE_CONV_RING, 0) == 1
-    k2 = drn.tune(drn.TUNE_CONV_K2_TILES, 0)
-    ks = drn.tune(drn.TUNE_CONV_KSPLIT, 0)
-    p8 = drn.tune(drn.TUNE_PP8, 0)
-    try:
+    with drn.tuned({drn.TUNE_CONV_RING: 0, drn.TUNE_CONV_K2_TILES: 0, drn.TUNE_CONV_KSPLIT: 0, drn.TUNE_PP8: 0}) as prev:
+        assert prev[drn.TUNE_CONV_RING] == 1
         tiled = run()  # conv_nhwc_kernel<64x64 | 128x128>
         ys = {}
         for pin in (64, 128, 1):
@@ -538,11 +496,6 @@ def test_conv_ring_kernels(drn, case):
             ys[pin] = run()
         drn.tune(drn.TUNE_CONV_RING, 64)
         again = run()
-    finally:
-        drn.tune(drn.TUNE_CONV_RING, 1)
-        drn.tune(drn.TUNE_CONV_K2_TILES, k2)
-        drn.tune(drn.TUNE_CONV_KSPLIT, ks)
-        drn.tune(drn.TUNE_PP8, p8)
     torch.cuda.synchronize()
     for pin, y in ys.items():
         assert torch.equal(y, tiled), (pin, float((y.float() - tiled.float()).abs().max()))
@@ -585,32 +538,17 @@ def test_pp8_conv_kernel(drn, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, k, k, stride, pad, dil, scale, bias, res, relu)
-    assert drn.tune(drn.TUNE_PP8, 0) == 1
-    ring = drn.tune(drn.TUNE_CONV_RING, 0)
-    k2 = drn.tune(drn.TUNE_CONV_K2_TILES, 0)
-    ks = drn.tune(drn.TUNE_CONV_KSPLIT, 0)
-    cpp = drn.tune(drn.TUNE_CONV_PP, 0)
-    try:
+    with drn.tuned({drn.TUNE_PP8: 0, drn.TUNE_CONV_RING: 0, drn.TUNE_CONV_K2_TILES: 0, drn.TUNE_CONV_KSPLIT: 0, drn.TUNE_CONV_PP: 0}) as prev:
+        assert prev[drn.TUNE_PP8] == 1
         tiled = run()  # conv_nhwc_kernel<64x64 | 128x128>
         drn.tune(drn.TUNE_PP8, 2)
         ys = {}
         for stages, variant, wide in ((3, 0, 0), (4, 0, 0), (4, 1, 0), (5, 0, 0), (5, 2, 0), (5, 5, 0), (5, 1, 0), (5, 1, 2), (5, 0, 2),
                                       (5, 1, 1)):
-            drn.tune(drn.TUNE_PP8_STAGES, stages)
-            drn.tune(drn.TUNE_PP8_VARIANT, variant)
-            drn.tune(drn.TUNE_PP8_WIDE, wide)  # 2: the 256x128 form (three 48-KB stages) whatever the tile count
-            drn.tune(drn.TUNE_PP8_WIDE_VARIANT, 5 if variant else 0)  # (its two DMA placements)
-            ys[(stages, variant, wide)] = [run() for _ in range(3)]
-    finally:
-        drn.tune(drn.TUNE_PP8, 1)
-        drn.tune(drn.TUNE_PP8_STAGES, 5)
-        drn.tune(drn.TUNE_PP8_VARIANT, 1)
-        drn.tune(drn.TUNE_PP8_WIDE, 1)
-        drn.tune(drn.TUNE_PP8_WIDE_VARIANT, 4)
-        drn.tune(drn.TUNE_CONV_RING, ring)
-        drn.tune(drn.TUNE_CONV_K2_TILES, k2)
-        drn.tune(drn.TUNE_CONV_KSPLIT, ks)
-        drn.tune(drn.TUNE_CONV_PP, cpp)
+            with drn.tuned({drn.TUNE_PP8_STAGES: stages, drn.TUNE_PP8_VARIANT: variant,
+                            drn.TUNE_PP8_WIDE: wide,  # 2: the 256x128 form (three 48-KB stages) whatever the tile count
+                            drn.TUNE_PP8_WIDE_VARIANT: 5 if variant else 0}):  # (its two DMA placements)
+                ys[(stages, variant, wide)] = [run() for _ in range(3)]
     torch.cuda.synchronize()
     for stages, lst in ys.items():
         for y in lst:
@@ -648,13 +586,8 @@ def test_linear_act_fwd_equals_gemm_then_act(drn, M, N, K, mode, relu):
         outT = torch.full((N, Mp), 7.0, dtype=dt, device=DEV)
         kw = dict(bias=bias, relu=relu, mask=mask, seed=seed, drop_p=drop_p, out=out, outT=outT, seed_dev=seed_dev)
         if fused:
-            drn.tune(drn.TUNE_PP8_STAGES, fused[0])
-            drn.tune(drn.TUNE_PP8_WIDE, fused[1])
-            try:
+            with drn.tuned({drn.TUNE_PP8_STAGES: fused[0], drn.TUNE_PP8_WIDE: fused[1]}):
                 assert drn.linear_act_fwd(A, W, M, N, K, **kw)
-            finally:
-                drn.tune(drn.TUNE_PP8_STAGES, 5)
-                drn.tune(drn.TUNE_PP8_WIDE, 1)
         else:
             drn.bias_act_fwd(drn.gemm_nt(A, W, M, N, K), M, N, **kw)
         outs.append((out, outT))
@@ -727,22 +660,12 @@ def test_conv1x1_pp_kernel(drn, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, 1, 1, 1, 0, 1, scale, bias, res, relu)
-    assert drn.tune(drn.TUNE_CONV_PP, 0) == 1
-    ring = drn.tune(drn.TUNE_CONV_RING, 0)
-    k2 = drn.tune(drn.TUNE_CONV_K2_TILES, 0)
-    ks = drn.tune(drn.TUNE_CONV_KSPLIT, 0)
-    p8 = drn.tune(drn.TUNE_PP8, 0)
-    try:
+    with drn.tuned({drn.TUNE_CONV_PP: 0, drn.TUNE_CONV_RING: 0, drn.TUNE_CONV_K2_TILES: 0, drn.TUNE_CONV_KSPLIT: 0, drn.TUNE_PP8: 0}) as prev:
+        assert prev[drn.TUNE_CONV_PP] == 1
         tiled = run()  # conv_nhwc_kernel<128x128>
         drn.tune(drn.TUNE_CONV_PP, 2)  # (any layer of >= 2 tiles)
         y = run()
         again = run()
-    finally:
-        drn.tune(drn.TUNE_CONV_PP, 1)
-        drn.tune(drn.TUNE_PP8, p8)
-        drn.tune(drn.TUNE_CONV_RING, ring)
-        drn.tune(drn.TUNE_CONV_K2_TILES, k2)
-        drn.tune(drn.TUNE_CONV_KSPLIT, ks)
     torch.cuda.synchronize()
     assert torch.equal(y, tiled), float((y.float() - tiled.float()).abs().max())
     assert torch.equal(again, y)
@@ -900,21 +823,20 @@ def test_roi_pool_lane_kernel_equals_map64(drn, C, H, W, R, t0, n_img):
     # maps; 0: the 64-ROI kernel
     # (lane 1 pools through the chunk-major scratch copy where the walking kernel takes the map - drn_roi_pool_nhwc_ws -, lane 3 without)
     for lane in (3, 2, 1, 0):
-        old = drn.tune(19, lane)
-        old22 = drn.tune(22, 8) if lane == 3 else None
+        knobs = {drn.TUNE_ROI_LANE: lane}
+        if lane == 3:
+            knobs[drn.TUNE_ROI_LANE_REPS] = 8
         drn.ROI_WORKSPACE = lane != 3
         try:
-            a = torch.full((R, drn.kpad(k, dtype)), 3.0, dtype=dtype, device=DEV)
-            a[:, k:] = 0
-            t = torch.full((k, drn.kpad(R, dtype)), 7.0, dtype=dtype, device=DEV)
-            drn.roi_pool_nhwc(fd, rois.to(DEV), obj.to(DEV), P, scale, out=a, out_t=t, t_first_channel=t0)
-            torch.cuda.synchronize()
-            res[lane] = (a, t)
+            with drn.tuned(knobs):
+                a = torch.full((R, drn.kpad(k, dtype)), 3.0, dtype=dtype, device=DEV)
+                a[:, k:] = 0
+                t = torch.full((k, drn.kpad(R, dtype)), 7.0, dtype=dtype, device=DEV)
+                drn.roi_pool_nhwc(fd, rois.to(DEV), obj.to(DEV), P, scale, out=a, out_t=t, t_first_channel=t0)
+                torch.cuda.synchronize()
+                res[lane] = (a, t)
         finally:
-            drn.tune(19, old)
             drn.ROI_WORKSPACE = True
-            if old22 is not None:
-                drn.tune(22, old22)
     ref, _ = O.roi_pool_forward(_q(feat, dtype), rois, P, scale)
     ref = _q(ref * (obj + 1).view(-1, 1, 1, 1), dtype).reshape(R, -1)
     for lane in (3, 2, 1):
@@ -968,8 +890,7 @@ def test_roi_pool_sparse_table_kernel(drn, C, H, W, R, n_img, st, scale):
     lib = drn.C.lib()
     res = {}
     for knob in (0, st):
-        old = drn.tune(drn.TUNE_ROI_ST, knob)
-        try:
+        with drn.tuned({drn.TUNE_ROI_ST: knob}):
             want = lib.drn_roi_pool_workspace_bytes(n_img, H, W, C, P, R, 0, 0, drn.C.dt(dtype), drn.C.dt(dtype))
             if knob:
                 assert want >= n_img * H * W * C * 2 + R * 257, "the shape must take the sparse-table kernel"
@@ -979,8 +900,6 @@ def test_roi_pool_sparse_table_kernel(drn, C, H, W, R, n_img, st, scale):
             b = drn.roi_pool_nhwc(fd, rois.to(DEV), None, P, scale)
             torch.cuda.synchronize()
             res[knob] = (a, b)
-        finally:
-            drn.tune(drn.TUNE_ROI_ST, old)
     ref, _ = O.roi_pool_forward(_q(feat, dtype), rois, P, scale)
     ref1 = _q(ref * (obj + 1).view(-1, 1, 1, 1), dtype).reshape(R, -1)
     assert torch.equal(res[st][0], res[0][0])
@@ -988,13 +907,12 @@ def test_roi_pool_sparse_table_kernel(drn, C, H, W, R, n_img, st, scale):
     assert torch.equal(res[st][0][:, :k].float().cpu(), ref1)
     assert torch.equal(res[st][1][:, :k].float().cpu(), _q(ref, dtype).reshape(R, -1))
     assert (res[st][0][:, k:] == 0).all()
-    old = drn.tune(drn.TUNE_ROI_ST, st)
     drn.ROI_WORKSPACE = False
     try:
-        c = drn.roi_pool_nhwc(fd, rois.to(DEV), obj.to(DEV), P, scale)
+        with drn.tuned({drn.TUNE_ROI_ST: st}):
+            c = drn.roi_pool_nhwc(fd, rois.to(DEV), obj.to(DEV), P, scale)
     finally:
         drn.ROI_WORKSPACE = True
-        drn.tune(drn.TUNE_ROI_ST, old)
     assert torch.equal(c, res[0][0])
 
 
@@ -1013,11 +931,8 @@ def test_roi_pool_sparse_table_full_size(drn, C, H, W, R):
     k = C * P * P
     outs = {}
     for knob in (0, 1):
-        old = drn.tune(drn.TUNE_ROI_ST, knob)
-        try:
+        with drn.tuned({drn.TUNE_ROI_ST: knob}):
             outs[knob] = drn.roi_pool_nhwc(fd, rois, obj, P, scale)
-        finally:
-            drn.tune(drn.TUNE_ROI_ST, old)
     assert drn.C.lib().drn_roi_pool_workspace_bytes(1, H, W, C, P, R, 0, 0, drn.C.dt(dtype), drn.C.dt(dtype)) >= H * W * C * 2 + R * 257
     assert torch.equal(outs[1], outs[0])
     const = drn.roi_pool_nhwc(torch.full_like(fd, 1.5), rois, obj, P, scale)[:, :k].float().view(R, C, 49)
@@ -1063,11 +978,8 @@ def test_roi_align_lane_kernel(drn, C, H, W, R, n_img, aligned, sr):
     run = lambda: drn.roi_pool_nhwc(fd, rois.to(DEV), obj.to(DEV), P, scale, mode=1, sampling_ratio=sr, aligned=aligned)
     lane = run()
     again = run()
-    old = drn.tune(drn.TUNE_ROI_LANE, 0)
-    try:
+    with drn.tuned({drn.TUNE_ROI_LANE: 0}):
         generic = run()
-    finally:
-        drn.tune(drn.TUNE_ROI_LANE, old)
     torch.cuda.synchronize()
     k = C * P * P
     assert torch.equal(lane[:, :k], generic[:, :k]), float((lane[:, :k].float() - generic[:, :k].float()).abs().max())
@@ -1369,12 +1281,9 @@ def test_softmax_ce(drn, K, M):
     assert torch.allclose(p2, ref, rtol=1e-5, atol=1e-9)
     # (round 6) the wave-per-row kernel sums the denominator in class order like the thread-per-row one: the same bits
     p2b = drn.mean_softmax(logits.to(DEV), [0, 3, 7], K + 1, bg_first=True).cpu()
-    old = drn.tune(drn.TUNE_MSM_WAVE, 0)
-    try:
+    with drn.tuned({drn.TUNE_MSM_WAVE: 0}):
         p3 = drn.mean_softmax(logits.to(DEV), [0, 3, 7], K + 1).cpu()
         p3b = drn.mean_softmax(logits.to(DEV), [0, 3, 7], K + 1, bg_first=True).cpu()
-    finally:
-        drn.tune(drn.TUNE_MSM_WAVE, old)
     assert torch.equal(p2, p3) and torch.equal(p2b, p3b)
     assert torch.equal(p2b[:, :-1], p2[:, 1:]) and torch.equal(p2b[:, -1], p2[:, 0])
 
@@ -1425,13 +1334,10 @@ def test_gemm_nt_bf16_output(drn, tile):
     M, N, K = 300, 520, 256
     A = torch.from_numpy(rs.standard_normal((M, K)).astype(np.float32)).to(DEV).to(torch.bfloat16)
     B = torch.from_numpy(rs.standard_normal((N, K)).astype(np.float32)).to(DEV).to(torch.bfloat16)
-    old = drn.gemm_set_tile(tile)
-    try:
+    with drn.tuned(tile=tile):
         ref = drn.gemm_nt(A, B, M, N, K)[0]
         out = torch.full((1, M, N), 7.0, dtype=torch.bfloat16, device=DEV)
         drn.gemm_nt(A, B, M, N, K, out=out)
-    finally:
-        drn.gemm_set_tile(old)
     assert torch.equal(out[0], ref.to(torch.bfloat16))
 
 
