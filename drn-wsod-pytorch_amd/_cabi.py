@@ -21,6 +21,8 @@ _SIGS = {
     "drn_conv2d_nhwc_q": "pppppp" + "iiiiiiiiii" + "lll" + "iiiifp",
     "drn_conv3x3_pw_nhwc": "pppp" + "i" + "pppp" + "p" + "iii" + "ll" + "f" + "ii" + "p",
     "drn_maxpool2x2_nhwc": "ppiiiiiip",
+    "drn_maxpool3x3s2_nhwc": "ppiiiiip",
+    "drn_stem7x7_pool_nhwc": "ppppp" + "iiiii" + "l" + "iip",
     "drn_roi_pool_nhwc": "pppppp" + "iiiiii" + "f" + "ll" + "iiiiip",
     "drn_roi_pool_nhwc_t": "pppppp" + "iiiiii" + "f" + "ll" + "iiiiiip",
     "drn_roi_pool_nhwc_ws": "pppppp" + "iiiiii" + "f" + "ll" + "iiiiii" + "plp",

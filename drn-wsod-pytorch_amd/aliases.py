@@ -52,6 +52,18 @@ def _table():
                                     build_model=rcnn.build_model, build_backbone=backbone.build_backbone,
                                     build_roi_heads=roi_heads.build_roi_heads, build_box_head=roi_heads.build_box_head,
                                     Backbone=backbone.Backbone, detector_postprocess=rcnn.detector_postprocess),
+        # the standard ResNet trunk under the reference's own class names (the WS classes keep the plain names here)
+        "detectron2.modeling.backbone": dict(Backbone=backbone.Backbone, build_backbone=backbone.build_backbone,
+                                             ResNet=backbone.ResNet, BasicStem=backbone.StdBasicStem,
+                                             BottleneckBlock=backbone.StdBottleneckBlock,
+                                             build_resnet_backbone=backbone.build_resnet_backbone,
+                                             BACKBONE_REGISTRY=registry.BACKBONE_REGISTRY),
+        "detectron2.modeling.backbone.resnet": dict(ResNet=backbone.ResNet, BasicStem=backbone.StdBasicStem,
+                                                    BottleneckBlock=backbone.StdBottleneckBlock,
+                                                    build_resnet_backbone=backbone.build_resnet_backbone,
+                                                    make_stage=backbone.ResNet.make_stage),
+        "detectron2.modeling.roi_heads": pick(roi_heads, "FastRCNNConvFCHead", "build_box_head", "ROIHeads", "build_roi_heads"),
+        "detectron2.modeling.roi_heads.box_head": pick(roi_heads, "FastRCNNConvFCHead", "build_box_head"),
         "detectron2.modeling.poolers": pick(roi_heads, "ROIPooler", "convert_boxes_to_pooler_format"),
         "detectron2.modeling.matcher": pick(roi_heads, "Matcher"),
         "detectron2.modeling.box_regression": pick(roi_heads, "Box2BoxTransform"),

@@ -8,7 +8,7 @@
 // sequence never changes, only the image size does - so the sequence is recorded ONCE as an array of DrnTrunkOp (weights,
 // folded FrozenBN affine, geometry, activation-slot indices) and every forward is one call: shapes per layer are derived
 // here from (Nb, H, W), and each op goes through the SAME entry points the per-layer path uses (drn_conv2d_nhwc_q,
-// drn_maxpool2x2_nhwc: identical kernel selection, identical launches, bit-identical results).
+// drn_maxpool2x2_nhwc / drn_maxpool3x3s2_nhwc: identical kernel selection, identical launches, bit-identical results).
 #include "drn_common.h"
 #include "../../include/drn_wsod.h"
 
@@ -42,6 +42,9 @@ int walk(const DrnTrunkOp* ops, int n_ops, int n_slots, int in_slot, int H, int 
     } else if (kind == DRN_TRUNK_MAXPOOL) {
       if (in.h < 2 || in.w < 2 || (o.stride != 1 && o.stride != 2)) return DRN_ERR_ARG;
       out = SlotGeom{(in.h - 2) / o.stride + 1, (in.w - 2) / o.stride + 1, in.c, in.es, true};
+    } else if (kind == DRN_TRUNK_MAXPOOL3X3) {  // F.max_pool2d(3, 2, 1): the standard stem's pool (drn_maxpool3x3s2_nhwc)
+      if (o.ksize != 3 || o.stride != 2 || o.pad != 1) return DRN_ERR_ARG;
+      out = SlotGeom{(in.h + 2 * o.pad - o.ksize) / o.stride + 1, (in.w + 2 * o.pad - o.ksize) / o.stride + 1, in.c, in.es, true};
     } else {
       return DRN_ERR_ARG;
     }
@@ -91,6 +94,18 @@ int drn_trunk_forward(const DrnTrunkOp* ops, int n_ops, int n_slots, int in_slot
     if (!slots[o.src] || !slots[o.dst] || (o.res >= 0 && !slots[o.res])) return DRN_ERR_ARG;
     const int idx = (int)(&o - ops);
     if (idx == fused_tail || idx == fused_pool) return DRN_OK;
+    if ((o.kind & DRN_TRUNK_FUSE_STEM) && idx + 1 < n_ops && (o.kind & DRN_TRUNK_KIND_MASK) == DRN_TRUNK_CONV) {
+      // the standard stem: 7x7 / stride-2 conv + ReLU whose output only the next op - the 3x3 / stride-2 / pad-1 max pool - reads:
+      // one launch (drn_stem7x7_pool_nhwc; bit-identical, the half-resolution map is never written) inside that kernel's class
+      const DrnTrunkOp& pl = ops[idx + 1];
+      if ((pl.kind & DRN_TRUNK_KIND_MASK) == DRN_TRUNK_MAXPOOL3X3 && pl.src == o.dst && pl.dst >= 0 && pl.dst < n_slots &&
+          slots[pl.dst] && o.res < 0 && o.ksize == 7 && o.stride == 2 && o.pad == 3 && o.dil == 1 && o.out_dtype == o.dtype) {
+        const int rc = drn_stem7x7_pool_nhwc(slots[o.src], o.w, o.scale, o.bias, slots[pl.dst], Nb, in.h, in.w, o.cin, o.cout,
+                                             o.ldw, o.relu, o.dtype, stream);
+        if (rc == DRN_OK) { fused_pool = idx + 1; return DRN_OK; }
+        if (rc != DRN_ERR_UNSUPPORTED) return rc;
+      }
+    }
     if ((o.kind & DRN_TRUNK_FUSE_NEXT) && idx + 1 < n_ops) {
       // 3x3 (64 -> 64) whose output only the next op - a 1x1 to 256 channels - reads: one launch on large maps
       // (drn_conv3x3_pw_nhwc; bit-identical to the two), the two launches wherever that kernel does not apply
@@ -132,6 +147,8 @@ int drn_trunk_forward(const DrnTrunkOp* ops, int n_ops, int n_slots, int in_slot
       return drn_conv2d_nhwc_q(slots[o.src], o.w, slots[o.dst], o.scale, o.bias, o.res >= 0 ? slots[o.res] : nullptr, Nb, in.h,
                                in.w, o.cin, o.cout, o.ksize, o.ksize, o.stride, o.pad, o.dil, o.ldw, o.cout, o.cout, o.relu,
                                o.dtype, o.out_dtype, o.res >= 0 ? o.res_dtype : o.out_dtype, o.res_mult, stream);
+    if ((o.kind & DRN_TRUNK_KIND_MASK) == DRN_TRUNK_MAXPOOL3X3)
+      return drn_maxpool3x3s2_nhwc(slots[o.src], slots[o.dst], Nb, in.h, in.w, in.c, o.dtype, stream);
     return drn_maxpool2x2_nhwc(slots[o.src], slots[o.dst], Nb, in.h, in.w, in.c, o.stride, o.dtype, stream);
   });
 }

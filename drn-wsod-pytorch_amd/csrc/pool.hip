@@ -145,6 +145,80 @@ __global__ void maxpool2x2_kernel(const char* __restrict__ x, char* __restrict__
   }
 }
 
+// F.max_pool2d(x, kernel_size=3, stride=2, padding=1) of the standard ResNet stem (detectron2/modeling/backbone/resnet.py:358).
+// One thread = one 16-B channel vector of one output pixel; the window is clipped to the map, which is what -inf padding
+// amounts to (its centre tap (2 ho, 2 wo) always lies inside, so no window is empty).
+template <int DT>
+__global__ void maxpool3x3s2_kernel(const char* __restrict__ x, char* __restrict__ y, int Nb, int H, int W, int C, int Ho,
+                                    int Wo) {
+  constexpr int ES = EsOf<DT>::value;
+  constexpr int V = 16 / ES;
+  const int cv = C / V;
+  const long total = (long)Nb * Ho * Wo * cv;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (i % cv) * V;
+    long t = i / cv;
+    const int wo = t % Wo; t /= Wo;
+    const int ho = t % Ho;
+    const int n = t / Ho;
+    const int h0 = max(2 * ho - 1, 0), h1 = min(2 * ho + 1, H - 1);
+    const int w0 = max(2 * wo - 1, 0), w1 = min(2 * wo + 1, W - 1);
+    char* dst = y + (((long)(n * Ho + ho) * Wo + wo) * C + c) * ES;
+    if constexpr (DT == DRN_F32) {
+      f32x4_t o = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      for (int h = h0; h <= h1; ++h)
+        for (int w = w0; w <= w1; ++w) {
+          const f32x4_t a = *(const f32x4_t*)(x + (((long)(n * H + h) * W + w) * C + c) * ES);
+          o.x = fmaxf(o.x, a.x);
+          o.y = fmaxf(o.y, a.y);
+          o.z = fmaxf(o.z, a.z);
+          o.w = fmaxf(o.w, a.w);
+        }
+      *(f32x4_t*)dst = o;
+    } else if constexpr (DT == DRN_BF16) {
+      // two packed bf16 per dword; bf16 -> f32 is a shift, the max of bf16 values is again bf16
+      float lo[4], hi[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) lo[k] = hi[k] = -INFINITY;
+      for (int h = h0; h <= h1; ++h)
+        for (int w = w0; w <= w1; ++w) {
+          const u32x4_t a = *(const u32x4_t*)(x + (((long)(n * H + h) * W + w) * C + c) * ES);
+          const unsigned u[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            lo[k] = fmaxf(lo[k], __builtin_bit_cast(float, u[k] << 16));
+            hi[k] = fmaxf(hi[k], __builtin_bit_cast(float, u[k] & 0xffff0000u));
+          }
+        }
+      unsigned r[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        r[k] = (__builtin_bit_cast(unsigned, lo[k]) >> 16) | (__builtin_bit_cast(unsigned, hi[k]) & 0xffff0000u);
+      u32x4_t o;
+      o.x = r[0]; o.y = r[1]; o.z = r[2]; o.w = r[3];
+      *(u32x4_t*)dst = o;
+    } else {
+      // the quantised trunk pools post-ReLU tensors only: non-negative e4m3 values order like their bytes
+      unsigned r[4] = {0u, 0u, 0u, 0u};
+      for (int h = h0; h <= h1; ++h)
+        for (int w = w0; w <= w1; ++w) {
+          const u32x4_t a = *(const u32x4_t*)(x + (((long)(n * H + h) * W + w) * C + c) * ES);
+          const unsigned u[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            unsigned o = 0;
+#pragma unroll
+            for (int s = 0; s < 32; s += 8) o |= max((r[k] >> s) & 0xffu, (u[k] >> s) & 0xffu) << s;
+            r[k] = o;
+          }
+        }
+      u32x4_t o;
+      o.x = r[0]; o.y = r[1]; o.z = r[2]; o.w = r[3];
+      *(u32x4_t*)dst = o;
+    }
+  }
+}
+
 struct RoiParams {
   const char* feat;  // NHWC
   const float* rois;  // [M][5]
@@ -2181,6 +2255,27 @@ int drn_maxpool2x2_nhwc(const void* x, void* y, int Nb, int H, int W, int C, int
                        (char*)y, Nb, H, W, C, Ho, Wo, stride);
   else
     return DRN_ERR_ARG;
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+int drn_maxpool3x3s2_nhwc(const void* x, void* y, int Nb, int H, int W, int C, int dtype, void* stream) {
+  if (!x || !y || Nb < 1 || H < 1 || W < 1 || C < 1) return DRN_ERR_ARG;
+  if (dtype != DRN_BF16 && dtype != DRN_F32 && dtype != DRN_FP8) return DRN_ERR_ARG;
+  const int es = drn_esize(dtype);
+  if ((C * es) % 16) return DRN_ERR_ARG;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;  // (H + 2 * 1 - 3) / 2 + 1
+  const long total = (long)Nb * Ho * Wo * (C * es / 16);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DRN_BF16)
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<DRN_BF16>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const char*)x,
+                       (char*)y, Nb, H, W, C, Ho, Wo);
+  else if (dtype == DRN_F32)
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<DRN_F32>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const char*)x,
+                       (char*)y, Nb, H, W, C, Ho, Wo);
+  else
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<DRN_FP8>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const char*)x,
+                       (char*)y, Nb, H, W, C, Ho, Wo);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

@@ -21,7 +21,8 @@ from ..layers import _DX_ONLY, dx_only, CNNBlockBase, Conv2d, FrozenBatchNorm2d,
 from ..registry import BACKBONE_REGISTRY
 
 __all__ = ["Backbone", "BasicStem", "BasicBlock", "BottleneckBlock", "ResNet", "PlainBlock", "VGG16",
-           "build_ws_resnet_backbone", "build_vgg_backbone", "build_backbone"]
+           "StdBasicStem", "StdBottleneckBlock", "build_ws_resnet_backbone", "build_resnet_backbone", "build_vgg_backbone",
+           "build_backbone"]
 
 
 def _as(t, dtype):
@@ -54,10 +55,15 @@ class _PlanBuilder:
 
     # fused groups (3x3 + 1x1 tail, max pool in the conv's epilogue) flagged in the plans; DRN_FUSE_TAILS=0: A/B runs
     fuse_tails = os.environ.get("DRN_FUSE_TAILS", "1") != "0"
+    # the standard stem's conv 7x7 + max pool 3x3 pair flagged as one launch (DRN_TRUNK_FUSE_STEM); DRN_FUSE_STEM=0: A/B runs
+    fuse_stem = os.environ.get("DRN_FUSE_STEM", "1") != "0"
 
-    def __init__(self, in_dtype, in_channels):
+    def __init__(self, in_dtype, in_channels, geometry_only=False):
         self.vals = [dict(dtype=in_dtype, scale=1.0, c=in_channels)]  # value 0: the (normalised, padded) image
         self.ops, self.keep, self.srcs = [], [], []
+        # geometry_only: the ops carry no device pointers - such a plan answers drn_trunk_shapes (host-only) for a model that
+        # sits on the CPU and can never be enqueued (Backbone.plan_shapes)
+        self._ptr = (lambda t: None) if geometry_only else C.ptr
 
     def conv(self, m, src, res=None, relu=False):
         v = self.vals[src]
@@ -73,8 +79,8 @@ class _PlanBuilder:
             raise DrnError("trunk plan: %d stored input channels, the conv expects %d" % (v["c"], m.cin_pad(v["dtype"])))
         self.keep += [w, scale, bias]
         self.srcs += m._source_tensors()
-        self.ops.append(dict(kind=0, src=src, res=-1 if res is None else res, w=C.ptr(w), scale=C.ptr(scale),
-                             bias=C.ptr(bias), cin=v["c"], cout=m.out_channels, ksize=m.kernel_size[0],
+        self.ops.append(dict(kind=0, src=src, res=-1 if res is None else res, w=self._ptr(w), scale=self._ptr(scale),
+                             bias=self._ptr(bias), cin=v["c"], cout=m.out_channels, ksize=m.kernel_size[0],
                              stride=m.stride[0], pad=m.padding[0], dil=m.dilation[0], relu=int(bool(relu)),
                              ldw=w.stride(0), dtype=C.dt(v["dtype"]), out_dtype=C.dt(out_dtype),
                              res_dtype=C.dt(self.vals[res]["dtype"]) if res is not None else C.dt(out_dtype),
@@ -87,6 +93,15 @@ class _PlanBuilder:
         self.ops.append(dict(kind=1, src=src, res=-1, w=None, scale=None, bias=None, cin=v["c"], cout=v["c"], ksize=2,
                              stride=int(stride), pad=0, dil=1, relu=0, ldw=0, dtype=C.dt(v["dtype"]),
                              out_dtype=C.dt(v["dtype"]), res_dtype=C.dt(v["dtype"]), res_mult=1.0))
+        self.vals.append(dict(v))
+        return len(self.vals) - 1
+
+    def pool3(self, src):
+        """F.max_pool2d(3, 2, 1) of the standard stem (DRN_TRUNK_MAXPOOL3X3)"""
+        v = self.vals[src]
+        self.ops.append(dict(kind=2, src=src, res=-1, w=None, scale=None, bias=None, cin=v["c"], cout=v["c"], ksize=3,
+                             stride=2, pad=1, dil=1, relu=0, ldw=0, dtype=C.dt(v["dtype"]), out_dtype=C.dt(v["dtype"]),
+                             res_dtype=C.dt(v["dtype"]), res_mult=1.0))
         self.vals.append(dict(v))
         return len(self.vals) - 1
 
@@ -127,6 +142,14 @@ class _PlanBuilder:
             tail = i > 0 and (self.ops[i - 1]["kind"] & 0x100) != 0
             if stem3 or tail:
                 o["kind"] |= 0x200
+        # the standard ResNet stem (resnet.py:355-359): conv 7x7 / 2 / 3 (+ ReLU, bf16, 8 stored -> 64 channels) whose output only the
+        # next op reads, the 3x3 / 2 / 1 max pool - flagged, the executor runs the pair as one drn_stem7x7_pool_nhwc launch
+        for i in range(len(self.ops) - 1 if getattr(self, "fuse_stem", True) else 0):
+            o, n = self.ops[i], self.ops[i + 1]
+            if (o["kind"] == 0 and n["kind"] == 2 and n["src"] == i + 1 and readers.get(i + 1) == 1 and (i + 1) not in pinned
+                    and o["ksize"] == 7 and o["stride"] == 2 and o["pad"] == 3 and o["dil"] == 1 and o["res"] < 0 and o["relu"]
+                    and o["cin"] == 8 and o["cout"] == 64 and o["dtype"] == bf and o["out_dtype"] == bf):
+                o["kind"] |= 0x400
         # a fused group is ONE launch: everything its ops read must stay alive until its LAST op has its output slot (the
         # two-launch form may reuse conv2's input slot for conv3's output, or the shortcut's slot for the pooled map - the
         # one-launch form reads those while it writes)
@@ -209,6 +232,20 @@ class Backbone(nn.Module):
         p["ptrs"], p["scratch"] = (ctypes.c_void_p * p["n_slots"])(), {}
         plans[(dtype, cin)] = p
         return p
+
+    def plan_shapes(self, n, h, w, dtype=None):
+        """Host-only view of the launch plan for an [n, 3, h, w] input: {"ops": DrnTrunkOp array, "n_ops", "n_slots",
+        "features": {name: (h, w, c)}, "slot_bytes": [...], "slot_hwc": [(h, w, c), ...]} as drn_trunk_shapes reports them.
+        Launches nothing and needs no GPU (the ops of this plan carry no device pointers)."""
+        dtype = dtype or compute_dtype()
+        cin = 8 if dtype == torch.bfloat16 else 4
+        b = _PlanBuilder(dtype, cin, geometry_only=True)
+        p = b.finish(self._plan_emit(b, 0))
+        nbytes, hwc = (ctypes.c_long * p["n_slots"])(), (ctypes.c_int * (3 * p["n_slots"]))()
+        C.call("drn_trunk_shapes", p["ops"], p["n_ops"], p["n_slots"], 0, n, h, w, cin, C.dt(dtype), nbytes, hwc)
+        geo = [tuple(hwc[3 * s_: 3 * s_ + 3]) for s_ in range(p["n_slots"])]
+        return dict(ops=p["ops"], n_ops=p["n_ops"], n_slots=p["n_slots"], slot_bytes=list(nbytes), slot_hwc=geo,
+                    features={name: geo[slot] for name, (slot, _, _) in p["outputs"].items()})
 
     def _run_plan(self, x_nhwc):
         """x_nhwc: [N, H, W, Cpad] contiguous in the compute dtype -> {feature name: NHWC tensor}"""
@@ -604,6 +641,130 @@ class ResNet(Backbone):
             blocks.append(block_class(in_channels=in_channels, out_channels=out_channels, **curr))
             in_channels = out_channels
         return blocks
+
+
+# ---- the standard ImageNet ResNet (detectron2/modeling/backbone/resnet.py), the trunk DRN-WSOD replaces ------------------
+# wsddn_R_50_DC5_1x.yaml / wsddn_R_101_DC5_1x.yaml run the same WSDDN heads on it, frozen (FREEZE_AT 5).  Same attribute
+# names as the reference's BasicStem / BottleneckBlock => same state_dict keys (backbone.stem.conv1.norm.weight,
+# backbone.res3.0.shortcut.weight, ...); the classes carry a Std prefix here because the WS classes own the plain names
+# (aliases.py serves them as detectron2.modeling.backbone.resnet.BasicStem / BottleneckBlock).
+
+def _pool3(x):
+    y = ops.maxpool3x3s2_nhwc(x)
+    if hasattr(x, "_drn_scale"):
+        y._drn_scale = x._drn_scale
+    return y
+
+
+class StdBasicStem(CNNBlockBase):
+    """resnet.py:331-359: conv 7x7 / stride 2 / pad 3 -> FrozenBN -> ReLU -> max_pool2d(3, 2, 1)."""
+
+    def __init__(self, in_channels=3, out_channels=64, norm="BN"):
+        super().__init__(in_channels, out_channels, 4)
+        self.in_channels = in_channels
+        self.conv1 = Conv2d(in_channels, out_channels, kernel_size=7, stride=2, padding=3, bias=False,
+                            norm=get_norm(norm, out_channels))
+        c2_msra_fill(self.conv1)
+
+    def forward_nhwc(self, x, save=False):
+        if save:
+            raise DrnError("the standard ResNet trunk runs frozen: MODEL.BACKBONE.FREEZE_AT must be 5 (no backward "
+                           "through its strided blocks is built)")
+        return _pool3(self.conv1.run_nhwc(x, relu=True))
+
+    def plan(self, b, x):
+        return b.pool3(b.conv(self.conv1, x, relu=True))
+
+    def forward(self, x):
+        return from_nhwc(self.forward_nhwc(to_nhwc(x, compute_dtype(), 8 if compute_dtype() == torch.bfloat16 else 4)))
+
+
+class StdBottleneckBlock(CNNBlockBase):
+    """resnet.py:101-211: 1x1 -> 3x3 -> 1x1 with a projection shortcut where the shape changes; the block's stride sits in
+    conv1 (STRIDE_IN_1X1, the MSRA weights) or in conv2, and in the shortcut; no pooling."""
+
+    def __init__(self, in_channels, out_channels, *, bottleneck_channels, stride=1, num_groups=1, norm="BN",
+                 stride_in_1x1=False, dilation=1):
+        super().__init__(in_channels, out_channels, stride)
+        if num_groups != 1:
+            raise DrnError("MODEL.RESNETS.NUM_GROUPS = %d: grouped convolutions are not built" % num_groups)
+        if in_channels != out_channels:
+            self.shortcut = Conv2d(in_channels, out_channels, kernel_size=1, stride=stride, bias=False,
+                                   norm=get_norm(norm, out_channels))
+        else:
+            self.shortcut = None
+        stride_1x1, stride_3x3 = (stride, 1) if stride_in_1x1 else (1, stride)
+        self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, stride=stride_1x1, bias=False,
+                            norm=get_norm(norm, bottleneck_channels))
+        self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, kernel_size=3, stride=stride_3x3, padding=1 * dilation,
+                            bias=False, groups=num_groups, dilation=dilation, norm=get_norm(norm, bottleneck_channels))
+        self.conv3 = Conv2d(bottleneck_channels, out_channels, kernel_size=1, bias=False, norm=get_norm(norm, out_channels))
+        for layer in (self.conv1, self.conv2, self.conv3, self.shortcut):
+            if layer is not None:
+                c2_msra_fill(layer)
+
+    def forward_nhwc(self, x, save=False):
+        if save:
+            raise DrnError("the standard ResNet trunk runs frozen: MODEL.BACKBONE.FREEZE_AT must be 5 (no backward "
+                           "through its strided blocks is built)")
+        o1 = self.conv1.run_nhwc(x, relu=True)
+        o2 = self.conv2.run_nhwc(o1, relu=True)
+        sc = self.shortcut.run_nhwc(x) if self.shortcut is not None else x
+        return self.conv3.run_nhwc(o2, residual=sc, relu=True)
+
+    def plan(self, b, x):
+        sc = b.conv(self.shortcut, x) if self.shortcut is not None else x
+        o2 = b.conv(self.conv2, b.conv(self.conv1, x, relu=True), relu=True)
+        return b.conv(self.conv3, o2, res=sc, relu=True)
+
+    def forward(self, x):
+        return from_nhwc(self.forward_nhwc(to_nhwc(x)))
+
+
+@BACKBONE_REGISTRY.register()
+def build_resnet_backbone(cfg, input_shape):
+    """resnet.py:560-643.  What no shipped recipe asks of this trunk is refused by config key."""
+    norm = cfg.MODEL.RESNETS.NORM
+    freeze_at = cfg.MODEL.BACKBONE.FREEZE_AT
+    out_features = cfg.MODEL.RESNETS.OUT_FEATURES
+    depth = cfg.MODEL.RESNETS.DEPTH
+    num_groups = cfg.MODEL.RESNETS.NUM_GROUPS
+    bottleneck_channels = num_groups * cfg.MODEL.RESNETS.WIDTH_PER_GROUP
+    in_channels = cfg.MODEL.RESNETS.STEM_OUT_CHANNELS
+    out_channels = cfg.MODEL.RESNETS.RES2_OUT_CHANNELS
+    stride_in_1x1 = cfg.MODEL.RESNETS.STRIDE_IN_1X1
+    res5_dilation = cfg.MODEL.RESNETS.RES5_DILATION
+    if norm != "FrozenBN":
+        raise DrnError("MODEL.RESNETS.NORM = '%s': the standard ResNet trunk is built with FrozenBN only" % norm)
+    if freeze_at < 5:
+        raise DrnError("MODEL.BACKBONE.FREEZE_AT = %d: the standard ResNet trunk (build_resnet_backbone) runs frozen "
+                       "(FREEZE_AT 5, as wsddn_R_50 / wsddn_R_101 set it); no backward through its strided blocks is built"
+                       % freeze_at)
+    if depth not in (50, 101, 152):
+        raise DrnError("MODEL.RESNETS.DEPTH = %d: build_resnet_backbone builds the bottleneck depths 50 / 101 / 152 "
+                       "(BasicBlock trunks, depth 18 / 34, are not built)" % depth)
+    if num_groups != 1:
+        raise DrnError("MODEL.RESNETS.NUM_GROUPS = %d: grouped convolutions are not built" % num_groups)
+    if any(cfg.MODEL.RESNETS.DEFORM_ON_PER_STAGE):
+        raise DrnError("MODEL.RESNETS.DEFORM_ON_PER_STAGE: deformable stages are not built")
+    if res5_dilation not in (1, 2):
+        raise DrnError("MODEL.RESNETS.RES5_DILATION = %s: 1 or 2" % (res5_dilation,))
+    stem = StdBasicStem(in_channels=input_shape.channels, out_channels=in_channels, norm=norm)
+    num_blocks_per_stage = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}[depth]
+    stages = []
+    max_stage_idx = max({"res2": 2, "res3": 3, "res4": 4, "res5": 5}[f] for f in out_features)
+    for idx, stage_idx in enumerate(range(2, max_stage_idx + 1)):
+        dilation = res5_dilation if stage_idx == 5 else 1
+        first_stride = 1 if idx == 0 or (stage_idx == 5 and dilation == 2) else 2
+        n = num_blocks_per_stage[idx]
+        stages.append(ResNet.make_stage(block_class=StdBottleneckBlock, num_blocks=n,
+                                        stride_per_block=[first_stride] + [1] * (n - 1), in_channels=in_channels,
+                                        out_channels=out_channels, norm=norm, bottleneck_channels=bottleneck_channels,
+                                        stride_in_1x1=stride_in_1x1, dilation=dilation, num_groups=num_groups))
+        in_channels = out_channels
+        out_channels *= 2
+        bottleneck_channels *= 2
+    return ResNet(stem, stages, out_features=out_features).freeze(freeze_at)
 
 
 @BACKBONE_REGISTRY.register()

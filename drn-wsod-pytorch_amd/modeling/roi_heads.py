@@ -159,6 +159,54 @@ class DiscriminativeAdaptionNeck(nn.Module):
         raise DrnError("DiscriminativeAdaptionNeck runs inside the fused OICRROIHeads schedule; call the ROI heads")
 
 
+@ROI_BOX_HEAD_REGISTRY.register()
+class FastRCNNConvFCHead(nn.Module):
+    """detectron2/modeling/roi_heads/box_head.py:23-95 as wsddn_R_50_DC5_1x.yaml configures it (NUM_CONV 0, NUM_FC 2):
+    flatten -> fc1 -> ReLU -> fc2 -> ReLU.  The same two-Linear neck as DiscriminativeAdaptionNeck WITHOUT dropout, so it runs
+    on the same head engine, which reads `dropout_p` (0 here) and `dropout_masks`."""
+
+    @configurable
+    def __init__(self, input_shape: ShapeSpec, *, conv_dims: List[int], fc_dims: List[int], conv_norm=""):
+        super().__init__()
+        assert len(conv_dims) + len(fc_dims) > 0
+        if len(conv_dims):
+            raise DrnError("MODEL.ROI_BOX_HEAD.NUM_CONV = %d: conv layers in the box head are not built (no shipped "
+                           "WSL recipe sets them)" % len(conv_dims))
+        if conv_norm:
+            raise DrnError("MODEL.ROI_BOX_HEAD.NORM = '%s': the box head has no conv layers to normalise" % conv_norm)
+        if len(fc_dims) != 2:
+            raise DrnError("MODEL.ROI_BOX_HEAD.NUM_FC = %d: the head engine runs the two-layer neck (fc1, fc2)" % len(fc_dims))
+        self._output_size = (input_shape.channels, input_shape.height, input_shape.width)
+        self.conv_norm_relus = []
+        self.fcs = []
+        for k, fc_dim in enumerate(fc_dims):
+            size = self._output_size if isinstance(self._output_size, int) else int(
+                self._output_size[0] * self._output_size[1] * self._output_size[2])
+            fc = Linear(size, fc_dim)
+            self.add_module("fc{}".format(k + 1), fc)
+            self.fcs.append(fc)
+            self._output_size = fc_dim
+        for layer in self.fcs:  # fvcore.nn.weight_init.c2_xavier_fill
+            torch.nn.init.kaiming_uniform_(layer.weight, a=1)
+            torch.nn.init.constant_(layer.bias, 0)
+        self.dropout_p = 0.0          # box_head.py:95-96: relu only
+        self.dropout_masks = None
+
+    @classmethod
+    def from_config(cls, cfg, input_shape):
+        return {"input_shape": input_shape, "conv_dims": [cfg.MODEL.ROI_BOX_HEAD.CONV_DIM] * cfg.MODEL.ROI_BOX_HEAD.NUM_CONV,
+                "fc_dims": [cfg.MODEL.ROI_BOX_HEAD.FC_DIM] * cfg.MODEL.ROI_BOX_HEAD.NUM_FC,
+                "conv_norm": cfg.MODEL.ROI_BOX_HEAD.NORM}
+
+    @property
+    def output_shape(self):
+        o = self._output_size
+        return ShapeSpec(channels=o) if isinstance(o, int) else ShapeSpec(channels=o[0], height=o[1], width=o[2])
+
+    def forward(self, x):
+        raise DrnError("FastRCNNConvFCHead runs inside the fused ROI-heads schedule; call the ROI heads")
+
+
 def build_box_head(cfg, input_shape):
     return ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, input_shape)
 

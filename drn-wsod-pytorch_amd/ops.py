@@ -262,6 +262,29 @@ def maxpool2x2_nhwc(x, stride):
     return y
 
 
+def maxpool3x3s2_nhwc(x):
+    """F.max_pool2d(x, kernel_size=3, stride=2, padding=1) on NHWC (the standard ResNet stem's pool)"""
+    n, h, w, c = x.shape
+    y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=x.dtype, device=x.device)
+    C.call("drn_maxpool3x3s2_nhwc", C.ptr(x), C.ptr(y), n, h, w, c, C.dt(x.dtype), C.stream())
+    return y
+
+
+def stem7x7_pool_nhwc(x, w_packed, cout, scale, bias, relu=True):
+    """conv 7x7 / 2 / 3 + affine + ReLU + max_pool2d(3, 2, 1) as one launch (drn_stem7x7_pool_nhwc) -> the pooled map, or
+    None where the shape is outside the kernel's class (the caller then runs conv2d_nhwc + maxpool3x3s2_nhwc)"""
+    n, h, w, cin = x.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    y = torch.empty((n, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1, cout), dtype=x.dtype, device=x.device)
+    rc = C.lib().drn_stem7x7_pool_nhwc(C.ptr(x), C.ptr(w_packed), C.ptr(scale), C.ptr(bias), C.ptr(y), n, h, w, cin, cout,
+                                       w_packed.stride(0), int(bool(relu)), C.dt(x.dtype), C.stream())
+    if rc == -3:
+        return None
+    if rc != 0:
+        raise C.DrnError("drn_stem7x7_pool_nhwc failed (%d)" % rc)
+    return y
+
+
 def preprocess_nhwc(images, mean, std, dtype, cpad):
     """images: list of [3,H,W] f32 device tensors -> ([N,Hmax,Wmax,cpad] NHWC, sizes)."""
     hmax = max(int(i.shape[1]) for i in images)

@@ -90,6 +90,23 @@ int drn_conv3x3_pw_nhwc(const void* x, const void* w2, const float* scale2, cons
  * (post-ReLU) values only - they order like their bytes. */
 int drn_maxpool2x2_nhwc(const void* x, void* y, int Nb, int H, int W, int C, int stride, int dtype, void* stream);
 
+/* F.max_pool2d(x, kernel_size=3, stride=2, padding=1), the pool of the standard ResNet stem
+ * (detectron2/modeling/backbone/resnet.py:355-359).  x [Nb][H][W][C] -> y [Nb][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C]
+ * (= (H + 2 - 3) / 2 + 1); padding never wins (it counts as -inf), any H, W >= 1; C * esize a multiple of 16 bytes.
+ * DRN_F32 / DRN_BF16; DRN_FP8: non-negative (post-ReLU) values only, as for drn_maxpool2x2_nhwc. */
+int drn_maxpool3x3s2_nhwc(const void* x, void* y, int Nb, int H, int W, int C, int dtype, void* stream);
+
+/* The standard ResNet stem as ONE launch (BasicStem.forward, detectron2/modeling/backbone/resnet.py:355-359):
+ * y = max_pool2d(relu(conv7x7(x, stride 2, pad 3) * scale + bias), 3, 2, 1), bf16.  x [Nb][H][W][8] (3 channels stored as
+ * 8), w [64][ldw] packed as for drn_conv2d_nhwc (k = (kh * 7 + kw) * 8 + ci, zero padded), y the POOLED map
+ * [Nb][(Ho - 1) / 2 + 1][(Wo - 1) / 2 + 1][64] with Ho = (H - 1) / 2 + 1; the half-resolution conv map is never written.
+ * The conv output is rounded to bf16 exactly as drn_conv2d_nhwc stores it and the k order is that kernel's: bit for bit
+ * the result of drn_conv2d_nhwc + drn_maxpool3x3s2_nhwc, for any H, W >= 1.
+ * Class: dtype DRN_BF16, Cin (stored) 8, Cout 64, relu != 0, 16-byte aligned pointers; DRN_ERR_UNSUPPORTED otherwise
+ * (callers then run the two launches). */
+int drn_stem7x7_pool_nhwc(const void* x, const void* w, const float* scale, const float* bias, void* y, int Nb, int H, int W,
+                          int Cin, int Cout, long ldw, int relu, int dtype, void* stream);
+
 /* ---- backward of the conv trunk (MODEL.BACKBONE.FREEZE_AT < 5; torch.autograd of F.conv2d / max_pool2d) ---- *
  * conv dgrad runs drn_conv2d_nhwc on the flipped/transposed packed weights (every trained conv has stride 1,
  * resnet_ws.py:148-150), the FrozenBN-affine/ReLU backward runs drn_bias_act_bwd, and the weight gradient is
@@ -501,20 +518,26 @@ int drn_csc_loss(const float* logits, long ld, int c_cls, int c_det, int K, int 
  * `VGG16.forward` / `PlainBlock.forward` (vgg.py:213-231, :104-122) when nothing has to be kept for a backward pass.
  * A plan is an array of ops over numbered activation SLOTS (buffers the caller owns; an op never writes its own input
  * or residual slot).  Geometry per op follows from the input size; every op runs through drn_conv2d_nhwc_q /
- * drn_maxpool2x2_nhwc, so the kernels, their selection and the results are those of the per-layer calls. */
+ * drn_maxpool2x2_nhwc, so the kernels, their selection and the results are those of the per-layer calls.
+ * DRN_TRUNK_MAXPOOL is nn.MaxPool2d(2, stride): it reads `stride` alone, as it always did (ksize / pad are ignored).
+ * DRN_TRUNK_MAXPOOL3X3 is F.max_pool2d(3, 2, 1) = drn_maxpool3x3s2_nhwc, the standard ResNet stem's pool
+ * (detectron2/modeling/backbone/resnet.py:358): ksize = 3, stride = 2, pad = 1 must be set, anything else is an
+ * argument error; output (H + 2 - 3) / 2 + 1 rows. */
 #define DRN_TRUNK_CONV 0
 #define DRN_TRUNK_MAXPOOL 1
+#define DRN_TRUNK_MAXPOOL3X3 2
 #define DRN_TRUNK_MAX_SLOTS 16
 #define DRN_TRUNK_KIND_MASK 0xff
 #define DRN_TRUNK_FUSE_POOL 0x200 /* flag on a conv op: its output is read by the NEXT op alone, a 2x2 / stride-2 max pool - may run inside the conv's launch (drn_conv3x3_pw_nhwc with pool = 1; with DRN_TRUNK_FUSE_NEXT on the op before it: three ops, one launch) */
+#define DRN_TRUNK_FUSE_STEM 0x400 /* flag on a 7x7 / stride-2 / pad-3 conv op (8 stored -> 64 channels, ReLU): its output is read by the NEXT op alone, a DRN_TRUNK_MAXPOOL3X3 - the executor may run the pair as one drn_stem7x7_pool_nhwc launch (the conv's dst slot is then not written; bit-identical), and runs the two launches where that entry point answers DRN_ERR_UNSUPPORTED */
 #define DRN_TRUNK_FUSE_NEXT 0x100 /* flag on a 3x3 / 64 -> 64 conv op: its output is read by the NEXT op alone, a 1x1 conv to 256 channels - the executor may run the pair as one drn_conv3x3_pw_nhwc launch (the dst slot is then not written) */
 typedef struct DrnTrunkOp {
-  int kind;           /* DRN_TRUNK_CONV | DRN_TRUNK_MAXPOOL, optionally | DRN_TRUNK_FUSE_NEXT */
+  int kind;           /* DRN_TRUNK_CONV | DRN_TRUNK_MAXPOOL | DRN_TRUNK_MAXPOOL3X3, optionally | DRN_TRUNK_FUSE_NEXT */
   int src, dst, res;  /* slot indices; res = -1: no residual (conv only) */
   const void* w;      /* conv: packed weights [cout][ldw] as for drn_conv2d_nhwc_q */
   const float* scale; /* per-cout affine (folded FrozenBN / quantisation scales) or NULL */
   const float* bias;
-  int cin, cout, ksize, stride, pad, dil, relu; /* cin = stored channels of the input slot; pool: stride only */
+  int cin, cout, ksize, stride, pad, dil, relu; /* cin = stored channels of the input slot; DRN_TRUNK_MAXPOOL: stride only; DRN_TRUNK_MAXPOOL3X3: ksize 3, stride 2, pad 1 */
   long ldw;
   int dtype, out_dtype, res_dtype; /* element types of x / w, of y, of the residual (pool: dtype) */
   float res_mult;
