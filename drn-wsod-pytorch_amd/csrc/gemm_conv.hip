@@ -46,6 +46,10 @@ struct GemmParams {
   // TN operand (drn_gemm_tn): B is given as Bt [kb_rows][ldb] row-major - the contraction index is the ROW index - and the
   // 256x256 ping-pong kernels read it through transposing LDS reads (ds_read_b64_tr_b16); rows >= kb_rows read as zeros
   int kb_rows;
+  // ACC (drn_gemm_tn_acc_sgd): fp32 [M][sgd_acc_ld] gradient accumulator of the window's earlier micro-steps, added to the
+  // fp32 accumulators in front of the bf16 rounding; read only
+  const float* sgd_acc;
+  long sgd_acc_ld;
 };
 
 using drn_conv::ConvParams;
@@ -904,7 +908,13 @@ struct GemmWork { int bm, bn, s0, s1, split; __amdgpu_buffer_rsrc_t ra, rb; };  
 // the fc7 weight gradient (128 tiles: half the CUs in one round) and the fc7 dX (64 tiles x 4 K-splits of half the
 // length), 46 + 41 us one after the other.  (Two concurrent launches on a forked stream do the same on paper and cost
 // 250 us in the captured step: the graph executor starts the branch late.)
-template <int DT, int PP = 0, bool TN = false, bool PAIR = false, bool SGDP = false>
+// ACC (with SGDP; drn_gemm_tn_acc_sgd): the closing micro-step of a gradient-accumulation window - the tile's fp32 accumulators
+// take the matching run of the fp32 gradient accumulator (p.sgd_acc) in the MFMA layout, where a lane owns 4 consecutive columns
+// per register quad and a wave reads whole 128-byte lines of 32 rows, right in front of the bf16 rounding: one fp32 add, one
+// rounding, the sum drn_gemm_tn (fp32 C, accumulate) + drn_cast2d would give.  The loads are plain epilogue loads behind the next
+// tile's first slab (the compiler counts its own wait; the fragment registers are dead here), so SgdPipe and its vmcnt ladder
+// are untouched.
+template <int DT, int PP = 0, bool TN = false, bool PAIR = false, bool SGDP = false, bool ACC = false>
 __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p_in, GemmParams p2_in, int pair_wg0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const bool second = PAIR && (int)(blockIdx.x >> 3) >= pair_wg0;
@@ -1088,6 +1098,25 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p_in, GemmP
       int lane_e = lane, tid_e = tid;
       asm volatile("" : "+v"(lane_e), "+v"(tid_e));
       if (!more) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+      if constexpr (ACC) {
+        static_assert(TN && SGDP, "the accumulating epilogue belongs to the fused TN dW + SGD launch (whole tiles)");
+        const float* ga = p.sgd_acc + (long)(bm + wm * 128 + (lane_e & 31)) * p.sgd_acc_ld + bn + wn * 32 + 4 * (lane_e >> 5);
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          const float* gi = ga + (long)(i * 32) * p.sgd_acc_ld;
+          f32x4_t o[NJ][4];
+#pragma unroll
+          for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) o[jj][qq] = __builtin_nontemporal_load((const f32x4_t*)(gi + jj * 128 + 8 * qq));
+#pragma unroll
+          for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[i][jj][4 * qq + e] = acc[i][jj][4 * qq + e] + o[jj][qq][e];
+        }
+      }
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         if (wm == half) {
@@ -2030,6 +2059,15 @@ static int launch_gemm256p_tn_sgdp(const GemmParams& p, int nwg, hipStream_t st)
   return DRN_OK;
 }
 
+static int launch_gemm256p_tn_acc_sgdp(const GemmParams& p, int nwg, hipStream_t st) {
+  constexpr int smem = 2 * 512 * 128;
+  auto k = gemm_nt256p_kernel<DRN_BF16, 1, true, false, true, true>;
+  if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
+  hipLaunchKernelGGL(k, dim3(nwg), dim3(512), smem, st, p, p, 0);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
 static int launch_gemm256p_pair(const GemmParams& p0, const GemmParams& p1, int nwg, int wg0, hipStream_t st) {
   constexpr int smem = 2 * 512 * 128;
   auto k = gemm_nt256p_kernel<DRN_BF16, 1, false, true>;
@@ -2208,6 +2246,43 @@ const TuneRow kTuneRows[] = {
 };
 }  // namespace
 
+// shared body of drn_gemm_tn_sgd / drn_gemm_tn_acc_sgd (grad_acc == nullptr: the former, launch and arguments unchanged)
+static int gemm_tn_sgd_entry(const void* A, const void* Bt, void* grad_bucket, const float* grad_acc, long ld_acc, int M, int N,
+                             int K, int kb_rows, long lda, long ldb, long ldc, float* weights, float* momentum_buf, void* shadow,
+                             long ld_w, const void* seg_dev, float momentum, int first_step, float grad_scale, void* stream) {
+  if (!A || !Bt || !grad_bucket || !weights || !momentum_buf || !seg_dev || M <= 0 || N <= 0 || K <= 0 || kb_rows < 0 ||
+      kb_rows > K)
+    return DRN_ERR_ARG;
+  if (lda < K || ldb < N || ldc < N || ld_w < N) return DRN_ERR_ARG;
+  // (alignment is part of the shape class, not an argument error: the caller's unfused pair takes such buffers - ADVICE r4)
+  if ((lda * 2) % 16 != 0 || (ldb * 2) % 16 != 0 ||
+      (((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)grad_bucket | (uintptr_t)weights | (uintptr_t)momentum_buf | (uintptr_t)shadow) & 15))
+    return DRN_ERR_UNSUPPORTED;
+  // shape class of the pipelined update: whole K slabs (one 8-row chunk of the previous tile rides in each; with fewer than 32
+  // slabs - fewer than 2048 proposals - the rest follows the mainloop, exposed), whole tiles, a bf16 shadow, 32-bit byte
+  // offsets, enough tiles for the persistent grid, the ping-pong mainloop
+  if (K < 128 || (K & 63) || (M & 255) || (N & 255) || !shadow || (ldc & 7) || (ld_w & 3) || g_tune.gemm_pingpong != 1 ||
+      (long)M * ld_w * 4 >= 0xFFFFFFF0L || (long)K * ldb * 2 >= 0xFFFFFFF0L)
+    return DRN_ERR_UNSUPPORTED;
+  if (grad_acc && ((ld_acc & 3) || (((uintptr_t)grad_acc) & 15) || (long)M * ld_acc * 4 >= 0xFFFFFFF0L)) return DRN_ERR_UNSUPPORTED;
+  const long tiles = (long)(M / 256) * (N / 256);
+  const int nwg = persistent_grid(tiles);
+  if (!nwg) return DRN_ERR_UNSUPPORTED;
+  GemmParams p{(const char*)A, (const char*)Bt, (float*)grad_bucket, M, N, K, lda, ldb, ldc, K * 2 / 128, 0, 0,
+               weights, momentum_buf, (bf16_t*)shadow, (const SgdSeg*)seg_dev, momentum, grad_scale, first_step};
+  p.sgd_ld = ld_w;
+  p.c_bf16 = g_tune.sgdp_ep4 ? 3 : 1;  // (bit 1: four-at-a-time epilogue reads)
+  p.nsplit = 1;
+  p.gm = gemm256_group_rows(M, N, 1);
+  p.kb_rows = kb_rows;
+  if (grad_acc) {
+    p.sgd_acc = grad_acc;
+    p.sgd_acc_ld = ld_acc;
+    return launch_gemm256p_tn_acc_sgdp(p, nwg, (hipStream_t)stream);
+  }
+  return launch_gemm256p_tn_sgdp(p, nwg, (hipStream_t)stream);
+}
+
 extern "C" {
 
 // tuning/test hook: pin the GEMM tile (0 restores the heuristic). Returns the previous value.
@@ -2376,31 +2451,20 @@ int drn_gemm_nt_pair(const void* A0, const void* B0, void* C0, int M0, int N0, i
 int drn_gemm_tn_sgd(const void* A, const void* Bt, void* grad_bucket, int M, int N, int K, int kb_rows, long lda, long ldb,
                     long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w, const void* seg_dev,
                     float momentum, int first_step, float grad_scale, void* stream) {
-  if (!A || !Bt || !grad_bucket || !weights || !momentum_buf || !seg_dev || M <= 0 || N <= 0 || K <= 0 || kb_rows < 0 ||
-      kb_rows > K)
-    return DRN_ERR_ARG;
-  if (lda < K || ldb < N || ldc < N || ld_w < N) return DRN_ERR_ARG;
-  // (alignment is part of the shape class, not an argument error: the caller's unfused pair takes such buffers - ADVICE r4)
-  if ((lda * 2) % 16 != 0 || (ldb * 2) % 16 != 0 ||
-      (((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)grad_bucket | (uintptr_t)weights | (uintptr_t)momentum_buf | (uintptr_t)shadow) & 15))
-    return DRN_ERR_UNSUPPORTED;
-  // shape class of the pipelined update: whole K slabs (one 8-row chunk of the previous tile rides in each; with fewer than 32
-  // slabs - fewer than 2048 proposals - the rest follows the mainloop, exposed), whole tiles, a bf16 shadow, 32-bit byte
-  // offsets, enough tiles for the persistent grid, the ping-pong mainloop
-  if (K < 128 || (K & 63) || (M & 255) || (N & 255) || !shadow || (ldc & 7) || (ld_w & 3) || g_tune.gemm_pingpong != 1 ||
-      (long)M * ld_w * 4 >= 0xFFFFFFF0L || (long)K * ldb * 2 >= 0xFFFFFFF0L)
-    return DRN_ERR_UNSUPPORTED;
-  const long tiles = (long)(M / 256) * (N / 256);
-  const int nwg = persistent_grid(tiles);
-  if (!nwg) return DRN_ERR_UNSUPPORTED;
-  GemmParams p{(const char*)A, (const char*)Bt, (float*)grad_bucket, M, N, K, lda, ldb, ldc, K * 2 / 128, 0, 0,
-               weights, momentum_buf, (bf16_t*)shadow, (const SgdSeg*)seg_dev, momentum, grad_scale, first_step};
-  p.sgd_ld = ld_w;
-  p.c_bf16 = g_tune.sgdp_ep4 ? 3 : 1;  // (bit 1: four-at-a-time epilogue reads)
-  p.nsplit = 1;
-  p.gm = gemm256_group_rows(M, N, 1);
-  p.kb_rows = kb_rows;
-  return launch_gemm256p_tn_sgdp(p, nwg, (hipStream_t)stream);
+  return gemm_tn_sgd_entry(A, Bt, grad_bucket, nullptr, 0, M, N, K, kb_rows, lda, ldb, ldc, weights, momentum_buf, shadow, ld_w,
+                           seg_dev, momentum, first_step, grad_scale, stream);
+}
+
+// The closing micro-step of a gradient-accumulation window (WSL.ITER_SIZE > 1: projects/WSL/tools/train_net.py:100-113 - every
+// micro-iteration back-propagates loss / N, the optimizer steps once per window) for the fc6 weight (box_head.py:82-91's fc1) as
+// ONE launch: drn_gemm_tn_sgd with G = bf16(grad_acc + A . Bt), the sum formed in fp32 and rounded once.  grad_acc (fp32,
+// [M][ld_acc]) holds the window's earlier micro-steps (drn_gemm_tn, fp32 C, accumulate); it is read, never written.
+int drn_gemm_tn_acc_sgd(const void* A, const void* Bt, const float* grad_acc, void* grad_bucket, int M, int N, int K, int kb_rows,
+                        long lda, long ldb, long ld_acc, long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w,
+                        const void* seg_dev, float momentum, int first_step, float grad_scale, void* stream) {
+  if (!grad_acc || ld_acc < N) return DRN_ERR_ARG;
+  return gemm_tn_sgd_entry(A, Bt, grad_bucket, grad_acc, ld_acc, M, N, K, kb_rows, lda, ldb, ldc, weights, momentum_buf, shadow,
+                           ld_w, seg_dev, momentum, first_step, grad_scale, stream);
 }
 
 // NHWC conv + per-channel affine (folded FrozenBN or bias) + optional residual + optional ReLU; `dtype` is the element

@@ -12,6 +12,7 @@
   Trainer.run_step             projects/WSL/tools/train_net.py:65-117 (ITER_SIZE accumulation, loss dict keys) without
                                the per-iteration host syncs (anomaly check / metric gather are deferred)."""
 import bisect
+import collections
 import math
 
 import numpy as np
@@ -22,6 +23,21 @@ import torch.distributed as dist
 from . import ops
 from ._cabi import DrnError
 from .events import EventStorage
+
+
+class Window(collections.namedtuple("Window", "first closing")):
+    """Position of a micro-iteration inside its gradient-accumulation window (WSL.ITER_SIZE = N > 1): `first` - nothing has been
+    accumulated yet, the gradients are overwritten; `closing` - the optimizer steps behind this backward.  A micro-iteration
+    that is neither is a middle one; the window {0} after start_iter = 0 is both."""
+    __slots__ = ()
+
+
+def window_position(it, iter_size, start_iter=0):
+    """projects/WSL/tools/train_net.py:100-113: the optimizer steps and the gradients are cleared when it % N == 0, so the first
+    window after start_iter = 0 is the single iteration 0 and the later ones are kN+1 .. (k+1)N; a run resumed at `start_iter`
+    starts from cleared gradients whatever its position (zero_grad at iter == start_iter)."""
+    n = int(iter_size)
+    return Window(first=(it == start_iter or (it - 1) % n == 0), closing=(it % n == 0))
 
 
 class FusedSGD:
@@ -115,8 +131,24 @@ class FusedSGD:
         return self._segs_dev, self._nseg
 
     # ---- pipelined mode: the update of a gradient bucket starts as soon as the bucket is final ----------------
-    def enable_pipelined(self, dp=None, slab_rows=None, comm_dtype=None, exchange=None, kshard_wire=None, fused_tn=None):
-        """ITER_SIZE == 1 only.  The explicit backward finishes gradients in a known order: first every small tensor
+    @property
+    def iter_size(self):
+        """WSL.ITER_SIZE the pipelined mode was enabled for (1: no accumulation; also for the plain step(), which the Trainer
+        drives by its own window rule)"""
+        return getattr(self, "_iter_size", 1)
+
+    def set_window(self, win):
+        """iter_size > 1: position (Window) of the micro-iteration whose backward comes next.  The head engine's fc6 tail and this
+        optimizer's hooks issue by it: gradients accumulate in the fp32 arena, buckets are announced and updated on closing
+        micro-iterations only."""
+        if self.iter_size == 1:
+            raise DrnError("set_window(): the pipelined mode was enabled without gradient accumulation (iter_size = 1)")
+        self._window = win
+        self.engine.accum_window = win
+
+    def enable_pipelined(self, dp=None, slab_rows=None, comm_dtype=None, exchange=None, kshard_wire=None, fused_tn=None,
+                         iter_size=1):
+        """The explicit backward finishes gradients in a known order: first every small tensor
         (predictors, fc7, fc6 bias), then fc6.weight in row slabs.  In pipelined mode each bucket is (all-reduced when
         N > 1 and then) updated by the SGD kernel on a second stream the moment its dW GEMM is queued, so the HBM-bound
         optimizer pass hides under the MFMA-bound remaining dW GEMMs; `step()` then only joins the streams.
@@ -135,7 +167,23 @@ class FusedSGD:
         next image's trunk / pooling graphs.  Same wire bytes as an all-reduce (2 (N-1)/N of the bucket), identical
         arithmetic (sum over ranks, 1/N in the kernel).  "allreduce" = one all-reduce per bucket and the replicated
         update on every rank (detectron2/engine/defaults.py:279-282's DDP, restated).  The small tensors (38 MB) are
-        all-reduced and updated on every rank in both modes."""
+        all-reduced and updated on every rank in both modes.
+        iter_size = WSL.ITER_SIZE (default 1: every launch as before).  N > 1, single process, frozen trunk: the micro-iterations
+        of a window (window_position; set_window() before every backward) accumulate in the fp32 gradient arena - the small
+        tensors through the accumulate flags of their GEMMs / column sums (always on: the arena's small-tensor region is
+        cleared behind the closing update instead, so ONE captured heads graph serves every position), fc1.weight through
+        drn_gemm_tn / drn_gemm_nt with fp32 C - and only the closing one announces buckets: the small tensors are updated in
+        fp32 from the arena, fc1.weight is rounded to the bf16 bucket ONCE per window, by drn_gemm_tn_acc_sgd together with
+        its update (fused_tn) or by drn_cast2d + drn_sgd_step_block.  In the fp32 parity mode the arena is the gradient."""
+        iter_size = int(iter_size)
+        if iter_size < 1:
+            raise DrnError("iter_size must be >= 1")
+        if iter_size > 1:
+            if self._bb is not None:
+                raise DrnError("WSL.ITER_SIZE > 1 in the pipelined optimizer mode needs a frozen backbone (FREEZE_AT=5)")
+            if (dp is not None and dp.exchange) or exchange == "fc6_kshard":
+                raise DrnError("WSL.ITER_SIZE > 1 in the pipelined optimizer mode is a single-process schedule: no gradient "
+                               "exchange, no K-sharded fc6 (use the plain step())")
         if self._bb is not None:
             raise DrnError("the pipelined optimizer mode assumes a frozen backbone (FREEZE_AT=5); use the plain step()")
         e = self.engine
@@ -200,7 +248,15 @@ class FusedSGD:
         self._slab_ends = slab_rows
         e.fc1_slab_ends = slab_rows
         e.grad_ready_hook = self._on_grad_ready
-        e.defer_colsum = True
+        self._iter_size, self._window = iter_size, None
+        e.accum_window = None
+        e.accum_small = iter_size > 1
+        # (iter_size > 1: the column sums finish inside the backward with their accumulate flag - as the plain step's do - instead
+        # of as partials that the optimizer stream adds up: nothing of a non-closing micro-iteration runs on that stream)
+        e.defer_colsum = iter_size == 1
+        if iter_size > 1:
+            e.ensure(next(self.model.roi_heads.parameters()).device)
+            e.arena_g.zero_()
         self._dp, self._pipelined = dp, True
         self._opt_stream = torch.cuda.Stream() if torch.cuda.is_available() else None
         self._bucket_segs = {}
@@ -234,9 +290,11 @@ class FusedSGD:
                 fused_tn = True
         if fused_tn and not self._exchange_on and e.fc1_grad_bucket is not None:
             self.enable_fused_fc1_tn()
+            if iter_size > 1:
+                e.fc1_fused_tn = self._fused_fc1_tn_acc
 
     def enable_fused_fc1_tn(self):
-        """Single process, ITER_SIZE == 1, bf16 mode, on top of the pipelined mode (round 4): the fc6 weight gradient's main
+        """Single process, bf16 mode, on top of the pipelined mode (round 4; iter_size > 1: _fused_fc1_tn_acc takes its place): the fc6 weight gradient's main
         columns - exact rounds of the persistent kernel - go through drn_gemm_tn_sgd, which applies the optimizer step of
         every tile inside the NEXT tile's mainloop of the same launch (steady HBM traffic under the MFMA work, gradient read
         back from L2, no optimizer launches for fc6 on the other stream).  The trailing columns keep the small-tile launch +
@@ -259,6 +317,21 @@ class FusedSGD:
         view = lambda t: t[o: o + n].view(D1, k1)[:, :n_main]
         return ops.gemm_tn_sgd(dPT, A[:, :n_main], D1, n_main, Mp, M, gw[:, :n_main], view(e.arena_w), view(self._mom),
                                view(e.arena_s), segs, self.momentum, self._steps == 0, 1.0)
+
+    def _fused_fc1_tn_acc(self, dPT, A, D1, n_main, Mp, M, ga, gw):
+        """closing micro-iteration of a window: bucket = bf16(fp32 accumulator + dW) and the update, one launch
+        (drn_gemm_tn_acc_sgd); False -> the caller runs drn_gemm_tn (accumulate) + drn_cast2d + drn_sgd_step_block"""
+        e = self.engine
+        if e.arena_s is None or gw.dtype != torch.bfloat16:
+            return False
+        if self._mom is None:
+            self._mom = torch.zeros_like(e.arena_w)
+        segs, _ = self._bucket_table(("fc1", 0, D1))
+        o, n = e._seg["fc1.weight"]
+        k1 = n // D1
+        view = lambda t: t[o: o + n].view(D1, k1)[:, :n_main]
+        return ops.gemm_tn_acc_sgd(dPT, A[:, :n_main], D1, n_main, Mp, M, ga[:, :n_main], gw[:, :n_main], view(e.arena_w),
+                                   view(self._mom), view(e.arena_s), segs, self.momentum, self._steps == 0, 1.0)
 
     def _fused_fc1_cols(self, dPT, A, D1, k0, k1, Kp, kb, gw):
         """K-sharded fc6: dW of the owned columns k0:k1 and their update as one launch (drn_gemm_tn_sgd; N = 2 / 4: the
@@ -482,6 +555,11 @@ class FusedSGD:
         self._opt_stream.wait_event(ev)
         if what == "small":
             self.small_ready_event = ev  # (graphed.py: recorded behind the step's heads; the graphed step's host-side throttle waits on old ones)
+        if self.iter_size > 1:
+            if self._window is None:
+                raise DrnError("WSL.ITER_SIZE > 1: set_window() must precede every backward (Trainer / GraphedTrainStep do)")
+            if not self._window.closing:
+                return  # the gradients stay in the fp32 arena; nothing for the optimizer stream
         with torch.cuda.stream(self._opt_stream):
             if what == "small":
                 e.flush_colsums()  # bias gradients: second stage of their column sums, off the backward's critical path
@@ -492,6 +570,9 @@ class FusedSGD:
                 self._deferred.append((what, bucket, segs, nseg, evc))
                 return
             self._update(what, bucket, segs, nseg)
+            if what == "small" and self.iter_size > 1:
+                # the next window accumulates from zero (the heads' accumulate flags are always on); step() joins this stream
+                e.arena_g[: e._seg["fc1.weight"][0]].zero_()
 
     def _update(self, what, bucket, segs, nseg):
         e = self.engine
@@ -927,8 +1008,10 @@ class Trainer:
         self.scheduler = scheduler
         self.dp = parallel or DataParallel(model)
         self.iter_size = cfg.WSL.ITER_SIZE
-        if self.iter_size > 1 and getattr(self.optimizer, "_pipelined", False):
-            raise DrnError("the pipelined optimizer updates each bucket during backward: WSL.ITER_SIZE must be 1")
+        if getattr(self.optimizer, "_pipelined", False) and self.optimizer.iter_size != self.iter_size:
+            raise DrnError("the pipelined optimizer updates each bucket during backward: its iter_size (%d) must equal "
+                           "WSL.ITER_SIZE (%d) - enable_pipelined(iter_size=cfg.WSL.ITER_SIZE)"
+                           % (self.optimizer.iter_size, self.iter_size))
         # resume: `start_iter` = checkpoint["iteration"] + 1 (DefaultTrainer.resume_or_load, defaults.py:304-319)
         self.iter = self.start_iter = int(start_iter)
         self.storage = EventStorage(self.start_iter)
@@ -967,6 +1050,8 @@ class Trainer:
             self.optimizer.zero_grad()
         last_micro = self.iter % self.iter_size == 0  # train_net.py:105: the optimizer steps on these iterations
         self.dp.sync_gradients = last_micro           # DDP no_sync() for the other micro-steps of the window
+        if self.iter_size > 1 and getattr(self.optimizer, "_pipelined", False):
+            self.optimizer.set_window(window_position(self.iter, self.iter_size, self.start_iter))
         if not (hasattr(self.model, "backward_losses") and self.model.backward_losses(1.0 / self.iter_size)):
             (sum(loss_dict.values()) / self.iter_size).backward()  # train_net.py:100-107; the line above = the same without autograd
         if last_micro:

@@ -45,7 +45,7 @@ class GraphedTrainStep:
     _needs_frozen_trunk = True
 
     def __init__(self, model, optimizer, example_batch, split_tail=False, lookahead=1, trunk_pairs=False,
-                 eager_fc6=False, stage_ahead=True, ring=True):
+                 eager_fc6=False, stage_ahead=True, ring=True, start_iter=0):
         if getattr(model, "cpg", False):
             raise DrnError("CSCROIHeads decides per step, on the host, which class maps to compute: eager steps only")
         if self._needs_frozen_trunk and any(p.requires_grad for p in model.backbone.parameters()):
@@ -130,6 +130,17 @@ class GraphedTrainStep:
         self._side = torch.cuda.Stream()
         self._primed = False
         self.split_tail = bool(split_tail)
+        # WSL.ITER_SIZE = N > 1 (the pipelined optimizer's iter_size): the captured heads graph back-propagates loss / N with
+        # the small tensors' accumulate flags on, and is the same for every micro-iteration; what differs by window position -
+        # where the fc6 weight gradient goes, whether the optimizer stream gets work, whether the step ends with opt.step() -
+        # is the eager tail, so the tail is always split off.  Micro-iterations count from start_iter (a resumed run).
+        self.iter_size = int(getattr(optimizer, "iter_size", 1))
+        self._iter = int(start_iter)
+        self._start_iter = int(start_iter)
+        if self.iter_size > 1:
+            if not getattr(optimizer, "_pipelined", False):
+                raise DrnError("GraphedTrainStep with WSL.ITER_SIZE > 1 needs FusedSGD.enable_pipelined(iter_size=N)")
+            self.split_tail = True
         if self.engine.kshard is not None and not (self.split_tail and self.eager_fc6 and (lookahead >= 2 or trunk_pairs)):
             raise DrnError("K-sharded fc6 holds collectives in the pooling piece, behind the fc6 GEMM and in the dW tail: "
                            "GraphedTrainStep(split_tail=True, eager_fc6=True, lookahead >= 2 or trunk_pairs)")
@@ -296,10 +307,17 @@ class GraphedTrainStep:
         else:
             self._eager_state = st
         # = sum(losses.values()).backward() without autograd's scalar adds / ones / stack launches
-        self.engine.backward(st, None)   # pipelined SGD buckets fork onto the optimizer stream in here
+        # (ITER_SIZE N > 1: the common upstream gradient is 1 / N, train_net.py:100-107)
+        self.engine.backward(st, None if self.iter_size == 1 else 1.0 / self.iter_size)   # pipelined SGD buckets fork onto the optimizer stream in here
         if not self.split_tail:
             self.opt.step(1.0)           # joins the optimizer stream
         return losses
+
+    def _opt_step(self):
+        """end of the eager tail: join the optimizer stream - on closing micro-iterations only when gradients accumulate (the
+        others gave that stream nothing to do, and optimizer.step() is not called for them)"""
+        if self.iter_size == 1 or self._win.closing:
+            self.opt.step(1.0)
 
     def _pool_body(self, slot=None):
         with torch.no_grad():
@@ -340,7 +358,7 @@ class GraphedTrainStep:
         self._bb_done[sL] = ev
         self._pool_body(s1)
         if self.split_tail:
-            self.opt.step(1.0)
+            self._opt_step()
         self._t = t + 1
         return losses
 
@@ -456,7 +474,7 @@ class GraphedTrainStep:
         main.wait_event(self._pdone[k1])
         self._pair_pool_body(k1, h1)
         if self.split_tail:
-            self.opt.step(1.0)
+            self._opt_step()
         self._t = t + 1
         return losses
 
@@ -521,7 +539,7 @@ class GraphedTrainStep:
         main.wait_event(done)
         self._pool_body() if eager else self.g_pool.replay()
         if self.split_tail:
-            self.opt.step(1.0)  # join the optimizer stream: the exchange ran under the backbone + pooling above
+            self._opt_step()  # join the optimizer stream: the exchange ran under the backbone + pooling above
         return losses
 
     def prime(self, first_batch, next_batch):
@@ -559,6 +577,12 @@ class GraphedTrainStep:
         if self._primed:
             # the captured (or eagerly issued) SGD launches read lr / weight decay from device tables: follow the schedule
             self.opt.refresh_tables()
+        if self.iter_size > 1:
+            from .engine import window_position
+
+            self._win = window_position(self._iter, self.iter_size, self._start_iter)
+            self.opt.set_window(self._win)
+            self._iter += 1
         if self.trunk_pairs:
             if len(upcoming) != 2 * self.G - 2:
                 raise DrnError("GraphedTrainStep(trunk_pairs=%d).step needs batches t+2 .. t+%d" % (self.G, 2 * self.G - 1))

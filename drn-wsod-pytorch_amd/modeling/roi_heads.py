@@ -1085,6 +1085,10 @@ class _HeadEngine:
             self._colidx, self._colidx_key = idx.to(dev), key
         colidx = self._colidx
         acc = self._grads_valid and fc2.weight.grad is not None  # fc1.weight.grad is not materialised in bucket modes
+        if getattr(self, "accum_small", False):
+            # pipelined optimizer with WSL.ITER_SIZE > 1: the small tensors always accumulate (one captured graph serves every
+            # position of the window); the optimizer clears their region of the arena behind the closing update
+            acc = True
         bo, _ = self._seg[self.cols[0][0] + ".bias"]
         wo, _ = self._seg[self.cols[0][0] + ".weight"]
         # bias gradients = column sums of the three pre-activation gradients, in two stages.  With the pipelined optimizer
@@ -1184,6 +1188,41 @@ class _HeadEngine:
         for colpart, nparts, N_, view, acc in getattr(self, "_pending_colsum", ()):
             ops.colsum_reduce(colpart, nparts, N_, view, acc)
 
+    def _fc1_tail_window(self, win, hook, bucket, tn):
+        """fc6 weight gradient of one micro-iteration of an accumulation window with a bf16 bucket.  Columns [0, split) come
+        straight from A (drn_gemm_tn), the trailing ones from the A^T rows the pooling piece wrote (small-tile drn_gemm_nt) -
+        the same per-element arithmetic whatever the split.  Not closing: fp32 C = the fc1.weight region of the gradient arena,
+        overwritten by the window's first micro-iteration, accumulated by the others; no bucket, no optimizer launch.  Closing:
+        the main columns as ONE launch that adds the accumulator, rounds to the bucket once and applies the update
+        (drn_gemm_tn_acc_sgd) when the fused launch is on and takes the shape; otherwise accumulate + drn_cast2d into the
+        bucket + a block update - which the trailing columns always take.  Every column is rounded once per window."""
+        dP1T, AT, D1, K1, Mp, acc, A, M, at_row0 = self._tail
+        ga = self._gview("fc1.weight", (D1, K1))
+        acc = not win.first
+        split = (at_row0 if at_row0 > 0 else K1) if tn else 0
+        if split < K1:
+            ops.gemm_nt(dP1T, AT[split:], D1, K1 - split, Mp, out=ga[:, split:].unsqueeze(0), accumulate=acc)
+            if win.closing:
+                ops.cast2d(ga[:, split:], D1, K1 - split, bucket[:, split:])
+                if hook is not None:
+                    hook(("fc1b", 0, D1, split, K1))
+        if split == 0:
+            return
+        ftn = getattr(self, "fc1_fused_tn", None)
+        if win.closing and ftn is not None:
+            plan = self._fc1_col_plan(dP1T.dtype, D1, K1)
+            if plan is not None and plan[0] == split:
+                if not acc:
+                    ga.zero_() if split == K1 else ga[:, :split].zero_()  # a window of one micro-iteration: nothing accumulated
+                if ftn(dP1T, A, D1, split, Mp, M, ga, bucket):
+                    return  # gradient sum, its one rounding AND the update done by the one launch
+                acc = True  # (outside the kernel's class: the unfused sequence on the accumulator as it stands)
+        ops.gemm_tn(dP1T, A[:, :split], D1, split, Mp, M, out=ga[:, :split].unsqueeze(0), accumulate=acc)
+        if win.closing:
+            ops.cast2d(ga[:, :split], D1, split, bucket[:, :split])
+            if hook is not None:
+                hook(("fc1b", 0, D1, 0, split))
+
     def run_fc1_tail(self):
         """Last piece of the explicit backward: announce the small gradients, then the fc6 weight gradient in row
         slabs (each announced as soon as its GEMM is queued).  Normally called by backward() itself; the multi-GPU
@@ -1194,7 +1233,16 @@ class _HeadEngine:
         if hook is not None:
             hook("small")  # everything except fc1.weight is final: the DP engine starts reducing it now
         bucket = getattr(self, "fc1_grad_bucket", None)  # [D1, K1] exchange buffer (bf16 or fp32) instead of the arena
-        if bucket is not None and acc:
+        # window state of the pipelined optimizer (WSL.ITER_SIZE > 1; engine.Window): fc1.weight accumulates in the fp32 arena -
+        # overwritten by the window's first micro-iteration - and is announced to the optimizer by the closing one alone
+        win = getattr(self, "accum_window", None) if getattr(self, "accum_small", False) else None
+        if win is not None:
+            acc = not win.first
+            if not win.closing:
+                hook = None
+        elif getattr(self, "accum_small", False):
+            raise DrnError("WSL.ITER_SIZE > 1: the pipelined optimizer was not told the window position (set_window)")
+        if bucket is not None and acc and win is None:
             raise DrnError("a bucketed fc6 gradient cannot be combined with gradient accumulation")
         gw = bucket if bucket is not None else self._gview("fc1.weight", (D1, K1))
         if self.kshard is not None:
@@ -1218,7 +1266,10 @@ class _HeadEngine:
             raise DrnError("this batch was pooled for the TN form of the fc6 weight gradient (A^T rows below %d were "
                            "not written) but the backward runs the NT form: fc1_tn / the fused update changed in "
                            "between" % at_row0)
-        plan = None if acc else self._fc1_col_plan(dP1T.dtype, D1, K1)
+        if win is not None and bucket is not None:
+            self._fc1_tail_window(win, hook, bucket, tn)
+            slabs = []
+        plan = None if (acc or win is not None) else self._fc1_col_plan(dP1T.dtype, D1, K1)
         if plan is not None:
             # column slabs: the trailing columns that do not fill a slab first (small-tile NT launch on the A^T tail rows,
             # all fc6 rows), then slabs of exact rounds straight from A; every piece is announced as a block

@@ -182,6 +182,31 @@ def gemm_tn_sgd(A, Bt, M, N, K, kb_rows, bucket, weights, mom, shadow, seg_dev, 
     return True
 
 
+def gemm_tn_acc_sgd(A, Bt, M, N, K, kb_rows, grad_acc, bucket, weights, mom, shadow, seg_dev, momentum, first_step,
+                    grad_scale=1.0):
+    """drn_gemm_tn_acc_sgd: gemm_tn_sgd with bucket = bf16(grad_acc + A @ Bt) - the closing micro-step of a gradient-accumulation
+    window; grad_acc [M, N] fp32 (a 2-D view, read only).  Returns False outside the kernel's shape class (nothing was launched:
+    run gemm_tn(accumulate=True) + cast2d + sgd_step_block instead)."""
+    assert A.dtype == torch.bfloat16 and Bt.dtype == torch.bfloat16 and bucket.dtype == torch.bfloat16
+    assert grad_acc.dtype == torch.float32 and grad_acc.dim() == 2 and grad_acc.stride(1) == 1
+    assert weights.dtype == torch.float32 and mom.dtype == torch.float32 and shadow.dtype == torch.bfloat16
+    assert _2d(weights) == _2d(mom) == _2d(shadow)
+    if GEMM_TIMING is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = C.lib().drn_gemm_tn_acc_sgd(C.ptr(A), C.ptr(Bt), C.ptr(grad_acc), C.ptr(bucket), M, N, K, int(kb_rows), _2d(A), _2d(Bt),
+                                     _2d(grad_acc), _2d(bucket), C.ptr(weights), C.ptr(mom), C.ptr(shadow), _2d(weights),
+                                     C.ptr(seg_dev), float(momentum), int(bool(first_step)), float(grad_scale), C.stream())
+    if rc == -3:
+        return False
+    if rc != 0:
+        raise C.DrnError("drn_gemm_tn_acc_sgd failed (%d)" % rc)
+    if GEMM_TIMING is not None:
+        e1.record()
+        GEMM_TIMING.append((e0, e1, 2.0 * M * N * K, ("tn_acc_sgd", M, N, K)))
+    return True
+
+
 def stage_heads_inputs(rois, props, words_src=None, words_dst=None):
     """props[M,4] <- rois[M,1:5]; words_dst <- words_src (int32 blocks of equal length), one launch"""
     assert rois.dtype == torch.float32 and props.dtype == torch.float32 and rois.is_contiguous() and props.is_contiguous()

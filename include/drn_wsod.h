@@ -246,6 +246,22 @@ int drn_gemm_tn_sgd(const void* A, const void* Bt, void* grad_bucket, int M, int
                     long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w, const void* seg_dev,
                     float momentum, int first_step, float grad_scale, void* stream);
 
+/* drn_gemm_tn_acc_sgd: the closing micro-step of a gradient-accumulation window for the fc6 weight, as one launch.  The reference
+ * accumulates WSL.ITER_SIZE micro-iterations before every optimizer step (projects/WSL/tools/train_net.py:100-113: each one
+ * back-propagates loss / ITER_SIZE, optimizer.step() and zero_grad() run when iter % ITER_SIZE == 0); for box_head.py:82-91's fc1
+ * the gradient of the window is the sum of its micro-steps' dW = dY^T X.  This entry is drn_gemm_tn_sgd with one more operand,
+ * grad_acc (fp32, [M][ld_acc]) - the sum of the window's earlier micro-steps, as drn_gemm_tn (fp32 C, accumulate) leaves it:
+ *   G = bf16(grad_acc + A[M][K] . Bt[K][N])
+ * formed in fp32 and rounded to bf16 ONCE (the single rounding point the bf16 gradient bucket has without accumulation), written
+ * to grad_bucket, and the update of drn_gemm_tn_sgd applied with it by the same launch.  Bit-identical to drn_gemm_tn (fp32,
+ * accumulate = 1) on grad_acc, drn_cast2d to bf16, drn_sgd_step.  grad_acc is read, never written; what it holds afterwards is
+ * unspecified to callers (the next window's first micro-step overwrites it).  Shape class and error codes of drn_gemm_tn_sgd,
+ * plus ld_acc % 4 == 0, a 16-byte aligned grad_acc and M * ld_acc * 4 inside the 32-bit offset range (DRN_ERR_UNSUPPORTED
+ * otherwise); grad_acc == NULL or ld_acc < N is DRN_ERR_ARG. */
+int drn_gemm_tn_acc_sgd(const void* A, const void* Bt, const float* grad_acc, void* grad_bucket, int M, int N, int K, int kb_rows,
+                        long lda, long ldb, long ld_acc, long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w,
+                        const void* seg_dev, float momentum, int first_step, float grad_scale, void* stream);
+
 /* tuning / test hook: pin the GEMM tile to 64, 128 or 256 (0 = heuristic); returns the previous setting. */
 int drn_gemm_set_tile(int tile);
 
