@@ -23,6 +23,24 @@ def get_precision():
     return _PRECISION
 
 
+_DETERMINISTIC = False
+
+
+def set_deterministic(flag):
+    """True: every float accumulation of the package runs in a fixed order (the counterpart of
+    torch.use_deterministic_algorithms): the RoIPool / ROIAlign backward - the one kernel that accumulates with fp32 atomics -
+    goes through drn_roi_pool_backward_det_nhwc wherever ops.roi_pool_backward_nhwc is not told otherwise.  False (the
+    default): the atomic scatter."""
+    global _DETERMINISTIC
+    if not isinstance(flag, bool):
+        raise TypeError("set_deterministic expects a bool, got %r" % (flag,))
+    _DETERMINISTIC = flag
+
+
+def get_deterministic():
+    return _DETERMINISTIC
+
+
 def compute_dtype():
     import torch
 

@@ -35,6 +35,7 @@ _SIGS = {
     "drn_stage_heads_inputs": "ppippip",
     "drn_stage_rois": "ppfpppip",
     "drn_roi_pool_backward_nhwc": "ppppp" + "iiiiii" + "f" + "l" + "iiiip",
+    "drn_roi_pool_backward_det_nhwc": "ppppp" + "iiiiii" + "f" + "l" + "iiii" + "plp",
     "drn_transpose2d": "ppiilliip",
     "drn_gemm_nt": "pppiiillliiilip",
     "drn_gemm_tn": "ppp" + "iiii" + "lll" + "iilip",
@@ -110,6 +111,8 @@ def lib():
         _lib.drn_gemm_nt_main_cols.restype = ctypes.c_long
         _lib.drn_roi_pool_workspace_bytes.argtypes = [ctypes.c_int] * 10
         _lib.drn_roi_pool_workspace_bytes.restype = ctypes.c_long
+        _lib.drn_roi_backward_det_ws_bytes.argtypes = [ctypes.c_int] * 4
+        _lib.drn_roi_backward_det_ws_bytes.restype = ctypes.c_long
         for kv in filter(None, os.environ.get("DRN_TUNE", "").split(",")):  # A/B runs: DRN_TUNE="5=0,4=1024" (drn_tune knobs)
             k, v = kv.split("=")
             _lib.drn_tune(int(k), int(v))
@@ -117,7 +120,8 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes"])
+    return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
+                                  "drn_roi_backward_det_ws_bytes"])
 
 
 _ERR = {-1: "invalid argument", -2: "kernel launch failure", -3: "unsupported"}

@@ -471,6 +471,195 @@ __global__ __launch_bounds__(256) void roi_bwd_kernel(RoiBwdParams p) {
   }
 }
 
+// ---- the same backward with a FIXED accumulation order and no atomics (drn_roi_pool_backward_det_nhwc) --------
+// dfeat[b, y, x, c] = +0.0f plus the contributions that land on it, added one at a time in ascending (ROI m, bin =
+// ph*P + pw) order - for ROIAlign then iy, ix and the taps (yl,xl), (yl,xh), (yh,xl), (yh,xh) - each contribution
+// rounded to fp32 before it is added (the scaled gradient sits in LDS as fp32; this file is built without contraction).
+// For RoIPool that is the order of the oracle's sequential scatter, so the result equals it bit for bit.
+// Every accumulator has ONE owner: the map is cut into T x T pixel tiles, a workgroup (one wave, lane = channel) owns
+// one tile of one image for 64 channels, keeps the [T*T][64] fp32 accumulator in LDS and STORES it at the end - every
+// element of dfeat is written exactly once, zeros included, so there is no memset either.
+//   pass 1 (roi_det_list_kernel): one wave per (image, tile) walks the ROIs in ascending order, 64 per round; a lane
+//     keeps its ROI if it is of that image and some bin can reach the tile; one ballot + a prefix popcount per round
+//     compact the survivors, so the list comes out ascending with no sort and no atomic.  An entry is (m, the bin rows
+//     that can reach the tile as a bit mask | the bin columns << 8): RoIPool from the forward's own window bounds (the
+//     arg-max of a bin lies in its window), ROIAlign from the bin's sample extent widened by two pixels (a superset -
+//     only taps inside the tile are ever added).
+//   pass 2 (roi_bwd_det_kernel): walks its tile's list in order; per entry the rows [first, last masked bin row] of the
+//     64-channel slice of grad_out are staged into LDS with coalesced reads (a large ROI on a large map is not re-read
+//     whole by every tile it covers), RoIPool's arg-max is turned into a tile-local pixel (or "not mine") on the way;
+//     then lane = channel walks the masked bins in ascending order and adds into its own LDS column.
+// Workspace: tiles(4) records of (M + 1) 8-byte entries, entry 0 = the count (drn_roi_backward_det_ws_bytes); the tile
+// edge is 4 when 8 would leave fewer than 256 workgroups (a 14x14 map), else 8 - the result does not depend on it.
+struct RoiDetParams {
+  const char* grad_out; const float* rois; const float* obj; const int32_t* argmax; float* dfeat;
+  int2* ws;
+  int N, H, W, C, P, M; float scale; long ld; int sampling_ratio, aligned;
+  int tiles_y, tiles_x;
+  unsigned wmagic;  // ceil(2^32 / W) (W >= 2): offset inside a tile's rows -> row by one v_mul_hi
+};
+
+struct RoiAlignGeom { float sh, sw, bin_h, bin_w, count; int gh, gw; };
+__device__ __forceinline__ RoiAlignGeom roi_align_geom(const float* roi, float scale, int aligned, int P, int sampling_ratio) {
+  RoiAlignGeom g;
+  const float off = aligned ? 0.5f : 0.f;
+  g.sw = roi[1] * scale - off; g.sh = roi[2] * scale - off;
+  const float ew = roi[3] * scale - off, eh = roi[4] * scale - off;
+  float rw = ew - g.sw, rh = eh - g.sh;
+  if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
+  g.bin_h = rh / (float)P; g.bin_w = rw / (float)P;
+  g.gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / P);
+  g.gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / P);
+  g.count = (float)(g.gh * g.gw);
+  return g;
+}
+
+template <int MODE, int T>
+__global__ __launch_bounds__(64) void roi_det_list_kernel(RoiDetParams p) {
+  const int lane = threadIdx.x;
+  const int id = blockIdx.x, per = p.tiles_y * p.tiles_x;
+  const int b = id / per, t = id - b * per;
+  const int ty0 = (t / p.tiles_x) * T, tx0 = (t % p.tiles_x) * T;
+  const int ty1 = min(ty0 + T, p.H), tx1 = min(tx0 + T, p.W);
+  int2* rec = p.ws + (long)id * (p.M + 1);
+  int n = 0;
+  for (int m0 = 0; m0 < p.M; m0 += 64) {
+    const int m = m0 + lane;
+    unsigned hmask = 0, wmask = 0;
+    if (m < p.M) {
+      const float* roi = p.rois + 5 * (long)m;
+      if ((int)roi[0] == b) {
+        if (MODE == 0) {
+          const int x1 = (int)roundf(roi[1] * p.scale), y1 = (int)roundf(roi[2] * p.scale);
+          const int x2 = (int)roundf(roi[3] * p.scale), y2 = (int)roundf(roi[4] * p.scale);
+          const int rw = max(x2 - x1 + 1, 1), rh = max(y2 - y1 + 1, 1);
+          const float bin_h = (float)rh / (float)p.P, bin_w = (float)rw / (float)p.P;
+          for (int i = 0; i < p.P; ++i) {  // the forward's window bounds, op for op
+            const int hs = min(max((int)floorf((float)i * bin_h) + y1, 0), p.H);
+            const int he = min(max((int)ceilf((float)(i + 1) * bin_h) + y1, 0), p.H);
+            const int ws = min(max((int)floorf((float)i * bin_w) + x1, 0), p.W);
+            const int we = min(max((int)ceilf((float)(i + 1) * bin_w) + x1, 0), p.W);
+            if (max(hs, ty0) < min(he, ty1)) hmask |= 1u << i;
+            if (max(ws, tx0) < min(we, tx1)) wmask |= 1u << i;
+          }
+        } else {
+          const RoiAlignGeom g = roi_align_geom(roi, p.scale, p.aligned, p.P, p.sampling_ratio);
+          if (g.gh > 0 && g.gw > 0)
+            for (int i = 0; i < p.P; ++i) {
+              // every sample of bin row i lies between its two edges (up to rounding); its taps are floor(y), floor(y) + 1
+              const float ya = g.sh + i * g.bin_h, yb = g.sh + (i + 1) * g.bin_h;
+              const float xa = g.sw + i * g.bin_w, xb = g.sw + (i + 1) * g.bin_w;
+              const float ylo = fminf(fmaxf(fminf(ya, yb), -2.f), (float)p.H + 2.f), yhi = fminf(fmaxf(fmaxf(ya, yb), -2.f), (float)p.H + 2.f);
+              const float xlo = fminf(fmaxf(fminf(xa, xb), -2.f), (float)p.W + 2.f), xhi = fminf(fmaxf(fmaxf(xa, xb), -2.f), (float)p.W + 2.f);
+              if ((int)floorf(ylo) - 1 < ty1 && (int)floorf(yhi) + 2 >= ty0) hmask |= 1u << i;
+              if ((int)floorf(xlo) - 1 < tx1 && (int)floorf(xhi) + 2 >= tx0) wmask |= 1u << i;
+            }
+        }
+      }
+    }
+    const bool keep = hmask != 0 && wmask != 0;
+    const unsigned long long bal = __ballot(keep);
+    if (keep) rec[1 + n + __popcll(bal & ((1ull << lane) - 1ull))] = make_int2(m, (int)(hmask | (wmask << 8)));
+    n += __popcll(bal);
+  }
+  if (lane == 0) rec[0] = make_int2(n, 0);
+}
+
+template <int DT, int MODE, int T>
+__global__ __launch_bounds__(64) void roi_bwd_det_kernel(RoiDetParams p) {
+  using E = ElemOf<DT>;
+  using TG = typename E::type;
+  constexpr int NOT_MINE = 255;
+  __shared__ float acc[T * T][RP_CH];               // lane = channel: conflict-free
+  __shared__ float tile[RP_CH][RP_MAXBIN + 1];      // the scaled gradients, fp32
+  __shared__ unsigned char apix[MODE == 0 ? RP_CH : 1][RP_MAXBIN + 4];  // RoIPool: tile-local arg-max pixel; 17-word pitch
+  const int lane = threadIdx.x;
+  const int id = blockIdx.x, per = p.tiles_y * p.tiles_x;
+  const int b = id / per, t = id - b * per;
+  const int ty0 = (t / p.tiles_x) * T, tx0 = (t % p.tiles_x) * T;
+  const int th = min(T, p.H - ty0), tw = min(T, p.W - tx0);
+  const int c0 = blockIdx.y * RP_CH, nch = min(RP_CH, p.C - c0);
+  const int PP = p.P * p.P;
+#pragma unroll
+  for (int q = 0; q < T * T; ++q) acc[q][lane] = 0.f;
+  const int2* rec = p.ws + (long)id * (p.M + 1);
+  const int n = rec[0].x;
+  const unsigned tbase = (unsigned)(ty0 * p.W + tx0), tspan = (unsigned)((th - 1) * p.W + tw);
+  for (int e = 0; e < n; ++e) {
+    const int2 ent = rec[1 + e];
+    const int m = ent.x;
+    const unsigned hmask = (unsigned)ent.y & 0xffu, wmask = ((unsigned)ent.y >> 8) & 0xffu;
+    const int ph_lo = __builtin_ctz(hmask), ph_hi = 31 - __builtin_clz(hmask);
+    const int off = ph_lo * p.P, L = (ph_hi - ph_lo + 1) * p.P;  // the staged run of every channel: bins [off, off + L)
+    const float mul = p.obj ? p.obj[m] + 1.f : 1.f;
+    const TG* grow = (const TG*)p.grad_out + (long)m * p.ld + (long)c0 * PP;
+    const int32_t* arow = MODE == 0 ? p.argmax + (long)m * p.C * PP + (long)c0 * PP : nullptr;
+    __syncthreads();  // the previous entry's walk no longer reads the staging tiles
+    const float inv_l = 1.f / (float)L;
+    for (int i = lane; i < nch * L; i += 64) {
+      const int lc = (int)(((float)i + 0.5f) * inv_l);  // i / L: i < 4096, L <= 64 - the product is >= 1/128 away from an integer
+      const int j = off + (i - lc * L);
+      tile[lc][j] = E::ld(grow + lc * PP + j) * mul;
+      if constexpr (MODE == 0) {
+        // arg-max (h*W + w) -> pixel of this tile, or NOT_MINE (also for -1 and for anything outside the map)
+        const unsigned u = (unsigned)arow[lc * PP + j] - tbase;
+        int q = NOT_MINE;
+        if (u < tspan) {
+          const unsigned r = p.W > 1 ? __umulhi(u, p.wmagic) : u, x = u - r * (unsigned)p.W;
+          if (x < (unsigned)tw) q = (int)(r * T + x);
+        }
+        apix[lc][j] = (unsigned char)q;
+      }
+    }
+    __syncthreads();
+    if (lane < nch) {
+      if constexpr (MODE == 0) {
+        for (int ph = ph_lo; ph <= ph_hi; ++ph)
+          for (unsigned wm = wmask; wm; wm &= wm - 1) {
+            const int bin = ph * p.P + __builtin_ctz(wm);
+            const int q = apix[lane][bin];
+            if (q != NOT_MINE) acc[q][lane] += tile[lane][bin];
+          }
+      } else {
+        const RoiAlignGeom g = roi_align_geom(p.rois + 5 * (long)m, p.scale, p.aligned, p.P, p.sampling_ratio);
+        for (int ph = ph_lo; ph <= ph_hi; ++ph) {
+          if (!((hmask >> ph) & 1u)) continue;
+          for (unsigned wm = wmask; wm; wm &= wm - 1) {
+            const int pw = __builtin_ctz(wm);
+            const float gv = tile[lane][ph * p.P + pw];
+            for (int iy = 0; iy < g.gh; ++iy) {
+              const float yy = g.sh + ph * g.bin_h + (float)(iy + .5f) * g.bin_h / (float)g.gh;
+              for (int ix = 0; ix < g.gw; ++ix) {
+                const float xx = g.sw + pw * g.bin_w + (float)(ix + .5f) * g.bin_w / (float)g.gw;
+                float x = xx, y = yy;
+                if (y < -1.0f || y > p.H || x < -1.0f || x > p.W) continue;
+                if (y <= 0) y = 0;
+                if (x <= 0) x = 0;
+                int yl = (int)y, xl = (int)x, yh, xh;
+                if (yl >= p.H - 1) { yh = yl = p.H - 1; y = (float)yl; } else yh = yl + 1;
+                if (xl >= p.W - 1) { xh = xl = p.W - 1; x = (float)xl; } else xh = xl + 1;
+                const float ly = y - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
+                const unsigned ryl = (unsigned)(yl - ty0), ryh = (unsigned)(yh - ty0);
+                const unsigned rxl = (unsigned)(xl - tx0), rxh = (unsigned)(xh - tx0);
+                const bool iyl = ryl < (unsigned)th, iyh = ryh < (unsigned)th, ixl = rxl < (unsigned)tw, ixh = rxh < (unsigned)tw;
+                if (iyl && ixl) acc[ryl * T + rxl][lane] += gv * (hy * hx) / g.count;
+                if (iyl && ixh) acc[ryl * T + rxh][lane] += gv * (hy * lx) / g.count;
+                if (iyh && ixl) acc[ryh * T + rxl][lane] += gv * (ly * hx) / g.count;
+                if (iyh && ixh) acc[ryh * T + rxh][lane] += gv * (ly * lx) / g.count;
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  if (lane < nch) {
+    float* ob = p.dfeat + (((long)b * p.H + ty0) * p.W + tx0) * p.C + c0 + lane;
+    for (int r = 0; r < th; ++r)
+      for (int x = 0; x < tw; ++x) ob[((long)r * p.W + x) * p.C] = acc[r * T + x][lane];
+  }
+}
+
 // ---- backward of the conv trunk (only when MODEL.BACKBONE.FREEZE_AT < 5) -------------------------------------
 // Transposed im2col: out[(ci*KH + kh)*KW + kw][p] = x[n, ho*s + kh*d - pad, wo*s + kw*d - pad, ci] (0 outside),
 // p = (n*Ho + ho)*Wo + wo.  It is the K-major B operand of the weight-gradient GEMM  dW[co][ci,kh,kw] = g^T . out^T,
@@ -2542,6 +2731,50 @@ int drn_roi_pool_backward_nhwc(const void* grad_out, const float* rois, const fl
   if (grad_dtype == DRN_BF16) { if (mode == 0) RB_LAUNCH(DRN_BF16, 0); else RB_LAUNCH(DRN_BF16, 1); }
   else { if (mode == 0) RB_LAUNCH(DRN_F32, 0); else RB_LAUNCH(DRN_F32, 1); }
 #undef RB_LAUNCH
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// The deterministic form of drn_roi_pool_backward_nhwc (see roi_bwd_det_kernel): same arguments plus a caller-owned
+// workspace of drn_roi_backward_det_ws_bytes(N, H, W, M) bytes.  No memset, no atomics; two launches.
+static inline long roi_det_tiles(int N, int H, int W, int T) { return (long)N * ((H + T - 1) / T) * ((W + T - 1) / T); }
+
+long drn_roi_backward_det_ws_bytes(int N, int H, int W, int M) {
+  if (N < 1 || H < 1 || W < 1 || M < 0) return 0;
+  return 8L * ((long)M + 1) * roi_det_tiles(N, H, W, 4);
+}
+
+int drn_roi_pool_backward_det_nhwc(const void* grad_out, const float* rois, const float* objectness, const int32_t* argmax,
+                                   float* dfeat, int N, int H, int W, int C, int P, int M, float spatial_scale, long ld_g,
+                                   int mode, int sampling_ratio, int aligned, int grad_dtype, void* ws, long ws_bytes,
+                                   void* stream) {
+  if (!dfeat || P < 1 || P * P > RP_MAXBIN || M < 0 || (mode != 0 && mode != 1)) return DRN_ERR_ARG;
+  if (N < 1 || H < 1 || W < 1 || C < 1 || (M > 0 && (!grad_out || !rois || (mode == 0 && !argmax) || ld_g < (long)C * P * P)))
+    return DRN_ERR_ARG;
+  if (grad_dtype != DRN_F32 && grad_dtype != DRN_BF16) return DRN_ERR_ARG;
+  if (!ws || (((uintptr_t)ws) & 7) != 0 || ws_bytes < drn_roi_backward_det_ws_bytes(N, H, W, M)) return DRN_ERR_ARG;
+  const int chunks = (C + RP_CH - 1) / RP_CH;
+  // W bounds the exact range of the row-by-multiply in the kernel (8 * W * W < 2^32); the grid's y extent bounds C
+  if (W > 16384 || chunks > 65535 || roi_det_tiles(N, H, W, 4) > 0x7fffffffL) return DRN_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int T = roi_det_tiles(N, H, W, 8) * chunks < 256 ? 4 : 8;
+  RoiDetParams p{(const char*)grad_out, rois, objectness, argmax, dfeat, (int2*)ws, N, H, W, C, P, M, spatial_scale, ld_g,
+                 sampling_ratio, aligned, (H + T - 1) / T, (W + T - 1) / T,
+                 W > 1 ? (unsigned)((0x100000000ULL + (unsigned)W - 1) / (unsigned)W) : 0u};
+  const dim3 lgrid((unsigned)roi_det_tiles(N, H, W, T)), grid((unsigned)roi_det_tiles(N, H, W, T), chunks), block(64);
+#define RD_LIST(MD, TT) hipLaunchKernelGGL((roi_det_list_kernel<MD, TT>), lgrid, block, 0, st, p)
+#define RD_ACC(DT, MD, TT) hipLaunchKernelGGL((roi_bwd_det_kernel<DT, MD, TT>), grid, block, 0, st, p)
+#define RD_BOTH(MD, TT)                                                  \
+  do {                                                                   \
+    RD_LIST(MD, TT);                                                     \
+    DRN_CHECK_LAUNCH();                                                  \
+    if (grad_dtype == DRN_BF16) RD_ACC(DRN_BF16, MD, TT); else RD_ACC(DRN_F32, MD, TT); \
+  } while (0)
+  if (mode == 0) { if (T == 4) RD_BOTH(0, 4); else RD_BOTH(0, 8); }
+  else { if (T == 4) RD_BOTH(1, 4); else RD_BOTH(1, 8); }
+#undef RD_BOTH
+#undef RD_ACC
+#undef RD_LIST
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

@@ -462,12 +462,34 @@ def add(a, b, out=None):
     return out
 
 
+def roi_backward_det_ws_bytes(n, h, w, m):
+    """bytes of workspace drn_roi_pool_backward_det_nhwc needs (host-only: no device is touched)"""
+    return C.lib().drn_roi_backward_det_ws_bytes(int(n), int(h), int(w), int(m))
+
+
 def roi_pool_backward_nhwc(grad_out, rois, objectness, feat_shape, P, scale, mode=0, sampling_ratio=0, aligned=False,
-                           argmax=None):
-    """grad_out [M, >= C*P*P] -> d(feat) [N,H,W,C] fp32 (see drn_roi_pool_backward_nhwc)."""
+                           argmax=None, deterministic=None, out=None):
+    """grad_out [M, >= C*P*P] -> d(feat) [N,H,W,C] fp32 (see drn_roi_pool_backward_nhwc).
+    deterministic: True = the order-fixed, atomic-free form (drn_roi_pool_backward_det_nhwc: bit-reproducible, RoIPool
+    bit-equal to a sequential host scatter), False = the atomic scatter, None = the package's mode (set_deterministic).
+    out: an fp32 [N,H,W,C] tensor to write into (every element is written)."""
+    from . import get_deterministic
+
     n, h, w, c = feat_shape
     m = rois.shape[0]
-    dfeat = torch.empty((n, h, w, c), dtype=torch.float32, device=grad_out.device)
+    assert grad_out.is_cuda and rois.is_cuda, "drn ops need device tensors (no CPU path)"
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=grad_out.device)
+    dfeat = out
+    assert dfeat.is_cuda and dfeat.dtype == torch.float32 and dfeat.is_contiguous() and tuple(dfeat.shape) == (n, h, w, c)
+    if get_deterministic() if deterministic is None else deterministic:
+        # scratch for the per-tile ROI lists: from torch's caching allocator on the current stream, nothing is kept between calls
+        ws_bytes = roi_backward_det_ws_bytes(n, h, w, m)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=grad_out.device)
+        C.call("drn_roi_pool_backward_det_nhwc", C.ptr(grad_out), C.ptr(rois), C.ptr(objectness), C.ptr(argmax), C.ptr(dfeat),
+               n, h, w, c, P, m, float(scale), _2d(grad_out), mode, sampling_ratio, int(aligned), C.dt(grad_out.dtype),
+               C.ptr(ws), ws_bytes, C.stream())
+        return dfeat
     C.call("drn_roi_pool_backward_nhwc", C.ptr(grad_out), C.ptr(rois), C.ptr(objectness), C.ptr(argmax), C.ptr(dfeat),
            n, h, w, c, P, m, float(scale), _2d(grad_out), mode, sampling_ratio, int(aligned), C.dt(grad_out.dtype),
            C.stream())

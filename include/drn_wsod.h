@@ -188,6 +188,30 @@ int drn_roi_pool_backward_nhwc(const void* grad_out, const float* rois, const fl
                                float* dfeat, int N, int H, int W, int C, int P, int M, float spatial_scale, long ld_g,
                                int mode, int sampling_ratio, int aligned, int grad_dtype, void* stream);
 
+/* The same backward with a FIXED accumulation order and no float atomics (bit-reproducible training; the package's
+ * deterministic mode).  Definition: dfeat[b][y][x][c] is the fp32 result of starting at +0.0f and adding the contributions
+ * that land on that element one at a time in ascending order of (ROI index m, bin = ph*P + pw) - for ROIAlign the order
+ * continues with iy, ix and the taps (y_low,x_low), (y_low,x_high), (y_high,x_low), (y_high,x_high).  A contribution is
+ * fl32(g[m][c*P*P + bin] * (objectness[m] + 1)) for RoIPool when the arg-max is >= 0 (no product without objectness) and that
+ * value * (hy*hx) / count per tap for ROIAlign, rounded to fp32 BEFORE it is added (no contraction).  ROIs of different
+ * images may interleave; the order is by m.  An element no contribution reaches is +0.0f; every element of dfeat is stored
+ * exactly once (no memset).  RoIPool: bit-equal to a sequential scatter over m, c, bin on the host.
+ * Two launches: a tile-list pass (one wave per image x pixel tile compacts, by ballot, the ascending list of ROIs that can
+ * reach the tile) and an accumulate pass (one wave per tile x 64 channels owns its accumulators in LDS and stores them).
+ * Class: grad_out fp32 or bf16, any C (ragged last 64-channel chunk), any H, W <= 16384 (ragged edge tiles), P*P <= 64,
+ * M >= 0 (M == 0 stores zeros; grad_out / rois / argmax may then be NULL); mode 0 expects the arg-max drn_roi_pool_nhwc
+ * returned for the same rois and scale (an arg-max outside its bin's window, or outside the map, is dropped); a ROI whose
+ * batch index is outside [0, N) is dropped.  DRN_ERR_ARG for a NULL, misaligned (8 bytes) or too small workspace.
+ * Workspace: drn_roi_backward_det_ws_bytes(N, H, W, M) = 8 * (M + 1) * N * ceil(H / 4) * ceil(W / 4) bytes - per 4 x 4 pixel
+ * tile of every image one count and up to M entries of 8 bytes (ROI index, bin-row mask | bin-column mask << 8); the kernels
+ * use 8 x 8 tiles (a quarter of the records) when that still fills the device.  Host-only, needs no device; 0 for invalid sizes.
+ * The workspace is written and read on `stream` only and holds nothing between calls. */
+long drn_roi_backward_det_ws_bytes(int N, int H, int W, int M);
+int drn_roi_pool_backward_det_nhwc(const void* grad_out, const float* rois, const float* objectness, const int32_t* argmax,
+                                   float* dfeat, int N, int H, int W, int C, int P, int M, float spatial_scale, long ld_g,
+                                   int mode, int sampling_ratio, int aligned, int grad_dtype, void* workspace,
+                                   long workspace_bytes, void* stream);
+
 /* out[c][r] = cast(in[r][c]) — builds the K-major operands of the dW GEMMs. */
 int drn_transpose2d(const void* in, void* out, int rows, int cols, long ld_in, long ld_out, int in_dtype,
                     int out_dtype, void* stream);
