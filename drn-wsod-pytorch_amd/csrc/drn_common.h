@@ -155,7 +155,8 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-// Lets `kernel` take `bytes` of dynamic LDS (launches above the 48-KB default need the attribute raised first).  The runtime
+// Launch helpers shared by the translation units.
+// allow_lds lets `kernel` take `bytes` of dynamic LDS (launches above the 48-KB default need the attribute raised first).  The runtime
 // call is made once per kernel: the kernels already raised are remembered in a small table (unlocked, like the launches
 // themselves: a lost race only repeats the call; a full table only stops caching).
 namespace drn_launch {
@@ -171,5 +172,17 @@ inline bool allow_lds(const void* kernel, int bytes) {
     ++n;
   }
   return true;
+}
+
+// Compute units of the current device; cached.  256 (an MI355X) when the query fails.
+inline int cu_count() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t pr;
+    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+            ? pr.multiProcessorCount : 256;
+  }
+  return n;
 }
 }  // namespace drn_launch

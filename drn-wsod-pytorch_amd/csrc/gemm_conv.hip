@@ -2029,16 +2029,7 @@ int launch_gemm256(const GemmParams& p, int splits, hipStream_t st) {
 }
 
 
-static int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
+using drn_launch::cu_count;
 
 template <int DT, int PP = 0, bool TN = false>
 int launch_gemm256p(const GemmParams& p, int nwg, hipStream_t st) {

@@ -621,16 +621,7 @@ int drn_linear_act_fwd(const void* A, const void* W, const float* bias, const fl
   p.bias = bias; p.relu = relu;
   p.Y = (char*)out; p.ldy = ld_out; p.YT = (char*)outT; p.ldyt = ld_outT;
   p.mask = mask; p.seed = seed; p.seed_dev = seed_dev; p.drop_p = drop_p;
-  int dev = 0, cus = 256;
-  hipDeviceProp_t prop;
-  static int cached = 0;
-  if (!cached) {
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cached = prop.multiProcessorCount;
-    else cached = 256;
-  }
-  cus = cached;
-  return launch_pp8_any<PP8_FC>(p, pp8_wide_ok(M, N, cus), (hipStream_t)stream);
+  return launch_pp8_any<PP8_FC>(p, pp8_wide_ok(M, N, drn_launch::cu_count()), (hipStream_t)stream);
 }
 
 }  // extern "C"

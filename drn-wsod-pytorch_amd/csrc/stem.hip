@@ -177,18 +177,6 @@ __global__ __launch_bounds__(256) void stem7x7_pool_kernel(StemParams p) {
   }
 }
 
-int stem_cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
 }  // namespace
 
 extern "C" int drn_stem7x7_pool_nhwc(const void* x, const void* w, const float* scale, const float* bias, void* y, int Nb,
@@ -209,7 +197,7 @@ extern "C" int drn_stem7x7_pool_nhwc(const void* x, const void* w, const float* 
   const long ntiles = (long)Nb * p.tiles_y * p.tiles_x;
   if (ntiles > 0x7fffffffL) return DRN_ERR_UNSUPPORTED;
   if (!drn_launch::allow_lds((const void*)stem7x7_pool_kernel, ST_LDS)) return DRN_ERR_LAUNCH;
-  const int grid = (int)(ntiles < stem_cu_count() ? ntiles : stem_cu_count());
+  const int grid = (int)(ntiles < drn_launch::cu_count() ? ntiles : drn_launch::cu_count());
   hipLaunchKernelGGL(stem7x7_pool_kernel, dim3(grid), dim3(256), ST_LDS, (hipStream_t)stream, p);
   DRN_CHECK_LAUNCH();
   return DRN_OK;

@@ -34,7 +34,7 @@ struct DrnTune {
   int pp8_wide = 1;          // 29 DRN_TUNE_PP8_WIDE: the 256x128 form: 0 = never, 1 = where it fills the chip, 2 = always
   int pp8_wvar = 4;          // 30 DRN_TUNE_PP8_WIDE_VARIANT: VAR of the 256x128 form (1 = all DMA pieces in phase L1, 4 = no s_setprio, 8 = profile)
   int roi_st = 1;            // 31 DRN_TUNE_ROI_ST: 0 = off, 1 = where it is faster (large maps with enough ROIs), 2 = every map whose slice fits ...
-  int roi_st_prof = 0;       //   ... and its profile builds (knob values 10 / 11: on / off; 12: pool.hip prints and clears the counters)
+  int roi_st_prof = 0;       //   ... and its profile builds (knob values 10 / 11: on / off; 12: roi.hip prints and clears the counters)
   int msm_wave = 1;          // 32 DRN_TUNE_MSM_WAVE: 0 = the thread-per-row kernel also for C <= 64 (tests, A/B)
   int force_tile = 0;        // drn_gemm_set_tile: 0 = heuristic; 64 / 128 / 256 pin the GEMM tile (tuning + tests)
 };
@@ -43,4 +43,4 @@ extern __attribute__((visibility("hidden"))) DrnTune g_tune;
 
 // The two knobs that act on device symbols of their own translation unit (called from drn_tune's table):
 __attribute__((visibility("hidden"))) int drn_tune_pp8_profile_dump();  // pp8.hip, knob 28: 0, or -1 when the device calls fail
-__attribute__((visibility("hidden"))) int drn_tune_roi_st_profile_dump();  // pool.hip, knob 31 value 12: likewise
+__attribute__((visibility("hidden"))) int drn_tune_roi_st_profile_dump();  // roi.hip, knob 31 value 12: likewise

@@ -775,6 +775,28 @@ def test_roi_pool(drn, dtype, C, P, scale, H, W, R):
     assert (out_t[:, R:] == 0).all()
 
 
+@pytest.mark.parametrize("C", [64, 70])
+def test_roi_pool_unaligned_out_rows(drn, C):
+    """An `out` whose row stride is not a multiple of 16 bytes (a column-sliced view: kpad + 1 elements per row) takes none of
+    the kernels that store 16 bytes at a time - C = 64: roi_kernel's window-staged path instead of the lane-per-bin kernel,
+    C = 70: its direct path - and must equal the aligned call bit for bit, with nothing written beside the view."""
+    dtype, P, scale, H, W, R, n_img = torch.bfloat16, 7, 1.0 / 16, 14, 14, 70, 2
+    feat = _rnd((n_img, C, H, W), 61)
+    rois = _rois(R, n_img, W / scale, H / scale, 62).to(DEV)
+    obj = torch.rand(R).to(DEV)
+    fd = feat.permute(0, 2, 3, 1).contiguous().to(DEV).to(dtype)
+    kp = drn.kpad(C * P * P, dtype)
+    want = drn.roi_pool_nhwc(fd, rois, obj, P, scale)
+    buf = torch.full((R, kp + 1), 5.0, dtype=dtype, device=DEV)
+    buf[:, C * P * P:kp] = 0
+    out = buf[:, :kp]
+    assert out.data_ptr() % 16 == 0 and (out.stride(0) * out.element_size()) % 16 != 0
+    drn.roi_pool_nhwc(fd, rois, obj, P, scale, out=out)
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    assert (buf[:, kp] == 5.0).all()
+
+
 @pytest.mark.parametrize("C,H,W,R,t0", [(1024, 14, 14, 2000, 1003), (64, 14, 14, 200, 40), (128, 50, 76, 130, 127),
                                         (70, 19, 23, 100, 30)])
 def test_roi_pool_transposed_tail_hint(drn, C, H, W, R, t0):
