@@ -11,12 +11,14 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdrn_wsod_hip.so")
 
 F32, BF16, FP8 = 0, 1, 2
 
-_T = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "Q": ctypes.c_ulonglong}
+_T = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "d": ctypes.c_double,
+      "Q": ctypes.c_ulonglong}
 
 # signature strings follow include/drn_wsod.h argument for argument
 _SIGS = {
     "drn_preprocess_nhwc": "piiipiiippip",
     "drn_resize_bilinear_u8": "piiipiippippiip",
+    "drn_augment_u8": "piii" + "iiii" + "pii" + "ppi" + "ppi" + "i" + "if" + "idf" + "p",
     "drn_conv2d_nhwc": "pppppp" + "iiiiiiiiii" + "lll" + "iip",
     "drn_conv2d_nhwc_q": "pppppp" + "iiiiiiiiii" + "lll" + "iiiifp",
     "drn_conv3x3_pw_nhwc": "pppp" + "i" + "pppp" + "p" + "iii" + "ll" + "f" + "ii" + "p",
@@ -113,6 +115,8 @@ def lib():
         _lib.drn_roi_pool_workspace_bytes.restype = ctypes.c_long
         _lib.drn_roi_backward_det_ws_bytes.argtypes = [ctypes.c_int] * 4
         _lib.drn_roi_backward_det_ws_bytes.restype = ctypes.c_long
+        _lib.drn_augment_lds_bytes.argtypes = [ctypes.c_int] * 7
+        _lib.drn_augment_lds_bytes.restype = ctypes.c_long
         for kv in filter(None, os.environ.get("DRN_TUNE", "").split(",")):  # A/B runs: DRN_TUNE="5=0,4=1024" (drn_tune knobs)
             k, v = kv.split("=")
             _lib.drn_tune(int(k), int(v))
@@ -121,7 +125,7 @@ def lib():
 
 def exported_symbols():
     return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
-                                  "drn_roi_backward_det_ws_bytes"])
+                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes"])
 
 
 _ERR = {-1: "invalid argument", -2: "kernel launch failure", -3: "unsupported"}

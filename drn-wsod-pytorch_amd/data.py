@@ -20,8 +20,9 @@ reference's crops / scales / flips / colour factors draw for draw (tests/golden/
                                    partition of SURVEY 8(e): rank g takes elements g, g+W, ... of ONE shared shuffled stream)
   AspectRatioGroupedDataset,       detectron2/data/common.py:115-149, :17-73; detectron2/data/build.py:249-296, :299-354
   MapDataset, build_batch_data_loader, build_detection_train_loader
-This is host-side preparation by design (as in the reference: loader workers); everything it emits is what
-GeneralizedRCNNWSL.forward consumes."""
+This is host-side preparation as in the reference (loader workers) unless a device is given: then DatasetMapper splits into
+plan() (host, in the workers) and finish() (the image chain in one launch, ops.augment_u8; see finish's stream contract).
+Everything it emits is what GeneralizedRCNNWSL.forward consumes."""
 import copy
 import pickle
 
@@ -326,9 +327,16 @@ def filter_empty_instances(instances):
 
 
 class DatasetMapper:
-    """dataset dict (file_name or an HWC uint8 "image_array", height, width, annotations, proposal_*) -> model input"""
+    """dataset dict (file_name or an HWC uint8 "image_array", height, width, annotations, proposal_*) -> model input.
 
-    def __init__(self, cfg, is_train=True):
+    device=None: everything runs on the host, as in the reference.  With a device the mapper works in two halves:
+    plan() - host only, picklable, what a loader worker runs - draws the augmentations and transforms the boxes, and
+    finish() - the process that owns the GPU - uploads the decoded image and forms "image" there in one launch
+    (ops.augment_u8): an fp32 [C, Ho, Wo] device tensor holding the same bytes as the host path's uint8 image."""
+
+    PIN_RING = 8  # pinned staging buffers of finish(); reuse of one is guarded by an event
+
+    def __init__(self, cfg, is_train=True, device=None):
         self.is_train = is_train
         self.augmentations = build_augmentation(cfg, is_train)
         if cfg.INPUT.CROP.ENABLED and is_train:
@@ -338,8 +346,21 @@ class DatasetMapper:
         if cfg.MODEL.LOAD_PROPOSALS:
             self.proposal_topk = (cfg.DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TRAIN if is_train
                                   else cfg.DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TEST)
+        self.device = None if device is None else torch.device(device)
+        self._reset_device_state()
 
-    def __call__(self, dataset_dict):
+    def _reset_device_state(self):
+        self._stream = None
+        self._pin = [None] * self.PIN_RING
+        self._pin_ev = [None] * self.PIN_RING
+        self._pin_i = 0
+
+    def __getstate__(self):  # a loader worker gets the host half only: no stream, no pinned memory
+        st = dict(self.__dict__)
+        st.update(_stream=None, _pin=[None] * self.PIN_RING, _pin_ev=[None] * self.PIN_RING, _pin_i=0)
+        return st
+
+    def _read(self, dataset_dict):
         d = copy.deepcopy(dataset_dict)
         image = d.pop("image_array") if "image_array" in d else read_image(d["file_name"], format=self.image_format)
         if "width" in d or "height" in d:
@@ -348,9 +369,9 @@ class DatasetMapper:
                                                                         (d["width"], d["height"])))
         d.setdefault("width", image.shape[1])
         d.setdefault("height", image.shape[0])
-        image, transforms = apply_augmentations(self.augmentations, image)
-        shape = image.shape[:2]
-        d["image"] = torch.as_tensor(np.ascontiguousarray(image.transpose(2, 0, 1)))
+        return d, image
+
+    def _boxes(self, d, shape, transforms):
         if self.proposal_topk is not None:
             transform_proposals(d, shape, transforms, proposal_topk=self.proposal_topk)
         if not self.is_train:
@@ -360,6 +381,141 @@ class DatasetMapper:
             annos = [transform_instance_annotations(o, transforms, shape) for o in d.pop("annotations")
                      if o.get("iscrowd", 0) == 0]
             d["instances"] = filter_empty_instances(annotations_to_instances(annos, shape))
+        return d
+
+    def _host(self, d, image):
+        image, transforms = apply_augmentations(self.augmentations, image)
+        shape = image.shape[:2]
+        d["image"] = torch.as_tensor(np.ascontiguousarray(image.transpose(2, 0, 1)))
+        return self._boxes(d, shape, transforms)
+
+    def __call__(self, dataset_dict):
+        if self.device is not None:
+            return self.finish(self.plan(dataset_dict))
+        return self._host(*self._read(dataset_dict))
+
+    def plan(self, dataset_dict):
+        """The host half: everything __call__ does except producing the image.  Draws from np.random in the host path's order
+        and count (every draw depends on shapes only; RandomSaturation's grey image, the one thing that needs pixels, is
+        formed on the device) and transforms proposals / annotations with the same Transform objects.  Returns what the
+        host path returns without "image", plus "image_src" (the decoded source, a contiguous uint8 [H, W, C] CPU tensor)
+        and "aug" (plain numbers: crop (x0, y0, cw, ch), out_hw, flip, wb, ws; None = that blend is off).  Picklable; makes
+        no torch.cuda call.  An image that is not uint8 takes the host path here and comes back with "image"."""
+        d, image = self._read(dataset_dict)
+        if image.dtype != np.uint8 or image.ndim != 3:
+            return self._host(d, image)
+        h, w, c = image.shape
+        aug = dict(crop=(0, 0, w, h), out_hw=(h, w), flip=False, wb=None, ws=None)
+        tfms, stage = [], 0
+        for a in self.augmentations:
+            if isinstance(a, RandomSaturation):
+                assert c == 3, "RandomSaturation only works on RGB images"
+                wgt = np.random.uniform(a.lo, a.hi)
+                t = BlendTransform(src_image=None, src_weight=1 - wgt, dst_weight=wgt)  # (the device forms the grey image)
+            else:
+                t = a.get_transform(np.broadcast_to(np.zeros((), np.uint8), (h, w, c)))  # shapes only
+            tfms.append(t)
+            if isinstance(t, NoOpTransform):
+                continue
+            # the kernel's order is fixed: crop, resize, flip, brightness, saturation
+            if isinstance(t, CropTransform):
+                at = 1
+                aug["crop"] = (int(t.x0), int(t.y0), int(t.w), int(t.h))
+                aug["out_hw"] = h, w = int(t.h), int(t.w)
+            elif isinstance(t, ResizeTransform):
+                at = 2
+                aug["out_hw"] = h, w = int(t.new_h), int(t.new_w)
+            elif isinstance(t, HFlipTransform):
+                at = 3
+                aug["flip"] = True
+            elif isinstance(t, BlendTransform) and isinstance(a, RandomBrightness):
+                at = 4
+                aug["wb"] = float(t.dst_weight)
+            elif isinstance(t, BlendTransform) and isinstance(a, RandomSaturation):
+                at = 5
+                aug["ws"] = float(t.dst_weight)
+            else:
+                raise DrnError("%s is not on the device mapper's path" % type(t).__name__)
+            if at <= stage:
+                raise DrnError("the device mapper applies crop, resize, flip, brightness, saturation in this order, once each")
+            stage = at
+        src = np.ascontiguousarray(image)
+        if not src.flags.writeable:
+            src = src.copy()
+        d["image_src"] = torch.from_numpy(src)
+        d["aug"] = aug
+        return self._boxes(d, aug["out_hw"], TransformList(tfms))
+
+    def _submit(self, planned):
+        """upload + kernel of one planned item on the mapper's stream -> (item, event recorded behind them)"""
+        from . import ops
+
+        d = dict(planned)
+        if "aug" not in d:  # (plan's host path: a non-uint8 image)
+            d["image"] = d["image"].to(self.device)
+            return d, None
+        src, aug = d.pop("image_src"), d.pop("aug")
+        dev = self.device
+        if dev.index is None:  # "cuda": the current device, from the first item on
+            dev = self.device = torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.device(dev):
+            if self._stream is None:
+                self._stream = torch.cuda.Stream(dev)
+            consumer = torch.cuda.current_stream(dev)
+            slot = self._pin_i
+            self._pin_i = (slot + 1) % self.PIN_RING
+            # ONE pinned copy per item: [x bounds | x coef | y bounds | y coef] (int32; absent where the size stays), then the image.
+            # With random crops and scales nearly every image has tables of its own: a device-side cache would miss, and each
+            # miss would cost pageable, host-blocking copies behind everything in flight on the stream.
+            (x0, y0, cw, ch), (ho, wo) = aug["crop"], aug["out_hw"]
+            parts, ks = [], []
+            for n_in, n_out in ((cw, wo), (ch, ho)):
+                b, k, s = (None, None, 0) if n_in == n_out else ops.pil_bilinear_coeffs_cached(n_in, n_out)
+                ks.append(s)
+                parts += [] if b is None else [b, k]
+            nt = 4 * sum(p.size for p in parts)
+            n = nt + src.numel()
+            if self._pin_ev[slot] is not None:
+                self._pin_ev[slot].synchronize()  # the copy that last read this buffer has left it (normally long done)
+            if self._pin[slot] is None or self._pin[slot].numel() < n:
+                self._pin[slot] = torch.empty((n + n // 4,), dtype=torch.uint8).pin_memory()
+            stage = self._pin[slot][:n]
+            host, o = stage.numpy(), 0
+            for p in parts:
+                host[o: o + 4 * p.size].view(np.int32)[:] = p.reshape(-1)
+                o += 4 * p.size
+            stage[nt:].copy_(src.reshape(-1))
+            with torch.cuda.stream(self._stream):
+                dbuf = stage.to(dev, non_blocking=True)
+                dtab, o = [], 0
+                for p in parts:
+                    dtab.append(dbuf[o: o + 4 * p.size].view(torch.int32))
+                    o += 4 * p.size
+                tx = (dtab.pop(0), dtab.pop(0), ks[0]) if ks[0] else (None, None, 0)
+                ty = (dtab.pop(0), dtab.pop(0), ks[1]) if ks[1] else (None, None, 0)
+                out = ops.augment_u8(dbuf[nt:].view(src.shape), aug["crop"], aug["out_hw"], aug["flip"], aug["wb"], aug["ws"],
+                                     tables=(tx, ty))
+                ev = torch.cuda.Event()
+                ev.record(self._stream)
+            self._pin_ev[slot] = ev
+            out.record_stream(consumer)
+        d["image"] = out
+        return d, ev
+
+    def finish(self, planned):
+        """The device half: "image_src" + "aug" of a planned item -> "image", an fp32 [C, Ho, Wo] tensor on the mapper's device
+        holding the bytes the host path produces; the two helper keys are dropped.
+
+        Stream contract.  The upload (through a ring of pinned buffers, each guarded by an event) and the kernel run on ONE
+        private stream of the mapper, an event is recorded behind them, and that event is HOST-synchronised before the item is
+        handed out: the returned image is complete for every stream, whichever reads it and however late that stream joined
+        (GraphedTrainStep's ring schedule reads staged inputs on a side stream that does not wait for the caller's).  The
+        image's memory belongs to the private stream's pool: finish() calls record_stream() for the stream current at the
+        call, and a consumer that reads the image on another stream calls image.record_stream(that stream) itself, as
+        GraphedTrainStep's staging copies do."""
+        d, ev = self._submit(planned)
+        if ev is not None:
+            ev.synchronize()
         return d
 
 
@@ -499,18 +655,54 @@ def build_batch_data_loader(dataset, sampler, total_batch_size, *, aspect_ratio_
                                        collate_fn=lambda batch: batch)
 
 
-def build_detection_train_loader(cfg, dataset_dicts, mapper=None, *, rank=None, world_size=None):
+class _DeviceFinishLoader:
+    """The main-process half of the device data path: the wrapped loader's workers ran mapper.plan; here every element of an
+    emitted batch goes through the mapper's upload + kernel, `prefetch` batches are kept in flight on the mapper's stream,
+    and a batch's events are synchronised only when that batch is yielded (DatasetMapper.finish's contract).
+    This is what build_detection_train_loader(device=...) returns INSTEAD of the DataLoader / AspectRatioGroupedDataset of the host
+    path: an iterable of batches and nothing more.  The wrapped object is `.loader` (its `dataset`, `batch_sampler`, ... live
+    there); an iterator that is abandoned leaves its submitted items unsynchronised, which is harmless (nobody holds them)."""
+
+    def __init__(self, loader, mapper, prefetch=2):
+        self.loader, self.mapper, self.prefetch = loader, mapper, int(prefetch)
+
+    def __iter__(self):
+        import collections
+
+        flight = collections.deque()
+        for batch in self.loader:
+            flight.append([self.mapper._submit(p) for p in batch])
+            if len(flight) > self.prefetch:
+                yield self._complete(flight.popleft())
+        while flight:
+            yield self._complete(flight.popleft())
+
+    @staticmethod
+    def _complete(items):
+        for _, ev in items:
+            if ev is not None:
+                ev.synchronize()
+        return [d for d, _ in items]
+
+
+def build_detection_train_loader(cfg, dataset_dicts, mapper=None, *, rank=None, world_size=None, device=None):
     """detectron2/data/build.py:299-354 without the dataset registry (out of scope: the caller passes the list of dataset
     dicts, e.g. after load_proposals_into_dataset): DatasetMapper(cfg, True) by default, TrainingSampler, batches of
-    SOLVER.IMS_PER_BATCH / W images grouped by aspect ratio (DATALOADER.ASPECT_RATIO_GROUPING)."""
+    SOLVER.IMS_PER_BATCH / W images grouped by aspect ratio (DATALOADER.ASPECT_RATIO_GROUPING).
+    With a device the loader's workers run mapper.plan only (they never touch the GPU) and this process forms the images on
+    the device: the return value is then a _DeviceFinishLoader around the host path's loader, not that loader itself; grouping
+    stays where it is, it reads width / height only."""
     if mapper is None:
-        mapper = DatasetMapper(cfg, True)
-    dataset = MapDataset(dataset_dicts, mapper)
+        mapper = DatasetMapper(cfg, True, device=device)
+    if device is not None and getattr(mapper, "device", None) is None:
+        raise DrnError("build_detection_train_loader(device=%s) needs a mapper built with a device" % (device,))
+    dataset = MapDataset(dataset_dicts, mapper if device is None else mapper.plan)
     name = cfg.DATALOADER.SAMPLER_TRAIN
     if name != "TrainingSampler":
         raise DrnError("training sampler %r is not on the WSL path (every projects/WSL yaml uses TrainingSampler)" % name)
     r, w = _rank_world(rank, world_size)
     sampler = TrainingSampler(len(dataset), rank=r, world_size=w)
-    return build_batch_data_loader(dataset, sampler, cfg.SOLVER.IMS_PER_BATCH,
-                                   aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING,
-                                   num_workers=cfg.DATALOADER.NUM_WORKERS, world_size=w)
+    loader = build_batch_data_loader(dataset, sampler, cfg.SOLVER.IMS_PER_BATCH,
+                                     aspect_ratio_grouping=cfg.DATALOADER.ASPECT_RATIO_GROUPING,
+                                     num_workers=cfg.DATALOADER.NUM_WORKERS, world_size=w)
+    return loader if device is None else _DeviceFinishLoader(loader, mapper)

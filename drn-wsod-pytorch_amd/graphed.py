@@ -232,6 +232,8 @@ class GraphedTrainStep:
     def _stage_image(self, batch, slot):
         for i, x in enumerate(batch):
             self._images[slot][i].copy_(x["image"], non_blocking=True)
+            if x["image"].is_cuda:  # (a device mapper's image lives in another stream's pool: DatasetMapper.finish)
+                x["image"].record_stream(torch.cuda.current_stream())
 
     def _backbone(self, slot=0):
         m = self.model
@@ -406,6 +408,8 @@ class GraphedTrainStep:
     def _pair_stage(self, group, ps):
         for i, x in enumerate([x for b in group for x in b]):
             self._pimages[ps][i].copy_(x["image"], non_blocking=True)
+            if x["image"].is_cuda:  # (a device mapper's image lives in another stream's pool: DatasetMapper.finish)
+                x["image"].record_stream(torch.cuda.current_stream())
 
     def _pair_bb_body(self, ps):
         with torch.no_grad():

@@ -353,6 +353,20 @@ def pil_bilinear_coeffs(in_size, out_size):
 _RESIZE_COEFFS = {}
 
 
+def _resize_tables(n_in, n_out, dev):
+    """device copies of pil_bilinear_coeffs(n_in, n_out), cached: (bounds, coef, ksize); (None, None, 0) when the size stays"""
+    if n_in == n_out:
+        return None, None, 0
+    key = (n_in, n_out, dev)
+    t = _RESIZE_COEFFS.get(key)
+    if t is None:
+        if len(_RESIZE_COEFFS) > 256:
+            _RESIZE_COEFFS.clear()
+        b, k, ks = pil_bilinear_coeffs(n_in, n_out)
+        t = _RESIZE_COEFFS[key] = (torch.from_numpy(b).to(dev), torch.from_numpy(k).to(dev), ks)
+    return t
+
+
 def resize_bilinear_u8(img_hwc, new_h, new_w, flip=False, out=None):
     """img_hwc: uint8 [H, W, C] device tensor -> fp32 [C, new_h, new_w] holding exactly the bytes
     PIL.Image.fromarray(img).resize((new_w, new_h), BILINEAR) produces (mirrored left-right when `flip`): ResizeTransform
@@ -360,26 +374,70 @@ def resize_bilinear_u8(img_hwc, new_h, new_w, flip=False, out=None):
     assert img_hwc.dtype == torch.uint8 and img_hwc.dim() == 3 and img_hwc.is_contiguous() and img_hwc.is_cuda
     h, w, c = img_hwc.shape
     dev = img_hwc.device
-
-    def tables(n_in, n_out):
-        if n_in == n_out:
-            return None, None, 0
-        key = (n_in, n_out, dev)
-        t = _RESIZE_COEFFS.get(key)
-        if t is None:
-            if len(_RESIZE_COEFFS) > 256:
-                _RESIZE_COEFFS.clear()
-            b, k, ks = pil_bilinear_coeffs(n_in, n_out)
-            t = _RESIZE_COEFFS[key] = (torch.from_numpy(b).to(dev), torch.from_numpy(k).to(dev), ks)
-        return t
-
-    xb, xk, ksx = tables(w, new_w)
-    yb, yk, ksy = tables(h, new_h)
+    xb, xk, ksx = _resize_tables(w, new_w, dev)
+    yb, yk, ksy = _resize_tables(h, new_h, dev)
     if out is None:
         out = torch.empty((c, new_h, new_w), dtype=torch.float32, device=dev)
     C.call("drn_resize_bilinear_u8", C.ptr(img_hwc), h, w, c, C.ptr(out), new_h, new_w, C.ptr(xb), C.ptr(xk), ksx, C.ptr(yb),
            C.ptr(yk), ksy, int(bool(flip)), C.stream())
     return out
+
+
+_HOST_COEFFS = {}
+
+
+def pil_bilinear_coeffs_cached(n_in, n_out):
+    """pil_bilinear_coeffs on the host, remembered (numpy arrays: nothing on the device) -> (bounds, coef, ksize)"""
+    t = _HOST_COEFFS.get((n_in, n_out))
+    if t is None:
+        if len(_HOST_COEFFS) > 1024:
+            _HOST_COEFFS.clear()
+        t = _HOST_COEFFS[(n_in, n_out)] = pil_bilinear_coeffs(n_in, n_out)
+    return t
+
+
+def augment_u8(src, crop, out_hw, flip=False, wb=None, ws=None, out=None, tables=None):
+    """The training DatasetMapper's image chain in one launch (drn_augment_u8).  src: uint8 [H, W, C] device tensor, C in
+    {1, 3, 4}; crop = (x0, y0, cw, ch) inside the image (None: the whole image); out_hw = (Ho, Wo) of the Pillow BILINEAR resize of
+    the crop; flip mirrors the columns; wb / ws are RandomBrightness' / RandomSaturation's drawn weights, None switches that
+    blend off (ws needs C == 3).  tables = ((xbounds, xcoef, ksx), (ybounds, ycoef, ksy)), int32 device tensors of
+    pil_bilinear_coeffs(cw, Wo) / (ch, Ho) with (None, None, 0) where the size stays, for a caller that uploads them itself (the
+    device mapper: one pinned copy with the image); by default they come from the _RESIZE_COEFFS cache.
+    -> fp32 [C, Ho, Wo] holding exactly the bytes the host chain CropTransform ->
+    ResizeTransform -> HFlipTransform -> BlendTransform x 2 produces (the saturation's grey value summed in index order)."""
+    assert src.dtype == torch.uint8 and src.dim() == 3 and src.is_contiguous() and src.is_cuda
+    h, w, c = src.shape
+    x0, y0, cw, ch = (0, 0, w, h) if crop is None else (int(v) for v in crop)
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    if cw <= 0 or ch <= 0 or x0 < 0 or y0 < 0 or x0 + cw > w or y0 + ch > h:
+        raise C.DrnError("augment_u8: crop (%d, %d, %d, %d) is not inside the %d x %d image" % (x0, y0, cw, ch, w, h))
+    dev = src.device
+    if tables is None:
+        xb, xk, ksx = _resize_tables(cw, wo, dev)
+        yb, yk, ksy = _resize_tables(ch, ho, dev)
+    else:
+        (xb, xk, ksx), (yb, yk, ksy) = tables
+        for b, k, ks, n_out in ((xb, xk, ksx, wo), (yb, yk, ksy, ho)):
+            assert b is None or (b.dtype == k.dtype == torch.int32 and b.numel() == 2 * n_out and k.numel() == n_out * ks
+                                 and b.is_contiguous() and k.is_contiguous())
+    if out is None:
+        out = torch.empty((c, ho, wo), dtype=torch.float32, device=dev)
+    assert out.shape == (c, ho, wo) and out.dtype == torch.float32 and out.is_contiguous()
+    C.call("drn_augment_u8", C.ptr(src), h, w, c, x0, y0, cw, ch, C.ptr(out), ho, wo, C.ptr(xb), C.ptr(xk), ksx, C.ptr(yb),
+           C.ptr(yk), ksy, int(bool(flip)), int(wb is not None), 0.0 if wb is None else float(wb), int(ws is not None),
+           0.0 if ws is None else 1 - float(ws), 0.0 if ws is None else float(ws), C.stream())
+    return out
+
+
+def augment_u8_lds_bytes(crop_wh, out_hw, c):
+    """LDS staging bytes drn_augment_u8 asks for at these sizes; 0 = the launch runs its one-thread-per-pixel path (the source
+    window of a 64 x 16 output tile does not fit: strong down-scaling).  Host arithmetic only."""
+    cw, ch = int(crop_wh[0]), int(crop_wh[1])
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    n = C.lib().drn_augment_lds_bytes(cw, ch, ho, wo, int(c), int(cw != wo), int(ch != ho))
+    if n < 0:
+        raise C.DrnError("drn_augment_lds_bytes failed (%d)" % n)
+    return int(n)
 
 
 ROI_WORKSPACE = True  # tools / tests: False = pool without the chunk-major scratch copy (same results)

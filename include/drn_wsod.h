@@ -48,6 +48,27 @@ int drn_preprocess_nhwc(const float* img_chw, int C, int H, int W, void* out_nhw
 int drn_resize_bilinear_u8(const void* src_hwc, int H, int W, int C, float* dst_chw, int Ho, int Wo, const int* xbounds,
                            const int* xcoef, int ksx, const int* ybounds, const int* ycoef, int ksy, int flip, void* stream);
 
+/* The training DatasetMapper's image chain on the device, one launch per image: DatasetMapper.__call__
+ * (detectron2/data/dataset_mapper.py:112-185) applies, to the decoded 8-bit image, fvcore's CropTransform (RandomCrop,
+ * detectron2/data/transforms/augmentation_impl.py:232-281), ResizeTransform.apply_image
+ * (detectron2/data/transforms/transform.py:101-122: PIL.Image.resize(size, BILINEAR)), fvcore's HFlipTransform and two
+ * fvcore BlendTransforms (RandomBrightness / RandomSaturation, augmentation_impl.py:403-455).  fvcore and Pillow are
+ * un-vendored dependencies of the reference; their published semantics are restated.
+ * src_hwc uint8 [H][W][C], C in {1, 3, 4}; the crop window (x0, y0, cw, ch) must lie inside the image; the tables are those of
+ * drn_resize_bilinear_u8 for cw -> Wo and ch -> Ho (DEVICE pointers; NULL skips that pass and its size must not change).
+ * Per output pixel, op for op: R = the two-pass integer resample of the crop; the pixel goes to column Wo - 1 - x when flip;
+ * brightness_on: B = (uint8) min(max(wb * (float) R, 0), 255), a float32 product, truncated; saturation_on (C == 3 only, else
+ * DRN_ERR_ARG): g = ((double) B0 * 0.299 + (double) B1 * 0.587) + (double) B2 * 0.114 by channel index, uncontracted, and
+ * out_c = (uint8) min(max(one_minus_ws * g + (double) (ws * (float) B_c), 0), 255), truncated; one_minus_ws is the host's
+ * double 1 - w.  dst_chw fp32 [C][Ho][Wo] holding the integers 0 .. 255.  No byte outside [src, src + H*W*C) is read. */
+int drn_augment_u8(const void* src_hwc, int H, int W, int C, int x0, int y0, int cw, int ch, float* dst_chw, int Ho, int Wo,
+                   const int* xbounds, const int* xcoef, int ksx, const int* ybounds, const int* ycoef, int ksy, int flip,
+                   int brightness_on, float wb, int saturation_on, double one_minus_ws, float ws, void* stream);
+/* Host-side query, no launch: the LDS staging bytes drn_augment_u8 asks for at these sizes (xpass / ypass: whether that
+ * direction has tables); 0 = the tile windows are too large to stage and the launch runs its one-thread-per-pixel path
+ * (same bits).  Negative: invalid argument. */
+long drn_augment_lds_bytes(int cw, int ch, int Ho, int Wo, int C, int xpass, int ypass);
+
 /* Conv2d.forward = F.conv2d -> FrozenBatchNorm2d -> relu_ [+ residual add before the relu],
  * detectron2/layers/wrappers.py:94-99, detectron2/layers/batch_norm.py:45-65,
  * projects/WSL/wsl/modeling/backbone/resnet_ws.py:217-237, vgg.py:104-122.
