@@ -4,8 +4,13 @@
                      batches on a side stream, pooling piece + fc6 forward + fc6 weight-gradient tail issued eagerly around it
                      (bench.py's step)
   GraphedFullStep    trainable trunk: forward, losses, backward, optimizer as one graph (two with a gradient exchange between)
+Both stage their inputs into the static buffers of _StaticInputs.  ahead_schedule() is the slot arithmetic of the frozen-trunk
+step: no torch in it, tests/test_schedule_cpu.py simulates it.
 
 Split out of engine.py in round 5; `engine` re-exports both names."""
+
+import weakref
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -14,66 +19,48 @@ from . import ops
 from ._cabi import DrnError
 
 
-class GraphedTrainStep:
-    """One training step as three hipGraphs captured once and replayed: a step is ~100 kernel launches of 2-450 us, so
-    the eager Python host needs ~2.4 ms to enqueue what the GPU executes in ~2.1 ms; a replay costs the host ~9 us per
-    node and nothing else.
+class Ahead(NamedTuple):
+    """what step t of the ahead schedule touches (ahead_schedule)"""
+    launch: Optional[int]  # trunk slot the conv chain launched at this step writes; None: no chain starts at this step
+    stage: slice           # the batches of that chain, as a slice of step()'s `upcoming` (upcoming[0] is batch t+2)
+    pool_slot: int         # the pooling at the end of the step (batch t+1) reads this trunk slot ...
+    pool_part: int         # ... and this batch of the slot's group
+    nb: int                # staging set the step stages batch t+1 into, and its pooling reads
 
-      g_main (main stream) : heads forward (fc6 GEMM first, on the pooled operand prepared by the PREVIOUS step), MIL /
-                             OICR losses, explicit backward up to the fc6 weight gradient
-      tail   (eager)       : fc6 dW row-slab GEMMs on the main stream; per bucket, (all-reduce +) SGD on the optimizer
-                             stream (`split_tail`, the default of bench.py; with split_tail=False the tail is part of
-                             g_main - measured 1.3 % slower, the executor schedules forked branches late)
-      g_bb   (side stream) : preprocess + frozen backbone of the NEXT batch's image (latency-bound convs under the GEMMs)
-      g_pool (main stream) : ROIPool(+objectness) -> A and A^T of the next batch, behind this step's last reader of A^T
-    One buffer set suffices.  Legal because every shipped config freezes the whole backbone (FREEZE_AT=5).
 
-    lookahead=2 (bench.py's default): measured with HIP events, the conv chain of ONE image takes ~1.7 ms beside the
-    GEMMs (0.6 ms alone) and the main stream idled 0.26 ms per step waiting for it.  With two feature buffers / image
-    staging sets the trunk of batch t+2 runs during step t (two graphs per piece, one per slot), so the pooling graph of
-    batch t+1 never waits; `step()` then takes the batch two steps ahead as a third argument (only its images are read).
+def ahead_arity(G, A):
+    """how many batches step() takes after next_batch: up to the last one of the group launched A groups ahead (it depends on
+    neither t nor P, and step() checks it before P is settled)"""
+    return A * G + G - 2
 
-    Static shapes only (fixed image size, proposals per image, images per GPU: the benchmark's case and the common
-    fixed-R training case); anything else runs the eager path.
 
-    N > 1 (`split_tail`): the captured heads graph stops in front of the fc6 weight-gradient GEMMs.  That tail - the
-    announcement of the small gradients, the dW row-slab GEMMs and, from the optimizer's hooks, one RCCL all-reduce +
-    SGD launch per bucket on the optimizer stream - is issued eagerly after the replay (~10 launches), so no
-    collective is ever captured into a hipGraph, while the next image's backbone graph and pooling graph run under
-    the exchange.  The optimizer stream is joined at the start of the next step."""
+def ahead_schedule(t, G, A, P, sets=1):
+    """The side-stream schedule of GraphedTrainStep at step t: one conv chain per group of G consecutive batches, launched A groups
+    ahead (on the steps with t % G == 0), group q living in trunk slot q % P; `sets` staging sets for proposals / labels (A G >= 2).
+      lookahead=L    is (G, A, P) = (1, L, L);
+      trunk_pairs=G  is (G, 1, 2), and (G, 1, RING_SLOTS) with RING_SETS staging sets under the ring.
+    The chain launched at step t is that of group t // G + A = batches t + A G .. t + A G + G - 1; the pooling at the end of step t
+    is that of batch t + 1, part (t + 1) % G of group (t + 1) // G."""
+    lo = A * G - 2
+    return Ahead((t // G + A) % P if t % G == 0 else None, slice(lo, lo + G), ((t + 1) // G) % P, (t + 1) % G, (t + 1) % sets)
 
-    _needs_frozen_trunk = True
 
-    def __init__(self, model, optimizer, example_batch, split_tail=False, lookahead=1, trunk_pairs=False,
-                 eager_fc6=False, stage_ahead=True, ring=True, start_iter=0):
+def _captured(body, *args):
+    """-> (hipGraph of body(*args), what body returned).  thread_local: with N > 1 the RCCL watchdog thread polls its events while
+    we capture; only this thread's calls belong to the capture"""
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        out = body(*args)
+    return g, out
+
+
+class _StaticInputs:
+    """What both graphed steps share: the static device buffers a captured graph reads its inputs from (proposals, objectness,
+    image-level labels, images) and the staging of labels and images into them."""
+
+    def __init__(self, model, optimizer, example_batch):
         if getattr(model, "cpg", False):
             raise DrnError("CSCROIHeads decides per step, on the host, which class maps to compute: eager steps only")
-        if self._needs_frozen_trunk and any(p.requires_grad for p in model.backbone.parameters()):
-            raise DrnError("GraphedTrainStep runs the trunk of FUTURE batches on a side stream, which needs a frozen "
-                           "backbone (FREEZE_AT = 5); use GraphedFullStep for a trainable trunk")
-        assert 1 <= lookahead <= 4
-        self.lookahead = lookahead
-        # eager_fc6 (bench.py): the fc6 forward GEMM - first launch of the heads and the step's dominant kernel - is
-        # issued eagerly in front of the captured heads graph, like the fc6 dW tail behind it, so HIP events on the
-        # launch stream can bracket it inside the timed region (ops.GEMM_TIMING)
-        self.eager_fc6 = bool(eager_fc6)
-        # stage_ahead: the next batch's labels are staged behind this step's heads graph and its proposals on the side
-        # stream (False = the round-2 order, kept for A/B runs: proposals in front of the pooling graph on the main
-        # stream, labels at the start of their own step, i.e. between the pooling kernel and the fc6 forward)
-        self.stage_ahead = bool(stage_ahead)
-        # (lookahead >= 2 / trunk groups) the pooling piece - one staging launch + the pooling kernel - is issued eagerly: a
-        # graph's hand-over to the next launch costs more than an eager launch gap (+0.65 %, profiles/r2_39_eager_pool_ab.txt;
-        # the graphed form of the piece was removed in round 5)
-        # trunk_pairs: ONE conv chain per TWO batches (t+2 and t+3, launched on even steps): the chain is latency-bound,
-        # so two images cost what one costs and the per-image chain time halves - for trunks whose chain is as long as
-        # the step (WS-R101).  step() then takes (batch, next, t+2, t+3).
-        self.trunk_pairs = bool(trunk_pairs)
-        # (round 4) an int G > 2 generalises the pair to a GROUP of G batches per conv chain, launched every G-th step for
-        # batches t+G .. t+2G-1: trunks whose chain is longer than TWO steps (WS-R101: ~100 launches, 0.7 ms of every 1.5-ms
-        # step spent waiting for it) get G steps per chain.  step() then takes batches t .. t+2G-1.
-        self.G = (2 if trunk_pairs is True else int(trunk_pairs)) if trunk_pairs else 0
-        if self.trunk_pairs and self.G < 2:
-            raise DrnError("trunk_pairs: True (two batches per conv chain) or an int >= 2")
         self.model, self.opt = model, optimizer
         self.heads = model.roi_heads
         self.engine = self.heads._engine
@@ -83,92 +70,30 @@ class GraphedTrainStep:
         n_img, M = len(example_batch), sum(self.nper)
         self.n_img, self.K = n_img, K
         self.image = [x["image"].to(dev).float().clone() for x in example_batch]
-        # lookahead 2: the trunk of batch t+2 runs during step t into the feature buffer batch t no longer needs, so the
-        # conv chain (0.6 ms alone, ~1.7 ms beside the GEMMs) has two steps to finish instead of one
-        # lookahead L >= 2: L slots; with L >= 3 the chains alternate over L-1 side streams, i.e. L-1 conv chains are in
-        # flight at once and each may take L-1 steps - for trunks whose chain is longer than the step (WS-R101: ~100 launches)
-        self._images = [self.image] + [[im.clone() for im in self.image] for _ in range(lookahead - 1)]
-        self._feats = [None] * max(lookahead, 2)
-        self._bb_done = [None] * max(lookahead, 2)
-        self._t = 0
-        off = [0]
+        self._images = [self.image]  # image sets by trunk slot (the ahead schedule of GraphedTrainStep allocates its own)
+        self._off = [0]
         for n in self.nper:
-            off.append(off[-1] + n)
-        mk = lambda: torch.zeros((M, 5), dtype=torch.float32, device=dev)
-        # Proposals / objectness / labels of the NEXT batch are staged on the side stream and read by the pooling piece at the end
-        # of the step.  RING (round 6, trunk groups on one GPU): RING_SETS staging sets and RING_SLOTS trunk-feature slots, and
-        # the side stream does NOT wait for the main stream at all - any such wait, even on an event that completed two steps
-        # ago, costs ~1 % of the step (profiles/r6_40_side_wait_experiments.txt).  What a wait guaranteed - the previous reader of
-        # a set / slot is done before the side stream overwrites it - the HOST guarantees instead: before it enqueues step t it
-        # waits (a no-op in steady state: it runs ~1 step ahead) for the event the optimizer stream already waits on, recorded
-        # behind the heads of step t - RING_LAG.  Set (t + 1) % RING_SETS was last read at the end of step t - RING_SETS, trunk slot
-        # q % RING_SLOTS by the pooling launches of group q - RING_SLOTS (the last at the end of step t + 2G - 2 - G RING_SLOTS):
-        # both in front of heads(t - RING_LAG) when RING_SETS >= RING_LAG + 1 and G RING_SLOTS >= 2G - 1 + RING_LAG.
-        self.RING_LAG, self.RING_SETS, self.RING_SLOTS = 3, 4, 3
-        self.rois, self._rois_nb = mk(), [mk() for _ in range(self.RING_SETS)]
-        for t in [self.rois] + self._rois_nb:
-            for i in range(n_img):
-                t[off[i]: off[i + 1], 0] = float(i)
+            self._off.append(self._off[-1] + n)
+        self.rois = self._new_rois()
         self.obj = torch.zeros((M,), dtype=torch.float32, device=dev)
-        self._obj_nb = [torch.zeros((M,), dtype=torch.float32, device=dev) for _ in range(self.RING_SETS)]
-        self._ring_want = bool(ring)  # (False: the side stream waits for the main stream at the start of every step, as before round 6)
-        self._ring_on = False  # (set by _prime_pairs)
-        self._nb = 0          # the staging set in use (0 for every schedule but the ring)
-        self._ring_evs = []   # events behind the heads of the last steps (oldest first)
         self.props = torch.zeros((M, 4), dtype=torch.float32, device=dev)
         # image-level labels live in ONE device block (one H2D copy per step): [onehot f32 | classes i32 | count i32]
         self._gt_block = torch.zeros((2 * n_img * K + n_img,), dtype=torch.int32, device=dev)
-        # labels of the NEXT batch land here (H2D on the side stream); the pooling graph moves them into the block the
-        # heads graph reads - a node inside a graph instead of an eager copy with two launch gaps on the main stream
-        self._gt_nb = [torch.zeros_like(self._gt_block) for _ in range(self.RING_SETS)]
         nk = n_img * K
         self.gt = dict(onehot=self._gt_block[:nk].view(torch.float32).view(n_img, K),
                        classes=self._gt_block[nk: 2 * nk].view(n_img, K), count=self._gt_block[2 * nk:],
                        props=self.props, max_rows=max(self.nper))
-        self.img_off = torch.tensor(off, dtype=torch.int32, device=dev)
+        self.img_off = torch.tensor(self._off, dtype=torch.int32, device=dev)
         self.losses = None
-        self._side = torch.cuda.Stream()
-        self._primed = False
-        self.split_tail = bool(split_tail)
-        # WSL.ITER_SIZE = N > 1 (the pipelined optimizer's iter_size): the captured heads graph back-propagates loss / N with
-        # the small tensors' accumulate flags on, and is the same for every micro-iteration; what differs by window position -
-        # where the fc6 weight gradient goes, whether the optimizer stream gets work, whether the step ends with opt.step() -
-        # is the eager tail, so the tail is always split off.  Micro-iterations count from start_iter (a resumed run).
-        self.iter_size = int(getattr(optimizer, "iter_size", 1))
-        self._iter = int(start_iter)
-        self._start_iter = int(start_iter)
-        if self.iter_size > 1:
-            if not getattr(optimizer, "_pipelined", False):
-                raise DrnError("GraphedTrainStep with WSL.ITER_SIZE > 1 needs FusedSGD.enable_pipelined(iter_size=N)")
-            self.split_tail = True
-        if self.engine.kshard is not None and not (self.split_tail and self.eager_fc6 and (lookahead >= 2 or trunk_pairs)):
-            raise DrnError("K-sharded fc6 holds collectives in the pooling piece, behind the fc6 GEMM and in the dW tail: "
-                           "GraphedTrainStep(split_tail=True, eager_fc6=True, lookahead >= 2 or trunk_pairs)")
-        self.engine.defer_fc1_tail = self.split_tail
         self.engine.pool_sets_pinned = None  # a new step captures anew: the previous owner's pin (if any) is void
         self.engine.pool_sets_pin_owner = None
 
-    def release(self):
-        """give the fc6 operand sets back (they may grow again); the captured graphs of this object must not be replayed
-        afterwards"""
-        own = getattr(self.engine, "pool_sets_pin_owner", None)
-        if own is not None and own() is self:
-            self.engine.pool_sets_pinned = None
-            self.engine.pool_sets_pin_owner = None
-        self._primed = False
-
-    # ---- host side of one step: stage inputs into the static buffers (tiny async copies) -----------------------
-    @property
-    def rois_next(self):
-        return self._rois_nb[self._nb]
-
-    @property
-    def obj_next(self):
-        return self._obj_nb[self._nb]
-
-    @property
-    def _gt_stage(self):
-        return self._gt_nb[self._nb]
+    def _new_rois(self):
+        """[M, 5] rows (image index, box): the index column is written once, here"""
+        t = torch.zeros((self._off[-1], 5), dtype=torch.float32, device=self.model.device)
+        for i in range(self.n_img):
+            t[self._off[i]: self._off[i + 1], 0] = float(i)
+        return t
 
     def _stage_labels(self, batch, dst=None):
         """Image-level labels of the CURRENT batch.  They are built on the host and go through a ring of PINNED
@@ -195,10 +120,152 @@ class GraphedTrainStep:
         slot["ev"] = torch.cuda.Event()
         slot["ev"].record()
 
+    def _stage_image(self, items, slot):
+        """images of `items` (one batch, or the batches of a group end to end) -> the image set of a trunk slot"""
+        for i, x in enumerate(items):
+            self._images[slot][i].copy_(x["image"], non_blocking=True)
+            if x["image"].is_cuda:  # (a device mapper's image lives in another stream's pool: DatasetMapper.finish)
+                x["image"].record_stream(torch.cuda.current_stream())
+
+    @property
+    def last_state(self):
+        """intermediate values (MIL scores, image scores, pseudo-GT rows, labels) of the step that ran last"""
+        return self._captured_state if getattr(self, "_replayed", False) else self._eager_state
+
+    def _keep_state(self, st):
+        # static buffers: after a replay the CAPTURED state holds that step's MIL scores / pseudo-GT / labels; the priming
+        # step ran eagerly (its state is the one built before the capture)
+        if torch.cuda.is_current_stream_capturing():
+            self._captured_state = st
+        else:
+            self._eager_state = st
+
+
+class GraphedTrainStep(_StaticInputs):
+    """One training step as hipGraphs captured once and replayed: a step is ~100 kernel launches of 2-450 us, so
+    the eager Python host needs ~2.4 ms to enqueue what the GPU executes in ~2.1 ms; a replay costs the host ~9 us per
+    node and nothing else.
+
+      g_main (main stream) : heads forward (fc6 GEMM first, on the pooled operand prepared by the PREVIOUS step), MIL /
+                             OICR losses, explicit backward up to the fc6 weight gradient
+      tail   (eager)       : fc6 dW row-slab GEMMs on the main stream; per bucket, (all-reduce +) SGD on the optimizer
+                             stream (`split_tail`, the default of bench.py; with split_tail=False the tail is part of
+                             g_main - measured 1.3 % slower, the executor schedules forked branches late)
+      trunk  (side stream) : preprocess + frozen backbone of FUTURE batches (latency-bound convs under the GEMMs), one graph per slot
+      pool   (main stream) : ROIPool(+objectness) -> A and A^T of the next batch, behind this step's last reader of A^T
+    Legal because every shipped config freezes the whole backbone (FREEZE_AT=5).
+
+    Two schedules.  lookahead=1 (_run): g_bb runs the trunk of the NEXT batch into feat_next during the step and the captured g_pool
+    pools it; one buffer set suffices.  Everything else is the AHEAD schedule (_run_ahead) at parameters (G, A, P) - one conv chain
+    per group of G batches, launched A groups ahead into one of P trunk slots (g_pbb: one graph per slot); ahead_schedule() is its
+    whole index arithmetic, and tests/test_schedule_cpu.py shows by simulation that no slot or staging set is overwritten before
+    its last reader ran:
+      lookahead=L >= 2  (1, L, L) on L-1 alternating side streams: measured with HIP events, the conv chain of ONE image takes
+                        ~1.7 ms beside the GEMMs (0.6 ms alone) and the main stream idled 0.26 ms per step waiting for it; with the
+                        trunk of batch t+L running during step t the pooling of batch t+1 never waits, L-1 chains are in flight at
+                        once and each may take L-1 steps.  step(batch, next_batch, batches t+2 .. t+L): only their images are read.
+      trunk_pairs=G     (G, 1, 2) on one side stream (True = 2): the chain is latency-bound, so G images cost what one costs and the
+                        per-image chain time shrinks G-fold - for trunks whose chain is as long as the step or longer (WS-R101: ~100
+                        launches, 0.7 ms of every 1.5-ms step spent waiting for it).  step() takes batches t .. t+2G-1.
+      the RING          (G, 1, RING_SLOTS) with RING_SETS staging sets (round 6; trunk groups on one GPU with the split tail and the
+                        pipelined optimizer's hook, ring=True): the side stream does NOT wait for the main stream at all - any such
+                        wait, even on an event that completed two steps ago, costs ~1 % of the step
+                        (profiles/r6_40_side_wait_experiments.txt).  What the wait guaranteed - the previous reader of a set / slot
+                        is done before the side stream overwrites it - the HOST guarantees instead: before it enqueues step t it
+                        waits (a no-op in steady state: it runs ~1 step ahead) for the event the optimizer stream already waits on,
+                        recorded behind the heads of step t - RING_LAG.
+    The pooling piece of the ahead schedule - one staging launch + the pooling kernel - is issued eagerly: a graph's hand-over to the
+    next launch costs more than an eager launch gap (+0.65 %, profiles/r2_39_eager_pool_ab.txt).
+
+    Static shapes only (fixed image size, proposals per image, images per GPU: the benchmark's case and the common
+    fixed-R training case); anything else runs the eager path.
+
+    N > 1 (`split_tail`): the captured heads graph stops in front of the fc6 weight-gradient GEMMs.  That tail - the
+    announcement of the small gradients, the dW row-slab GEMMs and, from the optimizer's hooks, one RCCL all-reduce +
+    SGD launch per bucket on the optimizer stream - is issued eagerly after the replay (~10 launches), so no
+    collective is ever captured into a hipGraph, while the next image's backbone graph and pooling graph run under
+    the exchange.  The optimizer stream is joined at the start of the next step."""
+
+    RING_LAG, RING_SETS, RING_SLOTS = 3, 4, 3
+
+    def __init__(self, model, optimizer, example_batch, split_tail=False, lookahead=1, trunk_pairs=False,
+                 eager_fc6=False, stage_ahead=True, ring=True, start_iter=0):
+        super().__init__(model, optimizer, example_batch)
+        if any(p.requires_grad for p in model.backbone.parameters()):
+            raise DrnError("GraphedTrainStep runs the trunk of FUTURE batches on a side stream, which needs a frozen "
+                           "backbone (FREEZE_AT = 5); use GraphedFullStep for a trainable trunk")
+        assert 1 <= lookahead <= 4
+        self.lookahead = lookahead
+        # eager_fc6 (bench.py): the fc6 forward GEMM - first launch of the heads and the step's dominant kernel - is
+        # issued eagerly in front of the captured heads graph, like the fc6 dW tail behind it, so HIP events on the
+        # launch stream can bracket it inside the timed region (ops.GEMM_TIMING)
+        self.eager_fc6 = bool(eager_fc6)
+        # stage_ahead: the next batch's labels are staged behind this step's heads graph and its proposals on the side
+        # stream (False = the round-2 order, kept for A/B runs: proposals in front of the pooling graph on the main
+        # stream, labels at the start of their own step, i.e. between the pooling kernel and the fc6 forward)
+        self.stage_ahead = bool(stage_ahead)
+        self.trunk_pairs = bool(trunk_pairs)
+        self.G = (2 if trunk_pairs is True else int(trunk_pairs)) if trunk_pairs else 0
+        if self.trunk_pairs and self.G < 2:
+            raise DrnError("trunk_pairs: True (two batches per conv chain) or an int >= 2")
+        # (G, A) of the ahead schedule; None: lookahead=1.  P and the ring are settled at priming (_prime_ahead)
+        self._GA = (self.G, 1) if self.trunk_pairs else (1, lookahead) if lookahead >= 2 else None
+        self._t = 0
+        # Proposals / objectness / labels of the NEXT batch are staged on the side stream (the labels by an H2D copy) and read by
+        # the pooling piece at the end of the step, which hands boxes and labels on to the buffers the heads graph reads - a node
+        # inside a graph / one launch instead of eager copies with launch gaps on the main stream.  One set, RING_SETS under the ring
+        self._rois_nb = [self._new_rois() for _ in range(self.RING_SETS)]
+        self._obj_nb = [torch.zeros_like(self.obj) for _ in range(self.RING_SETS)]
+        self._gt_nb = [torch.zeros_like(self._gt_block) for _ in range(self.RING_SETS)]
+        self._ring_want = bool(ring)  # (False: the side stream waits for the main stream at the start of every step, as before round 6)
+        self._ring_on = False  # (set by _prime_ahead)
+        self._nb = 0          # the staging set in use (0 for every schedule but the ring)
+        self._ring_evs = []   # events behind the heads of the last steps (oldest first)
+        self._side = torch.cuda.Stream()
+        self._primed = False
+        self.split_tail = bool(split_tail)
+        # WSL.ITER_SIZE = N > 1 (the pipelined optimizer's iter_size): the captured heads graph back-propagates loss / N with
+        # the small tensors' accumulate flags on, and is the same for every micro-iteration; what differs by window position -
+        # where the fc6 weight gradient goes, whether the optimizer stream gets work, whether the step ends with opt.step() -
+        # is the eager tail, so the tail is always split off.  Micro-iterations count from start_iter (a resumed run).
+        self.iter_size = int(getattr(optimizer, "iter_size", 1))
+        self._iter = int(start_iter)
+        self._start_iter = int(start_iter)
+        if self.iter_size > 1:
+            if not getattr(optimizer, "_pipelined", False):
+                raise DrnError("GraphedTrainStep with WSL.ITER_SIZE > 1 needs FusedSGD.enable_pipelined(iter_size=N)")
+            self.split_tail = True
+        if self.engine.kshard is not None and not (self.split_tail and self.eager_fc6 and (lookahead >= 2 or trunk_pairs)):
+            raise DrnError("K-sharded fc6 holds collectives in the pooling piece, behind the fc6 GEMM and in the dW tail: "
+                           "GraphedTrainStep(split_tail=True, eager_fc6=True, lookahead >= 2 or trunk_pairs)")
+        self.engine.defer_fc1_tail = self.split_tail
+
+    def release(self):
+        """give the fc6 operand sets back (they may grow again); the captured graphs of this object must not be replayed
+        afterwards"""
+        own = getattr(self.engine, "pool_sets_pin_owner", None)
+        if own is not None and own() is self:
+            self.engine.pool_sets_pinned = None
+            self.engine.pool_sets_pin_owner = None
+        self._primed = False
+
+    # ---- host side of one step: stage inputs into the static buffers (tiny async copies) -----------------------
+    @property
+    def rois_next(self):
+        return self._rois_nb[self._nb]
+
+    @property
+    def obj_next(self):
+        return self._obj_nb[self._nb]
+
+    @property
+    def _gt_stage(self):
+        return self._gt_nb[self._nb]
+
     def _stage_labels_ahead(self, next_batch, via_stage=False):
         """Labels of the NEXT batch, issued during this step instead of at the start of their own (where a 4-us H2D copy
-        and its two launch gaps sat between the pooling kernel and the fc6 forward).  via_stage (lookahead >= 2 / pairs,
-        called on the side stream next to the proposals): into `_gt_stage`, from where the pooling graph - which runs
+        and its two launch gaps sat between the pooling kernel and the fc6 forward).  via_stage (the ahead schedule,
+        called on the side stream next to the proposals): into `_gt_stage`, from where the pooling piece - which runs
         behind this step's heads graph, the label block's reader - copies them into the block; otherwise straight into
         the block on the current stream, behind the heads graph.  step() skips its own staging when it is handed this
         very batch."""
@@ -229,12 +296,7 @@ class GraphedTrainStep:
                     src.record_stream(torch.cuda.current_stream())
             off += n
 
-    def _stage_image(self, batch, slot):
-        for i, x in enumerate(batch):
-            self._images[slot][i].copy_(x["image"], non_blocking=True)
-            if x["image"].is_cuda:  # (a device mapper's image lives in another stream's pool: DatasetMapper.finish)
-                x["image"].record_stream(torch.cuda.current_stream())
-
+    # ---- the pieces of a trunk slot (lookahead=1: slot 0 = the staged image set and feat_next) ------------------------------------
     def _backbone(self, slot=0):
         m = self.model
         imgs = m.preprocess_image([{"image": im} for im in self._images[slot]])
@@ -243,21 +305,28 @@ class GraphedTrainStep:
         assert f.is_contiguous()
         return f
 
-    def _pool_next(self, slot=None):
-        """pooled fc6 operand (A, A^T) of the staged next batch + hand its proposals over to the heads"""
-        feat = self.feat_next if slot is None else self._feats[slot]
-        # the heads only need the pooled operand and the proposal boxes (pseudo-GT mining / IoU labelling) of a batch; the
-        # small copy goes IN FRONT of the pooling kernel (its last reader, the previous heads graph, is long done) so that
-        # nothing sits between the pooling and the fc6 forward
-        # one launch: proposal boxes -> props, and (lookahead >= 2) the next batch's labels, staged on the side stream
-        # (_stage_labels_ahead), -> the label block
-        via = slot is not None and self.stage_ahead
-        ops.stage_heads_inputs(self.rois_next, self.props, self._gt_stage if via else None, self._gt_block if via else None)
-        if self.engine.kshard is not None:  # K-sharded fc6: this rank's channel slice of every rank's image (collectives, eager)
-            self.pooled = self.engine.pool_kshard(feat, self.rois_next, self.obj_next)
-            return
-        self.pooled = self.engine.pool(feat, self.rois_next, self.obj_next, True, slot=0)
-        self._check_pooled()
+    def _bb_body(self, slot=0):
+        with torch.no_grad():
+            self._feats[slot].copy_(self._backbone(slot))
+
+    def _pool_body(self, slot=0, part=0):
+        """pooled fc6 operand (A, A^T) of the staged next batch - batch `part` of the slot's group - + hand its proposals over to
+        the heads"""
+        n = self.n_img
+        feat = self._feats[slot][part * n: (part + 1) * n]
+        via = self._GA is not None and self.stage_ahead
+        with torch.no_grad():
+            # the heads only need the pooled operand and the proposal boxes (pseudo-GT mining / IoU labelling) of a batch; the
+            # small copy goes IN FRONT of the pooling kernel (its last reader, the previous heads graph, is long done) so that
+            # nothing sits between the pooling and the fc6 forward
+            # one launch: proposal boxes -> props, and (via: the ahead schedule) the next batch's labels, staged on the side stream
+            # (_stage_labels_ahead), -> the label block
+            ops.stage_heads_inputs(self.rois_next, self.props, self._gt_stage if via else None, self._gt_block if via else None)
+            if self.engine.kshard is not None:  # K-sharded fc6: this rank's channel slice of every rank's image (collectives, eager)
+                self.pooled = self.engine.pool_kshard(feat, self.rois_next, self.obj_next)
+                return
+            self.pooled = self.engine.pool(feat, self.rois_next, self.obj_next, True, slot=0)
+            self._check_pooled()
 
     def _check_pooled(self):
         """The captured heads graph reads the fc6 operand pair (A, A^T) at the addresses it saw when it was captured; the
@@ -268,8 +337,6 @@ class GraphedTrainStep:
         if not getattr(self, "_primed", False):
             self._pool_ptrs = ptrs
             self.engine.pool_sets_pinned = (self.pooled["A"].dtype, True)
-            import weakref
-
             # the pin belongs to THIS step object: it lapses when the object dies or another step is built on the model
             # (it used to outlive its owner and made the re-creation the error message asks for fail)
             self.engine.pool_sets_pin_owner = weakref.ref(self)
@@ -277,19 +344,7 @@ class GraphedTrainStep:
             raise DrnError("the fc6 operand buffers moved after the step was captured (%s -> %s): re-create the "
                            "GraphedTrainStep" % (self._pool_ptrs, ptrs))
 
-    # ---- the three captured pieces ---------------------------------------------------------------------------
-    def _bb_body(self, slot=None):
-        with torch.no_grad():
-            if slot is None:
-                self.feat_next.copy_(self._backbone())
-            else:
-                self._feats[slot].copy_(self._backbone(slot))
-
-    @property
-    def last_state(self):
-        """intermediate values (MIL scores, image scores, pseudo-GT rows, labels) of the step that ran last"""
-        return self._captured_state if getattr(self, "_replayed", False) else self._eager_state
-
+    # ---- the heads -----------------------------------------------------------------------------------------------
     def _heads(self, eager):
         """fc6 forward (eager, when timed) + the heads graph of the current batch on the current stream"""
         self._fc6_eager()
@@ -302,12 +357,7 @@ class GraphedTrainStep:
     def _main_body(self):
         losses, st = self.engine.forward(None, self.rois, self.obj, True, self.img_off, self.n_img, self.gt,
                                          pooled=self.pooled, fc6_part=self._fc6_part if self.eager_fc6 else None)
-        # static buffers: after a replay the CAPTURED state holds that step's MIL scores / pseudo-GT / labels; the priming
-        # step ran eagerly (its state is the one built before the capture)
-        if torch.cuda.is_current_stream_capturing():
-            self._captured_state = st
-        else:
-            self._eager_state = st
+        self._keep_state(st)
         # = sum(losses.values()).backward() without autograd's scalar adds / ones / stack launches
         # (ITER_SIZE N > 1: the common upstream gradient is 1 / N, train_net.py:100-107)
         self.engine.backward(st, None if self.iter_size == 1 else 1.0 / self.iter_size)   # pipelined SGD buckets fork onto the optimizer stream in here
@@ -321,131 +371,26 @@ class GraphedTrainStep:
         if self.iter_size == 1 or self._win.closing:
             self.opt.step(1.0)
 
-    def _pool_body(self, slot=None):
-        with torch.no_grad():
-            self._pool_next(slot)
-
-    # ---- lookahead L >= 2 -----------------------------------------------------------------------------------
-    def _run2(self, eager, next_batch, far_batch):
-        """Step t with the trunk L batches ahead.  Batch j lives in slot j % L (image staging set + feature buffer).
-          side : image of batch t+L -> its slot, backbone graph of that slot (the slot's last reader, the pooling of batch t,
-                 finished with the previous call: one wait on the main stream orders it); L-1 side streams take turns
-          main : heads graph of batch t (+ eager tail), proposals of batch t+1, wait for the trunk of batch t+1 (launched
-                 L-1 calls ago), pooling graph of its slot"""
-        main = torch.cuda.current_stream()
-        L = self.lookahead
-        t = self._t
-        s1, sL = (t + 1) % L, (t + L) % L
-        side = self._sides[t % (L - 1)]
-        side.wait_stream(main)
-        losses = self._heads(eager)
-        if self.split_tail:
-            self.engine.run_fc1_tail()
-        with torch.cuda.stream(side):
-            evp = None
-            if self.stage_ahead:
-                self._stage_props(next_batch)  # in front of the conv chain, off the main stream (see _run_pairs)
-                self._stage_labels_ahead(next_batch, via_stage=True)
-                evp = torch.cuda.Event()
-                evp.record(side)
-            self._stage_image(far_batch, sL)
-            self._bb_body(sL) if eager else self.g_bb2[sL].replay()
-            ev = torch.cuda.Event()
-            ev.record(side)
-        if evp is not None:
-            main.wait_event(evp)
-        else:
-            self._stage_props(next_batch)
-        main.wait_event(self._bb_done[s1])
-        self._bb_done[sL] = ev
-        self._pool_body(s1)
-        if self.split_tail:
-            self._opt_step()
-        self._t = t + 1
-        return losses
-
-    def _prime2(self, first_batch, next_batch, upcoming):
-        """upcoming = [batch t+2, ..., batch t+L] (only their images are read)"""
-        self.heads.train()
-        main = torch.cuda.current_stream()
-        L = self.lookahead
-        self._sides = [self._side] + [torch.cuda.Stream() for _ in range(L - 2)]
-        ahead = [next_batch] + list(upcoming[:-1])  # batches 1 .. L-1: their trunks run here, eagerly
-        with torch.no_grad():
-            self._stage_image(first_batch, 0)
-            self._feats[0] = self._backbone(0).clone()
-            self._stage_props(first_batch)
-            self._pool_next(0)
-            for j, b in enumerate(ahead, start=1):
-                self._stage_image(b, j)
-                self._feats[j] = self._backbone(j).clone()
-                self._bb_done[j] = torch.cuda.Event()
-                self._bb_done[j].record(main)
-        self._stage_labels(first_batch)
-        self.opt.zero_grad()
-        self._t = 0
-        first = {k: v.detach().clone() for k, v in self._run2(True, next_batch, upcoming[-1]).items()}
-        self.opt.zero_grad()
-        torch.cuda.synchronize()
-        self.g_main = torch.cuda.CUDAGraph()
-        self.g_bb2 = [torch.cuda.CUDAGraph() for _ in range(L)]
-        for sl in range(L):
-            with torch.cuda.graph(self.g_bb2[sl], capture_error_mode="thread_local"):
-                self._bb_body(sl)
-        with torch.cuda.graph(self.g_main, capture_error_mode="thread_local"):
-            self.losses = self._main_body()
-        self._primed = True
-        return first
-
-    # ---- trunk in pairs ---------------------------------------------------------------------------------------
-    def _pair_backbone(self, ps):
-        m = self.model
-        imgs = m.preprocess_image([{"image": im} for im in self._pimages[ps]])
-        f = m.backbone(imgs.tensor)[self.heads.box_in_features[0]].permute(0, 2, 3, 1)
-        assert f.is_contiguous()
-        return f
-
-    def _pair_stage(self, group, ps):
-        for i, x in enumerate([x for b in group for x in b]):
-            self._pimages[ps][i].copy_(x["image"], non_blocking=True)
-            if x["image"].is_cuda:  # (a device mapper's image lives in another stream's pool: DatasetMapper.finish)
-                x["image"].record_stream(torch.cuda.current_stream())
-
-    def _pair_bb_body(self, ps):
-        with torch.no_grad():
-            self._pfeats[ps].copy_(self._pair_backbone(ps))
-
-    def _pair_pool_body(self, ps, half):
-        with torch.no_grad():
-            n = self.n_img
-            # in front of the pooling kernel (see _pool_next)
-            ops.stage_heads_inputs(self.rois_next, self.props, self._gt_stage if self.stage_ahead else None,
-                                   self._gt_block if self.stage_ahead else None)
-            if self.engine.kshard is not None:
-                self.pooled = self.engine.pool_kshard(self._pfeats[ps][half * n: (half + 1) * n], self.rois_next, self.obj_next)
-                return
-            self.pooled = self.engine.pool(self._pfeats[ps][half * n: (half + 1) * n], self.rois_next, self.obj_next, True,
-                                           slot=0)
-            self._check_pooled()
-
-    def _run_pairs(self, eager, next_batch, *ahead):
-        """Step t.  Batches 2k and 2k+1 form pair k, living in pair slot k % P (P = 2, or RING_SLOTS under the ring schedule).
-        Even t: the conv chain of pair t/2 + 1 (batches t+2, t+3) starts on the side stream - with P = 2 its slot was last read by
-        the pooling of batch t-1.  Every t: the
-        pooling of batch t+1 reads its half of its pair's features (pair (t+1)/2, launched at step 2 ((t+1)/2) - 2)."""
-        G = self.G
+    # ---- the ahead schedule: lookahead L >= 2, trunk groups, the ring ---------------------------------------------------------------
+    def _run_ahead(self, eager, next_batch, upcoming):
+        """Step t at (G, A, P): see ahead_schedule for the indices.
+          side : proposals / labels of batch t+1 -> the staging set; when t % G == 0, the images of the group A ahead -> its slot
+                 and the conv chain of that slot.  The slot's and the set's last readers are pooling launches of earlier steps: one
+                 wait on the main stream orders the side stream behind them, under the ring the host's throttle does.  With A >= 3
+                 the A-1 side streams take turns
+          main : heads graph of batch t (+ eager tail), wait for the trunk of batch t+1's group, pooling piece of batch t+1"""
         main = torch.cuda.current_stream()
         t = self._t
         ring = self._ring_on and not eager
+        s = ahead_schedule(t, *self._GAP, self.RING_SETS if ring else 1)
+        side = self._sides[t % len(self._sides)]
         if ring:
             while len(self._ring_evs) > self.RING_LAG - 1:
                 self._ring_evs.pop(0).synchronize()  # heads(t - RING_LAG) are done: every earlier reader of the set / slot written below
-            self._nb = (t + 1) % self.RING_SETS
         else:
-            self._side.wait_stream(main)
-        P = self.RING_SLOTS if self._ring_on else 2
+            side.wait_stream(main)
+        self._nb = s.nb
         losses = self._heads(eager)
-        evp = None
         if self.split_tail:
             self.engine.run_fc1_tail()
         if ring:
@@ -454,69 +399,70 @@ class GraphedTrainStep:
                 raise DrnError("the ring schedule needs the pipelined optimizer's hook on the fc6 tail")
             self.opt.small_ready_event = None
             self._ring_evs.append(ev)
-        with torch.cuda.stream(self._side):
-            # proposals of batch t+1 on the side stream (behind the last reader of their staging set: the wait above, or under
-            # the ring schedule the host's throttle; in front of the conv chain): three small launches that sat between the last dW slab and the
-            # pooling graph on the main stream (22 us in the timeline)
+        evp = None
+        with torch.cuda.stream(side):
+            # proposals of batch t+1 on the side stream (behind the last reader of their staging set, in front of the conv chain):
+            # three small launches that sat between the last dW slab and the pooling piece on the main stream (22 us in the timeline)
             if self.stage_ahead:
                 self._stage_props(next_batch)
-                self._stage_labels_ahead(next_batch, via_stage=True)  # -> _gt_stage; the pooling graph hands them on
+                self._stage_labels_ahead(next_batch, via_stage=True)  # -> _gt_stage; the pooling piece hands them on
                 evp = torch.cuda.Event()
-                evp.record(self._side)
-            if t % G == 0:
-                ps = (t // G + 1) % P
-                self._pair_stage(ahead[G - 2: 2 * G - 2], ps)  # batches t+G .. t+2G-1 (ahead[0] is batch t+2)
-                self._pair_bb_body(ps) if eager else self.g_pbb[ps].replay()
-                ev = torch.cuda.Event()
-                ev.record(self._side)
-                self._pdone[ps] = ev
+                evp.record(side)
+            if s.launch is not None:
+                self._stage_image([x for b in upcoming[s.stage] for x in b], s.launch)
+                self._bb_body(s.launch) if eager else self.g_pbb[s.launch].replay()
+                self._done[s.launch] = torch.cuda.Event()
+                self._done[s.launch].record(side)
         if evp is not None:
             main.wait_event(evp)
         else:
             self._stage_props(next_batch)
-        k1, h1 = ((t + 1) // G) % P, (t + 1) % G
-        main.wait_event(self._pdone[k1])
-        self._pair_pool_body(k1, h1)
+        main.wait_event(self._done[s.pool_slot])
+        self._pool_body(s.pool_slot, s.pool_part)
         if self.split_tail:
             self._opt_step()
         self._t = t + 1
         return losses
 
-    def _prime_pairs(self, b0, b1, *ahead):
+    def _prime_ahead(self, first_batch, next_batch, upcoming):
+        """The trunks of groups 0 .. A-1 and the pooling of batch 0, step 0 eagerly (_run_ahead launches group A's chain), then the
+        captures: the heads graph and one chain graph per slot."""
         self.heads.train()
         main = torch.cuda.current_stream()
-        G = self.G
-        # the ring: one GPU, the eager fc6 tail with the pipelined optimizer's hook (its event is the throttle's)
-        self._ring_on = (self.engine.kshard is None and self.split_tail and getattr(self.engine, "grad_ready_hook", None) is not None
-                         and self._ring_want)
-        P = self.RING_SLOTS if self._ring_on else 2
-        self._pimages = [[im.clone() for _ in range(G) for im in self.image] for _ in range(P)]
-        self._pfeats, self._pdone = [None] * P, [None] * P
+        G, A = self._GA
+        # the ring: trunk groups on one GPU, the eager fc6 tail with the pipelined optimizer's hook (its event is the throttle's)
+        self._ring_on = (self.trunk_pairs and self.engine.kshard is None and self.split_tail
+                         and getattr(self.engine, "grad_ready_hook", None) is not None and self._ring_want)
+        P = A if not self.trunk_pairs else self.RING_SLOTS if self._ring_on else 2
+        self._GAP = (G, A, P)
+        self._sides = [self._side] + [torch.cuda.Stream() for _ in range(A - 2)]
+        self._images = [[im.clone() for _ in range(G) for im in self.image] for _ in range(P)]
+        self._done = [None] * P
+        batches = [first_batch, next_batch] + list(upcoming)
         with torch.no_grad():
-            self._pair_stage([b0, b1] + list(ahead[: G - 2]), 0)
-            self._pfeats[0] = self._pair_backbone(0).clone()
-            for ps in range(1, P):
-                self._pfeats[ps] = torch.zeros_like(self._pfeats[0])
-            self._stage_props(b0)
-            self._pair_pool_body(0, 0)
-        self._pdone[0] = torch.cuda.Event()
-        self._pdone[0].record(main)
-        self._stage_labels(b0)
+            self._stage_image([x for b in batches[:G] for x in b], 0)
+            f0 = self._backbone(0).clone()
+            self._feats = [f0] + [torch.zeros_like(f0) for _ in range(P - 1)]
+            self._stage_props(first_batch)
+            self._pool_body(0, 0)
+            for q in range(A):
+                if q:
+                    self._stage_image([x for b in batches[q * G: (q + 1) * G] for x in b], q)
+                    self._bb_body(q)
+                self._done[q] = torch.cuda.Event()
+                self._done[q].record(main)
+        self._stage_labels(first_batch)
         self.opt.zero_grad()
         self._t = 0
-        first = {k: v.detach().clone() for k, v in self._run_pairs(True, b1, *ahead).items()}
+        first = {k: v.detach().clone() for k, v in self._run_ahead(True, next_batch, upcoming).items()}
         self.opt.zero_grad()
         torch.cuda.synchronize()
-        self.g_main = torch.cuda.CUDAGraph()
-        self.g_pbb = [torch.cuda.CUDAGraph() for _ in range(P)]
-        for ps in range(P):
-            with torch.cuda.graph(self.g_pbb[ps], capture_error_mode="thread_local"):
-                self._pair_bb_body(ps)
-        with torch.cuda.graph(self.g_main, capture_error_mode="thread_local"):
-            self.losses = self._main_body()
+        self.g_pbb = [_captured(self._bb_body, slot)[0] for slot in range(P)]
+        self.g_main, self.losses = _captured(self._main_body)
         self._primed = True
         return first
 
+    # ---- lookahead = 1 ------------------------------------------------------------------------------------------------------------
     def _run(self, eager, next_batch=None):
         """One step = three pieces on two torch streams, ordered by events exactly like eager multi-stream code.  (A
         single graph with the backbone as an internal branch was measured first: the HIP graph executor starts that
@@ -553,30 +499,25 @@ class GraphedTrainStep:
         self._stage_next(first_batch)
         with torch.no_grad():
             self.feat_next = self._backbone().clone()
-            self._pool_next()
+            self._feats = [self.feat_next]
+            self._pool_body()
         self._stage_labels(first_batch)
         self._stage_next(next_batch)
         self.opt.zero_grad()
         first = {k: v.detach().clone() for k, v in self._run(eager=True).items()}
         self.opt.zero_grad()
         torch.cuda.synchronize()
-        self.g_bb, self.g_main, self.g_pool = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        # thread_local: with N > 1 the RCCL watchdog thread polls its events while we capture; only this thread's calls
-        # belong to the capture
-        with torch.cuda.graph(self.g_bb, capture_error_mode="thread_local"):
-            self._bb_body()
-        with torch.cuda.graph(self.g_main, capture_error_mode="thread_local"):
-            self.losses = self._main_body()
-        with torch.cuda.graph(self.g_pool, capture_error_mode="thread_local"):
-            self._pool_body()
+        self.g_bb = _captured(self._bb_body)[0]
+        self.g_main, self.losses = _captured(self._main_body)
+        self.g_pool = _captured(self._pool_body)[0]
         self._primed = True
         return first
 
     def step(self, batch, next_batch, *upcoming):
         """run the step for `batch` (which must be the batch passed as `next_batch` to the previous call); the same
-        step prepares `next_batch` (backbone on the side stream, pooling behind the last dW GEMM).  With lookahead=L >= 2
-        the caller also hands over the L-1 batches after that (`upcoming` = batches t+2 .. t+L: only their images are
-        read); the backbone of the last one runs now.  With trunk_pairs: step(batch, next_batch, batch t+2, batch t+3)."""
+        step prepares `next_batch` (backbone on the side stream, pooling behind the last dW GEMM).  The ahead schedule also takes
+        the ahead_arity(G, A) batches after that, of which only the images are read: lookahead=L, batches t+2 .. t+L (the backbone
+        of the last one runs now); trunk_pairs=G, batches t+2 .. t+2G-1 (when t % G == 0 the chain of the last G starts now)."""
         self._replayed = self._primed
         if self._primed:
             # the captured (or eagerly issued) SGD launches read lr / weight decay from device tables: follow the schedule
@@ -587,28 +528,23 @@ class GraphedTrainStep:
             self._win = window_position(self._iter, self.iter_size, self._start_iter)
             self.opt.set_window(self._win)
             self._iter += 1
-        if self.trunk_pairs:
-            if len(upcoming) != 2 * self.G - 2:
+        if self._GA is None:
+            if not self._primed:
+                return self.prime(batch, next_batch)
+            self._stage_labels_now(batch)
+            return self._run(eager=False, next_batch=next_batch)
+        if len(upcoming) != ahead_arity(*self._GA):
+            if self.trunk_pairs:
                 raise DrnError("GraphedTrainStep(trunk_pairs=%d).step needs batches t+2 .. t+%d" % (self.G, 2 * self.G - 1))
-            if not self._primed:
-                return self._prime_pairs(batch, next_batch, *upcoming)
-            self._stage_labels_now(batch)
-            return self._run_pairs(False, next_batch, *upcoming)
-        if self.lookahead >= 2:
-            if len(upcoming) != self.lookahead - 1:
-                raise DrnError("GraphedTrainStep(lookahead=%d).step needs the %d batches after next_batch"
-                               % (self.lookahead, self.lookahead - 1))
-            if not self._primed:
-                return self._prime2(batch, next_batch, list(upcoming))
-            self._stage_labels_now(batch)
-            return self._run2(False, next_batch, upcoming[-1])
+            raise DrnError("GraphedTrainStep(lookahead=%d).step needs the %d batches after next_batch"
+                           % (self.lookahead, self.lookahead - 1))
         if not self._primed:
-            return self.prime(batch, next_batch)
+            return self._prime_ahead(batch, next_batch, upcoming)
         self._stage_labels_now(batch)
-        return self._run(eager=False, next_batch=next_batch)
+        return self._run_ahead(False, next_batch, upcoming)
 
 
-class GraphedFullStep(GraphedTrainStep):
+class GraphedFullStep(_StaticInputs):
     """The training step of a TRAINABLE trunk (MODEL.BACKBONE.FREEZE_AT < 5) as ONE hipGraph on one stream: preprocess,
     trunk forward with saved activations, ROIPool (with arg-max), heads, losses, the explicit backward through the
     heads, fc6 dX, RoIPool / ROIAlign backward and every trainable trunk block (conv dgrad / wgrad straight into the
@@ -624,12 +560,11 @@ class GraphedFullStep(GraphedTrainStep):
     only pay when the optimizer can update one while the next is still being produced, which the plain optimizer step of a
     trainable trunk does not do."""
 
-    _needs_frozen_trunk = False
-
     def __init__(self, model, optimizer, example_batch, parallel=None):
         if getattr(optimizer, "_pipelined", False):
             raise DrnError("GraphedFullStep uses the plain optimizer step (the pipelined mode assumes a frozen trunk)")
-        super().__init__(model, optimizer, example_batch, split_tail=False, lookahead=1)
+        super().__init__(model, optimizer, example_batch)
+        self.engine.defer_fc1_tail = False
         self.g_step = None
         self.g_trunk = None
         self.g_opt = None
@@ -662,10 +597,7 @@ class GraphedFullStep(GraphedTrainStep):
         # final when the heads' backward ends - runs under it; the hook only keeps what that piece needs
         eng.feature_grad_hook = m._backbone_backward if self.dp is None else self._keep_feature_grad
         losses, st = eng.forward(f, self.rois, self.obj, True, self.img_off, self.n_img, self.gt)
-        if torch.cuda.is_current_stream_capturing():
-            self._captured_state = st
-        else:
-            self._eager_state = st
+        self._keep_state(st)
         # the per-bucket hooks of DataParallel (eager trainer) are replaced by _exchange_* below: off while THIS step's
         # backward runs, restored right after (the flag used to stay off on the shared object for good)
         flag = None if self.dp is None else self.dp.sync_gradients
@@ -732,20 +664,13 @@ class GraphedFullStep(GraphedTrainStep):
             self.opt.zero_grad()
             first = {k: v.detach().clone() for k, v in self._full_body().items()}
             torch.cuda.synchronize()
-            self.g_step = torch.cuda.CUDAGraph()
+            # the capture pass RUNS nothing: the gradient arenas and weights are exactly as step 0 left them
             if self.dp is None:
-                with torch.cuda.graph(self.g_step, capture_error_mode="thread_local"):
-                    self.losses = self._full_body()
+                self.g_step, self.losses = _captured(self._full_body)
             else:
-                # the capture pass RUNS nothing: the gradient arenas and weights are exactly as step 0 left them
-                with torch.cuda.graph(self.g_step, capture_error_mode="thread_local"):
-                    self.losses = self._fwd_bwd()
-                self.g_trunk = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_trunk, capture_error_mode="thread_local"):
-                    self._trunk_bwd()
-                self.g_opt = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local"):
-                    self._opt_body()
+                self.g_step, self.losses = _captured(self._fwd_bwd)
+                self.g_trunk = _captured(self._trunk_bwd)[0]
+                self.g_opt = _captured(self._opt_body)[0]
             return first
         self.opt.refresh_tables()
         self.g_step.replay()

@@ -402,7 +402,7 @@ def test_grad_accumulation_iter_size():
     assert torch.allclose(model.roi_heads.box_refinery_0.cls_score.bias.grad, 1.5 * b1, rtol=1e-4, atol=1e-7)
 
 
-@pytest.mark.parametrize("lookahead", [1, 2, 3, "pairs", "group3", "group4"])
+@pytest.mark.parametrize("lookahead", [1, 2, 3, 4, "pairs", "group3", "group4"])
 def test_hipgraph_step_equals_eager(lookahead):
     """GraphedTrainStep (whole step captured into a hipGraph, next image's backbone forked onto a side stream) must
     reproduce the eager trainer step for step: same losses over the steps on a cycle of three different batches (with
