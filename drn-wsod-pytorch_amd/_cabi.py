@@ -66,6 +66,9 @@ _SIGS = {
     "drn_sum_small": "pifpp",
     "drn_sgd_step": "pppilpipififp",
     "drn_sgd_step_block": "pppilpip" + "iiiil" + "fifp",
+    "drn_grad_norms": "pilpiifpplp",
+    "drn_sgd_step_clip": "pppilpipifif" + "ifp" + "p",
+    "drn_sgd_step_block_clip": "pppilpip" + "iiiil" + "fif" + "ifp" + "p",
     "drn_detect_topk": "ppiii" + "ffff" + "i" + "pl" + "i" + "ppp",
     "drn_detect_gather": "plippippppp",
     "drn_csc_cpg": "piiiiippp",
@@ -115,6 +118,8 @@ def lib():
         _lib.drn_roi_pool_workspace_bytes.restype = ctypes.c_long
         _lib.drn_roi_backward_det_ws_bytes.argtypes = [ctypes.c_int] * 4
         _lib.drn_roi_backward_det_ws_bytes.restype = ctypes.c_long
+        _lib.drn_grad_norms_ws_bytes.argtypes = [ctypes.c_int]
+        _lib.drn_grad_norms_ws_bytes.restype = ctypes.c_long
         _lib.drn_augment_lds_bytes.argtypes = [ctypes.c_int] * 7
         _lib.drn_augment_lds_bytes.restype = ctypes.c_long
         for kv in filter(None, os.environ.get("DRN_TUNE", "").split(",")):  # A/B runs: DRN_TUNE="5=0,4=1024" (drn_tune knobs)
@@ -125,7 +130,7 @@ def lib():
 
 def exported_symbols():
     return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
-                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes"])
+                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes", "drn_grad_norms_ws_bytes"])
 
 
 _ERR = {-1: "invalid argument", -2: "kernel launch failure", -3: "unsupported"}

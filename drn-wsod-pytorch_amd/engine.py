@@ -42,9 +42,21 @@ def window_position(it, iter_size, start_iter=0):
 
 class FusedSGD:
     def __init__(self, model, base_lr, momentum, weight_decay, bias_lr_factor=1.0, weight_decay_bias=None,
-                 weight_decay_norm=0.0, nesterov=False):
+                 weight_decay_norm=0.0, nesterov=False, clip_type=None, clip_value=1.0, norm_type=2.0):
+        """clip_type / clip_value / norm_type: SOLVER.CLIP_GRADIENTS (detectron2/solver/build.py:19-90) - every parameter is
+        clipped on its own right before the update, on the gradient the update sees (g * grad_scale): "value" clamps to
+        +-clip_value, "norm" scales by min(clip_value / (||g||_norm_type + 1e-6), 1); None = no clipping (every launch as before)."""
         if nesterov:
             raise DrnError("nesterov SGD is not used by any DRN-WSOD config")
+        if clip_type not in (None, "value", "norm"):
+            raise ValueError("%r is not a valid GradientClipType (SOLVER.CLIP_GRADIENTS.CLIP_TYPE: 'value' or 'norm')" % (clip_type,))
+        self.clip_type, self.clip_value, self.norm_type = clip_type, float(clip_value), float(norm_type)
+        if clip_type == "norm":
+            ops.norm_type_code(norm_type)  # 1, 2 and inf are built; DrnError naming the key otherwise
+        if clip_type is not None and not self.clip_value >= 0.0:
+            raise DrnError("SOLVER.CLIP_GRADIENTS.CLIP_VALUE must be >= 0 (got %r)" % (clip_value,))
+        self._norms = None  # clip_type "norm": per-parameter norms of the last plain step (heads' segments, then the trunk's)
+        self._norm_ws = None
         self.model = model
         self.engine = model.roi_heads._engine
         self.momentum = momentum
@@ -110,10 +122,39 @@ class FusedSGD:
         if bb["mom"] is None:
             bb["mom"] = torch.zeros_like(bb["w"])
         segs, nseg = self._segs_bb()
-        ops.sgd_step(bb["w"], bb["mom"], bb["g"], segs, nseg, self.momentum, self._steps == 0, grad_scale)
+        ops.sgd_step(bb["w"], bb["mom"], bb["g"], segs, nseg, self.momentum, self._steps == 0, grad_scale,
+                     clip=self._clip(bb["g"], segs, nseg, grad_scale, self._nseg))
         for m in self.model.backbone.modules():
             if hasattr(m, "invalidate_packs"):
                 m.invalidate_packs()  # updated in place: the packed compute copies of the conv weights are stale
+
+    def _clip(self, grads, segs, nseg, grad_scale, first):
+        """clip argument of the plain step's ops.sgd_step over one arena (None without clipping).  "norm": the per-segment norms
+        are computed here, on the device, into elements first .. first + nseg of ONE buffer that is allocated once (as is the
+        workspace), so a captured step keeps writing what last_grad_norms() hands out."""
+        if self.clip_type is None:
+            return None
+        if self.clip_type == "value":
+            return (ops.CLIP_VALUE, self.clip_value, None)
+        if self._norms is None:
+            tot = self._nseg + (len(self._bb["groups"]) if self._bb is not None else 0)
+            self._norms = torch.zeros((tot,), dtype=torch.float32, device=grads.device)
+            self._norm_ws = torch.empty((ops.grad_norms_ws_bytes(tot),), dtype=torch.uint8, device=grads.device)
+        norms = self._norms[first: first + nseg]
+        ops.grad_norms(grads, segs, nseg, self.norm_type, grad_scale, out=norms, workspace=self._norm_ws)
+        return (ops.CLIP_NORM, self.clip_value, norms)
+
+    def last_grad_norms(self):
+        """(names, norms): the per-parameter gradient norms ||g * grad_scale||_NORM_TYPE the last plain step() clipped by, as the
+        device tensor the step wrote (no synchronisation: float() it only when you need to look), in the order of `names` -
+        the heads' parameters, then a trainable trunk's.  clip_type "norm" only; (names, None) before the first step."""
+        if self.clip_type != "norm":
+            raise DrnError("last_grad_norms(): SOLVER.CLIP_GRADIENTS.CLIP_TYPE is %r, norms are computed for 'norm' only"
+                           % (self.clip_type,))
+        names = [g["name"] for g in self.param_groups if g["used"] and not g.get("bb")]
+        if self._bb is not None:
+            names += [g["name"] for g in self._bb["groups"]]
+        return names, self._norms
 
     def _segs(self):
         groups = [g for g in self.param_groups if g["used"] and not g.get("bb")]
@@ -178,6 +219,26 @@ class FusedSGD:
         iter_size = int(iter_size)
         if iter_size < 1:
             raise DrnError("iter_size must be >= 1")
+        self._bucket_clip = None
+        if self.clip_type is not None:
+            # SOLVER.CLIP_GRADIENTS on this schedule: value clipping, single process, iter_size 1, fc6 dW unfused (the fused
+            # launches' epilogues carry no clamp); everything else is the plain step()'s
+            why = None
+            if self.clip_type == "norm":
+                why = "CLIP_TYPE 'norm' needs a whole tensor's norm before any of it is updated, and fc6.weight arrives in slabs"
+            elif dp is not None and dp.exchange:
+                why = "clipping acts on the gradient summed over the ranks, which this schedule updates bucket by bucket"
+            elif exchange == "fc6_kshard":
+                why = "the K-sharded fc6 updates its columns in the fused fc6 dW + SGD launch"
+            elif iter_size > 1:
+                why = "the closing micro-iteration of a WSL.ITER_SIZE > 1 window rounds and updates fc6.weight in one fused launch"
+            elif fused_tn:
+                why = "fused_tn=True: the fused fc6 dW + SGD launch has no clamp in its epilogue (leave fused_tn unset)"
+            if why is not None:
+                raise DrnError("SOLVER.CLIP_GRADIENTS is not built for this pipelined optimizer schedule (%s); use the "
+                               "plain step()" % why)
+            fused_tn = False
+            self._bucket_clip = (ops.CLIP_VALUE, self.clip_value, None)
         if iter_size > 1:
             if self._bb is not None:
                 raise DrnError("WSL.ITER_SIZE > 1 in the pipelined optimizer mode needs a frozen backbone (FREEZE_AT=5)")
@@ -303,6 +364,9 @@ class FusedSGD:
             raise DrnError("enable_pipelined() first")
         if self._exchange_on:
             raise DrnError("the fused fc6 dW + SGD launch is a single-process schedule")
+        if self.clip_type is not None:
+            raise DrnError("SOLVER.CLIP_GRADIENTS: the fused fc6 dW + SGD launch has no clamp in its epilogue; the clipped "
+                           "pipelined schedule runs fc6 dW unfused")
         self.engine.fc1_fused_tn = self._fused_fc1_tn
 
     def _fused_fc1_tn(self, dPT, A, D1, n_main, Mp, M, gw):
@@ -577,13 +641,14 @@ class FusedSGD:
     def _update(self, what, bucket, segs, nseg):
         e = self.engine
         world = self._dp.world if self._dp is not None else 1
+        clip = self._bucket_clip  # value clipping is element-wise: every bucket's launch clamps its own elements
         if what[0] == "fc1b":
             # a rectangular block of fc1.weight (the trailing columns of the fused dW launch; the K-sharded fc6's owned columns)
             _, r0, r1, c0, c1 = what
             k1 = self.model.roi_heads.box_head.fc1.weight.shape[1]
             ops.sgd_step_block(e.arena_w, self._mom, bucket if bucket is not None else e.arena_g, segs, r0, r1 - r0, c0,
                                c1 - c0, k1, self.momentum, self._steps == 0, 1.0 / world, shadow=e.arena_s,
-                               grad_off=e._seg["fc1.weight"][0] if bucket is not None else 0)
+                               grad_off=e._seg["fc1.weight"][0] if bucket is not None else 0, clip=clip)
             if getattr(self, "_kshard", False):
                 self._master_stale = True  # the other ranks' columns of fc1.weight / momentum / shadow live on those ranks
             return
@@ -593,15 +658,15 @@ class FusedSGD:
             k1 = self.model.roi_heads.box_head.fc1.weight.shape[1]
             segs, nseg = self._bucket_table(("fc1", a, b))
             ops.sgd_step(e.arena_w, self._mom, bucket, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
-                         shadow=e.arena_s, grad_off=e._seg["fc1.weight"][0] + a * k1)
+                         shadow=e.arena_s, grad_off=e._seg["fc1.weight"][0] + a * k1, clip=clip)
             self._master_stale = True  # momentum (and, with a bf16 shadow, the fp32 master) of the other ranks' rows
             return
         if bucket is not None:
             ops.sgd_step(e.arena_w, self._mom, bucket, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
-                         shadow=e.arena_s, grad_off=0 if what == "small" else e._seg["fc1.weight"][0])
+                         shadow=e.arena_s, grad_off=0 if what == "small" else e._seg["fc1.weight"][0], clip=clip)
         else:
             ops.sgd_step(e.arena_w, self._mom, e.arena_g, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
-                         shadow=e.arena_s)
+                         shadow=e.arena_s, clip=clip)
         if what == "small" and hasattr(e, "sh"):
             e.refresh_transposes()  # fc7 / predictor weights are final for this step: rebuild their K-major twins here
             e._transposes_fresh = True
@@ -650,7 +715,7 @@ class FusedSGD:
             self._mom = torch.zeros_like(e.arena_w)
         segs, nseg = self._segs()
         ops.sgd_step(e.arena_w, self._mom, e.arena_g, segs, nseg, self.momentum, self._steps == 0, grad_scale,
-                     shadow=e.arena_s)
+                     shadow=e.arena_s, clip=self._clip(e.arena_g, segs, nseg, grad_scale, 0))
         if self._bb is not None:
             self._step_bb(grad_scale)
         self._steps += 1
@@ -718,9 +783,13 @@ class FusedSGD:
 
 
 def build_optimizer(cfg, model):
-    """detectron2/solver/build.py:93-137."""
+    """detectron2/solver/build.py:93-137, with maybe_add_gradient_clipping (:62-90) folded into the optimizer's own kernels."""
+    clip = cfg.SOLVER.CLIP_GRADIENTS
+    kw = {}
+    if clip.ENABLED:
+        kw = dict(clip_type=clip.CLIP_TYPE, clip_value=clip.CLIP_VALUE, norm_type=clip.NORM_TYPE)
     return FusedSGD(model, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, cfg.SOLVER.WEIGHT_DECAY, cfg.SOLVER.BIAS_LR_FACTOR,
-                    cfg.SOLVER.WEIGHT_DECAY_BIAS, cfg.SOLVER.WEIGHT_DECAY_NORM, cfg.SOLVER.NESTEROV)
+                    cfg.SOLVER.WEIGHT_DECAY_BIAS, cfg.SOLVER.WEIGHT_DECAY_NORM, cfg.SOLVER.NESTEROV, **kw)
 
 
 class WarmupMultiStepLR:

@@ -835,16 +835,62 @@ def sum_small(x, scale=1.0):
     return out
 
 
+CLIP_NONE, CLIP_VALUE, CLIP_NORM = 0, 1, 2  # clip_mode of drn_sgd_step_clip / drn_sgd_step_block_clip
+_NORM_TYPES = {1.0: 1, 2.0: 2, float("inf"): 0}  # NORM_TYPE -> norm_type of drn_grad_norms
+
+
+def norm_type_code(norm_type):
+    """SOLVER.CLIP_GRADIENTS.NORM_TYPE -> drn_grad_norms' code; 1, 2 and inf are built."""
+    code = _NORM_TYPES.get(float(norm_type))
+    if code is None:
+        raise C.DrnError("SOLVER.CLIP_GRADIENTS.NORM_TYPE %r is not built: 1, 2 and inf are" % (norm_type,))
+    return code
+
+
+def grad_norms_ws_bytes(nseg):
+    """bytes of the workspace drn_grad_norms needs for nseg segments (host-only)"""
+    return C.lib().drn_grad_norms_ws_bytes(int(nseg))
+
+
+def grad_norms(grads, segs_dev, nseg, norm_type, grad_scale=1.0, grad_off=0, out=None, workspace=None):
+    """Per-segment norms || grads[segment] * grad_scale ||_p (p = norm_type: 1, 2 or inf) -> fp32 [nseg] on the device; grads /
+    grad_off as in sgd_step.  No atomics, fixed summation order, no host synchronisation.  out / workspace (uint8,
+    grad_norms_ws_bytes(nseg)): buffers to reuse, e.g. under a captured graph."""
+    code = norm_type_code(norm_type)
+    if out is None:
+        out = torch.empty((nseg,), dtype=torch.float32, device=grads.device)
+    need = grad_norms_ws_bytes(nseg)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=grads.device)
+    C.call("drn_grad_norms", C.ptr(grads), C.dt(grads.dtype), int(grad_off), C.ptr(segs_dev), int(nseg), code,
+           float(grad_scale), C.ptr(out), C.ptr(workspace), int(workspace.numel() * workspace.element_size()), C.stream())
+    return out
+
+
+def _clip_args(clip):
+    mode, value, norms = clip
+    mode = int(mode)
+    if mode == CLIP_NORM and norms is None:
+        raise C.DrnError("clip=(CLIP_NORM, value, norms) needs the device norms of grad_norms()")
+    return mode, float(value), C.ptr(norms) if mode == CLIP_NORM else None
+
+
 def sgd_step(weights, momentum_buf, grads, segs_dev, nseg, momentum, first_step, grad_scale=1.0, shadow=None,
-             grad_off=0):
+             grad_off=0, clip=None):
     """grads: the fp32 gradient arena, or (grad_off > 0) a bucket buffer - fp32 or bf16 - whose element 0 is arena
-    element grad_off."""
+    element grad_off.  clip = (mode, value, norms): SOLVER.CLIP_GRADIENTS per segment on g * grad_scale (drn_sgd_step_clip;
+    norms = grad_norms() over the same table for CLIP_NORM); None = drn_sgd_step."""
     if HBM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    C.call("drn_sgd_step", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
-           C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
-           int(first_step), float(grad_scale), C.stream())
+    if clip is None:
+        C.call("drn_sgd_step", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
+               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
+               int(first_step), float(grad_scale), C.stream())
+    else:
+        C.call("drn_sgd_step_clip", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
+               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
+               int(first_step), float(grad_scale), *_clip_args(clip), C.stream())
     if HBM_TIMING is not None:
         e1.record()
         # bytes are the caller's to know (the segment table lives on the device): keyed by (segments, bucket offset)
@@ -852,16 +898,22 @@ def sgd_step(weights, momentum_buf, grads, segs_dev, nseg, momentum, first_step,
 
 
 def sgd_step_block(weights, momentum_buf, grads, seg_dev, r0, rows, c0, cols, ld, momentum, first_step, grad_scale=1.0,
-                   shadow=None, grad_off=0):
+                   shadow=None, grad_off=0, clip=None):
     """drn_sgd_step on rows r0 .. r0+rows, columns c0 .. c0+cols of the [., ld] tensor described by seg_dev (ONE
     {offset, count, lr, wd} entry on the device); weights / momentum_buf / shadow are the flat arenas, grads as in
-    sgd_step."""
+    sgd_step.  clip as in sgd_step (drn_sgd_step_block_clip); its norms = ONE element, the norm of that tensor."""
     if HBM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    C.call("drn_sgd_step_block", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
-           C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0), int(rows), int(c0),
-           int(cols), int(ld), float(momentum), int(first_step), float(grad_scale), C.stream())
+    if clip is None:
+        C.call("drn_sgd_step_block", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
+               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0), int(rows), int(c0),
+               int(cols), int(ld), float(momentum), int(first_step), float(grad_scale), C.stream())
+    else:
+        C.call("drn_sgd_step_block_clip", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype),
+               int(grad_off), C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0),
+               int(rows), int(c0), int(cols), int(ld), float(momentum), int(first_step), float(grad_scale),
+               *_clip_args(clip), C.stream())
     if HBM_TIMING is not None:
         e1.record()
         HBM_TIMING.append((e0, e1, int(rows) * int(cols), ("sgd_block", int(r0), int(rows), int(c0), int(cols),

@@ -498,6 +498,40 @@ int drn_sgd_step_block(float* weights, float* momentum_buf, const void* grads, i
                        int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
                        int first_step, float grad_scale, void* stream);
 
+/* SOLVER.CLIP_GRADIENTS, detectron2/solver/build.py:19-90 (maybe_add_gradient_clipping): every parameter is clipped ON ITS OWN right
+ * before SGD.step, on the gradient as it stands there - here g * grad_scale of one segment of the table.
+ *
+ * drn_grad_norms: norms[s] = || grads[segment s] * grad_scale ||_p in fp32 (the norm torch.nn.utils.clip_grad_norm_(p, CLIP_VALUE,
+ * NORM_TYPE) takes of ONE tensor); norm_type 1, 2, or 0 for inf (a maximum; a NaN entry gives NaN, as torch's does).  grads / grad_dtype /
+ * grad_off / segs_dev / nseg as for drn_sgd_step.  Shape class: any segment offset and length (16-byte non-temporal loads when the
+ * segment's first gradient is 16-byte aligned, scalar loads otherwise and for the tail); every segment is spread over a fixed grid of
+ * 512 workgroups.  No float atomics, fixed order of addition (wave butterfly, LDS tree, one fp32 partial per (segment, workgroup) in
+ * `workspace`, second launch in a fixed order): the same input gives the same bits.  No host synchronisation: capturable.
+ * workspace: drn_grad_norms_ws_bytes(nseg) = 2048 * nseg bytes (host-only function; 0 for nseg < 1), written, never read by the caller.
+ * Errors: DRN_ERR_ARG (null pointer, nseg < 1, dtype, workspace too small), DRN_ERR_UNSUPPORTED (norm_type not 0 / 1 / 2). */
+long drn_grad_norms_ws_bytes(int nseg);
+int drn_grad_norms(const void* grads, int grad_dtype, long grad_off, const void* segs_dev, int nseg, int norm_type,
+                   float grad_scale, float* norms, void* workspace, long workspace_bytes, void* stream);
+
+/* drn_sgd_step / drn_sgd_step_block with the clipped gradient d in place of g * grad_scale (the rest of the update - weight decay,
+ * momentum, lr, bf16 shadow - and its op order are unchanged; the same kernels, one more template parameter):
+ *   clip_mode 0  d = g * grad_scale                                     (bit-identical to drn_sgd_step / drn_sgd_step_block)
+ *   clip_mode 1  d = clamp(g * grad_scale, -clip_value, clip_value)      torch.nn.utils.clip_grad_value_, build.py:38-39
+ *   clip_mode 2  d = (g * grad_scale) * min((1.f / (seg_norms[s] + 1e-6f)) * clip_value, 1)   torch.nn.utils.clip_grad_norm_, build.py:35-36
+ *                (torch evaluates max_norm / (total_norm + 1e-6) as reciprocal(total_norm + 1e-6) * max_norm - Tensor.__rtruediv__ -
+ *                and so does the kernel: the coefficient has torch's bits given the norm)
+ * seg_norms (mode 2): device array from drn_grad_norms over the same table (the block form: pointer to the norm of the ONE tensor
+ * seg_dev describes); the coefficient is formed on the device, nothing crosses to the host.  A NaN gradient or coefficient stays NaN
+ * (torch.clamp's rule).  Shape class: that of the unclipped entry point.  Errors: those of the unclipped entry point, plus
+ * DRN_ERR_ARG for clip_mode outside 0 .. 2, mode 2 without seg_norms, or a clip_value that is negative or NaN. */
+int drn_sgd_step_clip(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
+                      int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
+                      int clip_mode, float clip_value, const float* seg_norms, void* stream);
+int drn_sgd_step_block_clip(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
+                            int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
+                            int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
+                            void* stream);
+
 /* ---- inference tail -------------------------------------------------------------------------- */
 
 /* fast_rcnn_inference_single_image, fast_rcnn.py:88-141 + batched_nms, detectron2/layers/nms.py:10-29. */

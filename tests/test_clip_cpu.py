@@ -1,0 +1,142 @@
+"""SOLVER.CLIP_GRADIENTS (detectron2/solver/build.py:19-90), the parts that need no GPU: build_optimizer reads the key, refuses what
+is not built, and FusedSGD.enable_pipelined refuses every clipped schedule but value clipping on the single-process,
+iter_size = 1, unfused one - each with a message that names the key and points to the plain step()."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import golden_util as G
+from __graft_entry__ import build, load_package
+
+load_package()
+from drn_wsod_pytorch_amd import ops  # noqa: E402
+from drn_wsod_pytorch_amd._cabi import DrnError  # noqa: E402
+from drn_wsod_pytorch_amd.engine import build_optimizer  # noqa: E402
+from drn_wsod_pytorch_amd.modeling import build_model  # noqa: E402
+
+
+def _cpu_model(freeze_at=None, **clip):
+    kw = {} if freeze_at is None else {"freeze_at": freeze_at}
+    cfg = G.drn_cfg(G.MODEL_CASES["model_r50c4_tiny"], "cpu", **kw)
+    for k, v in clip.items():
+        setattr(cfg.SOLVER.CLIP_GRADIENTS, k, v)
+    return cfg, build_model(cfg)
+
+
+def _opt(**clip):
+    cfg, model = _cpu_model(**clip)
+    return build_optimizer(cfg, model), model
+
+
+def test_build_optimizer_reads_the_key():
+    opt, _ = _opt()
+    assert opt.clip_type is None  # ENABLED False (the default)
+    opt, _ = _opt(CLIP_TYPE="norm", CLIP_VALUE=0.25)
+    assert opt.clip_type is None  # the other fields mean nothing while ENABLED is False
+    opt, _ = _opt(ENABLED=True)
+    assert (opt.clip_type, opt.clip_value) == ("value", 1.0)  # detectron2's defaults
+    opt, _ = _opt(ENABLED=True, CLIP_TYPE="norm", CLIP_VALUE=0.25)
+    assert (opt.clip_type, opt.clip_value, opt.norm_type) == ("norm", 0.25, 2.0)
+    opt, _ = _opt(ENABLED=True, CLIP_TYPE="norm", NORM_TYPE=float("inf"))
+    assert opt.norm_type == float("inf")
+    opt, _ = _opt(ENABLED=True, CLIP_TYPE="norm", NORM_TYPE=1.0)
+    assert opt.norm_type == 1.0
+    names, norms = opt.last_grad_norms()
+    assert norms is None and "fc1.weight" in " ".join(names)  # nothing stepped yet
+    with pytest.raises(DrnError, match="CLIP_GRADIENTS"):
+        _opt(ENABLED=True)[0].last_grad_norms()  # value clipping computes no norms
+
+
+def test_build_optimizer_refuses_what_is_not_built():
+    with pytest.raises(ValueError):
+        _opt(ENABLED=True, CLIP_TYPE="full_model")  # GradientClipType(...) raises ValueError in the reference
+    with pytest.raises(ValueError):
+        _opt(ENABLED=True, CLIP_TYPE="Value")  # the enum is case-sensitive
+    with pytest.raises(DrnError, match=r"SOLVER\.CLIP_GRADIENTS\.NORM_TYPE"):
+        _opt(ENABLED=True, CLIP_TYPE="norm", NORM_TYPE=3.0)
+    with pytest.raises(DrnError, match=r"SOLVER\.CLIP_GRADIENTS\.NORM_TYPE"):
+        _opt(ENABLED=True, CLIP_TYPE="norm", NORM_TYPE=0.0)
+    _opt(ENABLED=True, CLIP_TYPE="value", NORM_TYPE=3.0)  # NORM_TYPE is read for "norm" only, as in the reference
+    assert ops.norm_type_code(2) == 2 and ops.norm_type_code(1.0) == 1 and ops.norm_type_code(float("inf")) == 0
+
+
+class _DP:
+    world, exchange, group = 1, True, None
+
+
+def test_pipelined_value_clipping_runs_unfused():
+    opt, model = _opt(ENABLED=True, CLIP_VALUE=0.5)
+    opt.enable_pipelined()
+    eng = model.roi_heads._engine
+    assert eng.fc1_fused_tn is None  # fc6 dW + its update stay two launches: the update clamps
+    assert opt._bucket_clip == (ops.CLIP_VALUE, 0.5, None)
+    with pytest.raises(DrnError, match=r"SOLVER\.CLIP_GRADIENTS"):
+        opt.enable_fused_fc1_tn()
+    with pytest.raises(DrnError, match=r"SOLVER\.CLIP_GRADIENTS.*plain step\(\)"):
+        opt.enable_pipelined(fused_tn=True)
+    opt.enable_pipelined(fused_tn=False)
+    # and without clipping nothing changed: the fused launch is still what enable_pipelined() picks
+    plain, pm = _opt()
+    plain.enable_pipelined(fused_tn=True)
+    assert plain._bucket_clip is None
+
+
+@pytest.mark.parametrize("kw", [dict(dp=_DP()), dict(exchange="fc6_kshard"), dict(iter_size=4)])
+def test_pipelined_refuses_clipped_schedules_that_are_not_built(kw):
+    opt, _ = _opt(ENABLED=True, CLIP_VALUE=0.5)
+    with pytest.raises(DrnError, match=r"SOLVER\.CLIP_GRADIENTS.*plain step\(\)"):
+        opt.enable_pipelined(**kw)
+    assert not getattr(opt, "_pipelined", False)  # refused before anything was switched
+
+
+@pytest.mark.parametrize("norm_type", [1.0, 2.0, float("inf")])
+def test_pipelined_refuses_norm_clipping(norm_type):
+    opt, _ = _opt(ENABLED=True, CLIP_TYPE="norm", NORM_TYPE=norm_type)
+    with pytest.raises(DrnError, match=r"SOLVER\.CLIP_GRADIENTS.*plain step\(\)"):
+        opt.enable_pipelined()
+
+
+def test_clip_entry_points_declared_and_exported():
+    pkg = build()
+    hdr = open(os.path.join(G.ROOT, "include", "drn_wsod.h")).read()
+    lib = ctypes.CDLL(pkg._cabi.LIB_PATH)
+
+    def args_of(name):
+        m = re.search(r"\bint\s+%s\s*\(([^;]*)\);" % name, hdr)
+        assert m, "include/drn_wsod.h does not declare %s" % name
+        return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
+
+    for name, base in (("drn_sgd_step_clip", "drn_sgd_step"), ("drn_sgd_step_block_clip", "drn_sgd_step_block")):
+        a, b = args_of(name), args_of(base)
+        assert a[: len(b) - 1] == b[:-1] and a[-1] == b[-1]  # the unclipped arguments, in order, stream last
+        assert a[len(b) - 1: -1] == ["int clip_mode", "float clip_value", "const float* seg_norms"]
+        assert hasattr(lib, name) and len(pkg._cabi._SIGS[name]) == len(a)
+    assert len(pkg._cabi._SIGS["drn_grad_norms"]) == len(args_of("drn_grad_norms")) and hasattr(lib, "drn_grad_norms")
+    # host-only workspace size: one fp32 partial per (segment, workgroup of the fixed 512-wide grid)
+    assert ops.grad_norms_ws_bytes(7) == 7 * 512 * 4 and ops.grad_norms_ws_bytes(0) == 0
+
+
+def test_the_coefficient_is_formed_as_torch_forms_it():
+    """csrc/head.hip forms the norm-clipping coefficient as (1.f / (norm + 1e-6f)) * CLIP_VALUE, not as CLIP_VALUE / (norm + 1e-6f):
+    torch.nn.utils.clip_grad_norm_ writes `max_norm / (total_norm + 1e-6)` with a Python float on the left, which Tensor.__rtruediv__
+    evaluates as reciprocal * max_norm.  Pinned to torch itself: on fp32 gradients, clip_grad_norm_'s result equals g * coef bit for
+    bit with coef restated in numpy fp32 as the kernel computes it, and a true division gives other bits for some of the norms."""
+    rs = np.random.RandomState(3)
+    differs = 0
+    for i in range(200):
+        g = torch.from_numpy((rs.standard_normal(50) * (1.0 + i)).astype(np.float32))
+        c = float(rs.rand() * 3.0 + 0.1)
+        q = torch.nn.Parameter(torch.zeros_like(g))
+        q.grad = g.clone()
+        n = torch.nn.utils.clip_grad_norm_([q], c, norm_type=2.0).numpy().astype(np.float32)
+        x = np.float32(n + np.float32(1e-6))
+        kernel = np.float32(np.float32(1.0) / x) * np.float32(c)
+        kernel = np.float32(1.0) if kernel > 1 else kernel
+        assert np.array_equal(q.grad.numpy(), g.numpy() * kernel), i
+        division = np.float32(c) / x
+        differs += int(min(division, np.float32(1.0)) != kernel)
+    assert differs > 0
