@@ -69,6 +69,11 @@ _SIGS = {
     "drn_grad_norms": "pilpiifpplp",
     "drn_sgd_step_clip": "pppilpipifif" + "ifp" + "p",
     "drn_sgd_step_block_clip": "pppilpip" + "iiiil" + "fif" + "ifp" + "p",
+    "drn_loss_guard": "piiipp",
+    "drn_sgd_step_guard": "pppilpipifif" + "ifp" + "pp",
+    "drn_sgd_step_block_guard": "pppilpip" + "iiiil" + "fif" + "ifp" + "pp",
+    "drn_gemm_tn_sgd_guard": "ppp" + "iiii" + "lll" + "ppplp" + "fif" + "pp",
+    "drn_gemm_tn_acc_sgd_guard": "pppp" + "iiii" + "llll" + "ppplp" + "fif" + "pp",
     "drn_detect_topk": "ppiii" + "ffff" + "i" + "pl" + "i" + "ppp",
     "drn_detect_gather": "plippippppp",
     "drn_csc_cpg": "piiiiippp",

@@ -35,6 +35,14 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
   return __builtin_bit_cast(bf16_t, (__bf16)f);
 }
 
+// relu_ of the heads' forward (box_head.py:88-90).  torch.relu propagates NaN, fmaxf drops it: a NaN activation - e.g. behind ONE NaN
+// objectness logit - would vanish from the loss while the weight-gradient GEMMs, which read the pooled operand, still turn the weights
+// to NaN, and neither the reference's anomaly check nor drn_loss_guard would see it.  Every other input: fmaxf's bits.
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+// torch.clamp(v, lo, hi) and the std::max(log(x), -100) of F.binary_cross_entropy keep a NaN as well (fminf / fmaxf drop it)
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+__device__ __forceinline__ float fmax_nan(float v, float lo) { return v != v ? v : fmaxf(v, lo); }
+
 // fp8 e4m3fn <-> f32.  v_cvt_pk_fp8_f32 rounds to nearest even; the clamp makes the conversion saturating (|x| > 448 would
 // otherwise become NaN), like the quantisers the oracle emulates (x.clamp(-448, 448).to(torch.float8_e4m3fn)).
 __device__ __forceinline__ float fp8_to_f32(uint8_t v) { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }

@@ -50,6 +50,8 @@ struct GemmParams {
   // fp32 accumulators in front of the bf16 rounding; read only
   const float* sgd_acc;
   long sgd_acc_ld;
+  // GUARD (drn_gemm_tn_sgd_guard / drn_gemm_tn_acc_sgd_guard): state[0] of drn_loss_guard, one uniform load per workgroup
+  const int* sgd_guard;
 };
 
 using drn_conv::ConvParams;
@@ -436,12 +438,16 @@ __device__ __forceinline__ void pp_issue_first(char* smem, __amdgpu_buffer_rsrc_
 //   phase 1 / 2: vmcnt(4) -> vmcnt(7)   (3 loads of this slab's phase 1)      phase 4: vmcnt(4) -> vmcnt(7) from slab 1 on
 //   (3 stores of phase 3);  chunk i - 1's loads have 18 (slab 1: 15) younger operations when phase 3 of slab i needs them.
 // Same arithmetic, element for element, as sgd_kernel on the bf16 bucket (bit-identical: tests).
+// GUARD (the anomaly guard, drn_loss_guard): a skipped step keeps ALL SIX memory operations of a chunk and selects the stored
+// VALUES - w_old, m_old and the shadow word of w_old (the shadow is bf16(w) by construction) - so every count above holds
+// unchanged; a predicated store would change what each wait guards.  The flag is wave-uniform (SgdPipe::skip).
 struct SgdPipe {
   float* w; float* m; const bf16_t* g; bf16_t* s;  // bases (wave-uniform); in-place update
   unsigned off, step;    // byte offset of this lane's 16 B in chunk 0 of the tile (fp32 arrays), bytes per chunk (8 rows)
   unsigned goff, gstep;  // the same in the bf16 gradient bucket (8 B per lane); the shadow uses off / 2, step / 2
   float lr, wd, mom, gs;
   int first;
+  int skip;  // GUARD: the step's loss was not finite - every chunk stores back what it loaded
 };
 typedef float f32x2_t_ __attribute__((ext_vector_type(2)));
 struct SgdRegs { f32x4_t w, m; f32x2_t_ g; };
@@ -454,6 +460,7 @@ __device__ __forceinline__ void sgdp_load(const SgdPipe& sp, SgdRegs& r, unsigne
   r.m = __builtin_nontemporal_load((const f32x4_t*)((const char*)sp.m + off));
   r.g = __builtin_nontemporal_load((const f32x2_t_*)((const char*)sp.g + goff));
 }
+template <bool GUARD = false>
 __device__ __forceinline__ void sgdp_apply_store(const SgdPipe& sp, const SgdRegs& r, unsigned off) {
 #pragma clang fp contract(off)
   typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -468,6 +475,13 @@ __device__ __forceinline__ void sgdp_apply_store(const SgdPipe& sp, const SgdReg
     nb[e] = sp.first ? d : sp.mom * r.m[e] + d;
     nw[e] = r.w[e] - sp.lr * nb[e];
   }
+  if constexpr (GUARD) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      nb[e] = sp.skip ? r.m[e] : nb[e];
+      nw[e] = sp.skip ? r.w[e] : nw[e];
+    }
+  }
   u32x2_t o;
   o.x = (uint32_t)f32_to_bf16(nw[0]) | ((uint32_t)f32_to_bf16(nw[1]) << 16);
   o.y = (uint32_t)f32_to_bf16(nw[2]) | ((uint32_t)f32_to_bf16(nw[3]) << 16);
@@ -480,7 +494,7 @@ __device__ __forceinline__ void sgdp_apply_store(const SgdPipe& sp, const SgdReg
 // barriers (wave row 1 one extra in front, wave row 0 one extra behind).
 // SGDP: the optimizer step of the previous tile rides along (above); VAR == 1.  s1 - s0 < 32: the chunks the loop has no
 // slab for follow it, exposed.
-template <int DT, int VAR, bool TN = false, bool SGDP = false>
+template <int DT, int VAR, bool TN = false, bool SGDP = false, bool GUARD = false>
 __device__ __forceinline__ void pp_mainloop(f32x16_t (&acc)[4][2], char* smem, __amdgpu_buffer_rsrc_t ra,
                                             __amdgpu_buffer_rsrc_t rb, const unsigned (&voa)[4], const unsigned (&vob)[4],
                                             int s0, int s1, int lane, int wave, unsigned bstep = 128,
@@ -614,7 +628,7 @@ __device__ __forceinline__ void pp_mainloop(f32x16_t (&acc)[4][2], char* smem, _
     if constexpr (SGDP) {
       const unsigned i_ = (unsigned)(s - s0);
       // chunk i - 1: its loads went out in phase 1 of the previous slab (18 vector memory operations ago; 15 in slab 1)
-      if (i_ >= 1 && i_ <= 32) sgdp_apply_store(*spp, sr_use, spp->off + (i_ - 1) * spp->step);
+      if (i_ >= 1 && i_ <= 32) sgdp_apply_store<GUARD>(*spp, sr_use, spp->off + (i_ - 1) * spp->step);
     }
     PP_BARRIER();
     mm(acc[2][1], acc[3][1], NOWAIT);
@@ -654,8 +668,8 @@ __device__ __forceinline__ void pp_mainloop(f32x16_t (&acc)[4][2], char* smem, _
     // are dead at this point, the accumulators are not touched).
     const unsigned S = (unsigned)(s1 - s0);
     if (S <= 32) {
-      if (S & 1) sgdp_apply_store(*spp, srA, spp->off + (S - 1) * spp->step);
-      else sgdp_apply_store(*spp, srB, spp->off + (S - 1) * spp->step);
+      if (S & 1) sgdp_apply_store<GUARD>(*spp, srA, spp->off + (S - 1) * spp->step);
+      else sgdp_apply_store<GUARD>(*spp, srB, spp->off + (S - 1) * spp->step);
     }
     for (unsigned c = S; c < 32; c += 4) {
       SgdRegs q[4];
@@ -666,7 +680,7 @@ __device__ __forceinline__ void pp_mainloop(f32x16_t (&acc)[4][2], char* smem, _
       }
 #pragma unroll
       for (unsigned j = 0; j < 4; ++j)
-        if (c + j < 32) sgdp_apply_store(*spp, q[j], spp->off + (c + j) * spp->step);
+        if (c + j < 32) sgdp_apply_store<GUARD>(*spp, q[j], spp->off + (c + j) * spp->step);
     }
   }
   if (wm == 0) PP_BARRIER();
@@ -914,7 +928,7 @@ struct GemmWork { int bm, bn, s0, s1, split; __amdgpu_buffer_rsrc_t ra, rb; };  
 // rounding, the sum drn_gemm_tn (fp32 C, accumulate) + drn_cast2d would give.  The loads are plain epilogue loads behind the next
 // tile's first slab (the compiler counts its own wait; the fragment registers are dead here), so SgdPipe and its vmcnt ladder
 // are untouched.
-template <int DT, int PP = 0, bool TN = false, bool PAIR = false, bool SGDP = false, bool ACC = false>
+template <int DT, int PP = 0, bool TN = false, bool PAIR = false, bool SGDP = false, bool ACC = false, bool GUARD = false>
 __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p_in, GemmParams p2_in, int pair_wg0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const bool second = PAIR && (int)(blockIdx.x >> 3) >= pair_wg0;
@@ -995,6 +1009,8 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p_in, GemmP
     sp.step = (unsigned)(8 * p.sgd_ld * 4); sp.gstep = (unsigned)(8 * p.ldc * 2);
     sp.lr = p.sgd_seg->lr; sp.wd = p.sgd_seg->wd; sp.mom = p.sgd_momentum; sp.gs = p.sgd_grad_scale;
     sp.first = p.sgd_first_step;
+    sp.skip = 0;
+    if constexpr (GUARD) sp.skip = __builtin_amdgcn_readfirstlane(p.sgd_guard[0]);
     sp.off = sp.goff = 0;
   }
   for (;;) {
@@ -1007,7 +1023,7 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p_in, GemmP
     const int s0 = cur.s0, s1 = cur.s1;
     if constexpr (PP) {
       if constexpr (SGDP) {
-        if (have_prev) pp_mainloop<DT, PP, TN, true>(acc, smem, cur.ra, cur.rb, pva, pvb, s0, s1, lane, wave, bstep, &sp);
+        if (have_prev) pp_mainloop<DT, PP, TN, true, GUARD>(acc, smem, cur.ra, cur.rb, pva, pvb, s0, s1, lane, wave, bstep, &sp);
         else pp_mainloop<DT, PP, TN>(acc, smem, cur.ra, cur.rb, pva, pvb, s0, s1, lane, wave, bstep);
       } else if (s0 < s1) pp_mainloop<DT, PP, TN>(acc, smem, cur.ra, cur.rb, pva, pvb, s0, s1, lane, wave, bstep);
     } else if (s0 < s1) {
@@ -1231,8 +1247,8 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p_in, GemmP
       SgdRegs q0, q1;
       sgdp_load(sp, q0, sp.off + c * sp.step, sp.goff + c * sp.gstep);
       sgdp_load(sp, q1, sp.off + (c + 1) * sp.step, sp.goff + (c + 1) * sp.gstep);
-      sgdp_apply_store(sp, q0, sp.off + c * sp.step);
-      sgdp_apply_store(sp, q1, sp.off + (c + 1) * sp.step);
+      sgdp_apply_store<GUARD>(sp, q0, sp.off + c * sp.step);
+      sgdp_apply_store<GUARD>(sp, q1, sp.off + (c + 1) * sp.step);
     }
   }
 }
@@ -2041,18 +2057,20 @@ int launch_gemm256p(const GemmParams& p, int nwg, hipStream_t st) {
   return DRN_OK;
 }
 
+template <bool GUARD>
 static int launch_gemm256p_tn_sgdp(const GemmParams& p, int nwg, hipStream_t st) {
   constexpr int smem = 2 * 512 * 128;
-  auto k = gemm_nt256p_kernel<DRN_BF16, 1, true, false, true>;
+  auto k = gemm_nt256p_kernel<DRN_BF16, 1, true, false, true, false, GUARD>;
   if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(nwg), dim3(512), smem, st, p, p, 0);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
 
+template <bool GUARD>
 static int launch_gemm256p_tn_acc_sgdp(const GemmParams& p, int nwg, hipStream_t st) {
   constexpr int smem = 2 * 512 * 128;
-  auto k = gemm_nt256p_kernel<DRN_BF16, 1, true, false, true, true>;
+  auto k = gemm_nt256p_kernel<DRN_BF16, 1, true, false, true, true, GUARD>;
   if (!drn_launch::allow_lds((const void*)k, smem)) return DRN_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(nwg), dim3(512), smem, st, p, p, 0);
   DRN_CHECK_LAUNCH();
@@ -2237,10 +2255,11 @@ const TuneRow kTuneRows[] = {
 };
 }  // namespace
 
-// shared body of drn_gemm_tn_sgd / drn_gemm_tn_acc_sgd (grad_acc == nullptr: the former, launch and arguments unchanged)
+// shared body of drn_gemm_tn_sgd / drn_gemm_tn_acc_sgd (grad_acc == nullptr: the former, launch and arguments unchanged) and of
+// their guarded forms (guard == nullptr: the unguarded instantiations, as before)
 static int gemm_tn_sgd_entry(const void* A, const void* Bt, void* grad_bucket, const float* grad_acc, long ld_acc, int M, int N,
                              int K, int kb_rows, long lda, long ldb, long ldc, float* weights, float* momentum_buf, void* shadow,
-                             long ld_w, const void* seg_dev, float momentum, int first_step, float grad_scale, void* stream) {
+                             long ld_w, const void* seg_dev, float momentum, int first_step, float grad_scale, const int* guard, void* stream) {
   if (!A || !Bt || !grad_bucket || !weights || !momentum_buf || !seg_dev || M <= 0 || N <= 0 || K <= 0 || kb_rows < 0 ||
       kb_rows > K)
     return DRN_ERR_ARG;
@@ -2266,12 +2285,15 @@ static int gemm_tn_sgd_entry(const void* A, const void* Bt, void* grad_bucket, c
   p.nsplit = 1;
   p.gm = gemm256_group_rows(M, N, 1);
   p.kb_rows = kb_rows;
+  p.sgd_guard = guard;
   if (grad_acc) {
     p.sgd_acc = grad_acc;
     p.sgd_acc_ld = ld_acc;
-    return launch_gemm256p_tn_acc_sgdp(p, nwg, (hipStream_t)stream);
+    return guard ? launch_gemm256p_tn_acc_sgdp<true>(p, nwg, (hipStream_t)stream)
+                 : launch_gemm256p_tn_acc_sgdp<false>(p, nwg, (hipStream_t)stream);
   }
-  return launch_gemm256p_tn_sgdp(p, nwg, (hipStream_t)stream);
+  return guard ? launch_gemm256p_tn_sgdp<true>(p, nwg, (hipStream_t)stream)
+               : launch_gemm256p_tn_sgdp<false>(p, nwg, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -2443,7 +2465,18 @@ int drn_gemm_tn_sgd(const void* A, const void* Bt, void* grad_bucket, int M, int
                     long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w, const void* seg_dev,
                     float momentum, int first_step, float grad_scale, void* stream) {
   return gemm_tn_sgd_entry(A, Bt, grad_bucket, nullptr, 0, M, N, K, kb_rows, lda, ldb, ldc, weights, momentum_buf, shadow, ld_w,
-                           seg_dev, momentum, first_step, grad_scale, stream);
+                           seg_dev, momentum, first_step, grad_scale, nullptr, stream);
+}
+
+// drn_gemm_tn_sgd under the anomaly guard: guard -> state[0] of drn_loss_guard (device memory, read once per workgroup).
+// guard[0] == 0: drn_gemm_tn_sgd's bits.  guard[0] != 0: weights, momentum_buf and shadow keep their bits (the shadow is
+// re-derived from the weights it mirrors: it must hold bf16(weights), as FusedSGD keeps it); grad_bucket is written as ever.
+int drn_gemm_tn_sgd_guard(const void* A, const void* Bt, void* grad_bucket, int M, int N, int K, int kb_rows, long lda, long ldb,
+                          long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w, const void* seg_dev,
+                          float momentum, int first_step, float grad_scale, const int* guard, void* stream) {
+  if (!guard) return DRN_ERR_ARG;
+  return gemm_tn_sgd_entry(A, Bt, grad_bucket, nullptr, 0, M, N, K, kb_rows, lda, ldb, ldc, weights, momentum_buf, shadow, ld_w,
+                           seg_dev, momentum, first_step, grad_scale, guard, stream);
 }
 
 // The closing micro-step of a gradient-accumulation window (WSL.ITER_SIZE > 1: projects/WSL/tools/train_net.py:100-113 - every
@@ -2455,7 +2488,17 @@ int drn_gemm_tn_acc_sgd(const void* A, const void* Bt, const float* grad_acc, vo
                         const void* seg_dev, float momentum, int first_step, float grad_scale, void* stream) {
   if (!grad_acc || ld_acc < N) return DRN_ERR_ARG;
   return gemm_tn_sgd_entry(A, Bt, grad_bucket, grad_acc, ld_acc, M, N, K, kb_rows, lda, ldb, ldc, weights, momentum_buf, shadow,
-                           ld_w, seg_dev, momentum, first_step, grad_scale, stream);
+                           ld_w, seg_dev, momentum, first_step, grad_scale, nullptr, stream);
+}
+
+// drn_gemm_tn_acc_sgd under the anomaly guard (as drn_gemm_tn_sgd_guard)
+int drn_gemm_tn_acc_sgd_guard(const void* A, const void* Bt, const float* grad_acc, void* grad_bucket, int M, int N, int K,
+                              int kb_rows, long lda, long ldb, long ld_acc, long ldc, float* weights, float* momentum_buf,
+                              void* shadow, long ld_w, const void* seg_dev, float momentum, int first_step, float grad_scale,
+                              const int* guard, void* stream) {
+  if (!grad_acc || ld_acc < N || !guard) return DRN_ERR_ARG;
+  return gemm_tn_sgd_entry(A, Bt, grad_bucket, grad_acc, ld_acc, M, N, K, kb_rows, lda, ldb, ldc, weights, momentum_buf, shadow,
+                           ld_w, seg_dev, momentum, first_step, grad_scale, guard, stream);
 }
 
 // NHWC conv + per-channel affine (folded FrozenBN or bias) + optional residual + optional ReLU; `dtype` is the element

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void act_kernel(ActParams p) {
         if (!BWD) {
           for (int s = 0; s < p.splits; ++s) v += p.in[(long)s * p.split_stride + (long)m * p.ld_in + n];
           if (p.bias) v += p.bias[n];
-          if (p.relu) v = fmaxf(v, 0.f);
+          if (p.relu) v = relu_nan(v);
           if (p.mask) v *= p.mask[(long)m * p.N + n];
           else if (p.drop_p > 0.f) v *= drn_drop_mult(drop, (unsigned long long)m * p.N + n);
         } else {
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void act_vec_kernel(ActParams p) {
         if (p.bias) v += bias4;
         if (p.relu) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+          for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
         }
         if (p.mask) v *= *(const f32x4v*)(p.mask + (long)m * p.N + n0);
         else if (p.drop_p > 0.f) {
@@ -617,10 +617,10 @@ __device__ __forceinline__ void wsddn_stage_body(const WsddnParams& p, const Log
   for (int j = 0; j < CPL; ++j) {
     g[j] = 0.f;
     if (!ok[j]) continue;
-    const float s_ = fminf(fmaxf(S[j], 1e-6f), 1.0f - 1e-6f);
+    const float s_ = clamp_nan(S[j], 1e-6f, 1.0f - 1e-6f);  // (a NaN score reaches the loss, as through torch.clamp)
     const float y = p.gt_onehot[img * K + col[j]];
     // F.binary_cross_entropy: -(y*log(s) + (1-y)*log(1-s)), logs clamped at -100
-    lsum += -(y * fmaxf(logf(s_), -100.f) + (1.f - y) * fmaxf(logf(1.f - s_), -100.f));
+    lsum += -(y * fmax_nan(logf(s_), -100.f) + (1.f - y) * fmax_nan(logf(1.f - s_), -100.f));
     g[j] = (S[j] >= 1e-6f && S[j] <= 1.0f - 1e-6f) ? (-(y / s_) + (1.f - y) / (1.f - s_)) * norm * p.loss_scale : 0.f;
     if (blk == 0 && ph == 0) p.img_scores[img * K + col[j]] = s_;
   }
@@ -1105,11 +1105,17 @@ __device__ __forceinline__ float clip_grad(float d, float clip_value, float coef
   return d;
 }
 
-template <bool SHADOW, int GDT, bool NT = true, int CLIP = CLIP_NONE>
+// GUARD (the anomaly guard): guard -> state[0] of drn_loss_guard; non-zero = the step's loss was not finite, and the whole
+// launch leaves w / mom / shadow as they are (a wave-uniform early exit: no load, no store).
+template <bool SHADOW, int GDT, bool NT = true, int CLIP = CLIP_NONE, bool GUARD = false>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, float* __restrict__ mom,
                                                   const void* __restrict__ gv, long goff, bf16_t* __restrict__ shadow,
                                                   const SgdSeg* segs, int nseg, float momentum, int first_step,
-                                                  float grad_scale, float clip_value, const float* seg_norms) {
+                                                  float grad_scale, float clip_value, const float* seg_norms,
+                                                  const int* guard) {
+  if constexpr (GUARD) {
+    if (guard[0] != 0) return;
+  }
   using GT = typename ElemOf<GDT>::type;
   const GT* g = (const GT*)gv - goff;  // arena element j <-> g[j]
   for (int s = blockIdx.y; s < nseg; s += gridDim.y) {
@@ -1176,12 +1182,15 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, float* 
 // kernel each, run_fc1_tail), and each slab's update starts the moment its GEMM is queued.  Arithmetic, access width
 // and cache policy are sgd_kernel's; only the index map differs (a row of the block is a contiguous run of cols / 4
 // 16-byte vectors).  c0, cols, ld, sg.off and goff are multiples of 4 (launcher).
-template <bool SHADOW, int GDT, int CLIP = CLIP_NONE>
+template <bool SHADOW, int GDT, int CLIP = CLIP_NONE, bool GUARD = false>
 __global__ __launch_bounds__(256) void sgd_block_kernel(float* __restrict__ w, float* __restrict__ mom,
                                                         const void* __restrict__ gv, long goff, bf16_t* __restrict__ shadow,
                                                         const SgdSeg* seg, int r0, int rows, int c0, int cols, long ld,
                                                         float momentum, int first_step, float grad_scale, float clip_value,
-                                                        const float* seg_norms) {
+                                                        const float* seg_norms, const int* guard) {
+  if constexpr (GUARD) {
+    if (guard[0] != 0) return;  // (as sgd_kernel)
+  }
   using GT = typename ElemOf<GDT>::type;
   const GT* g = (const GT*)gv - goff;
   const SgdSeg sg = seg[0];
@@ -1665,7 +1674,7 @@ int drn_apply_deltas(const float* deltas, long ld_d, const float* boxes, float* 
 // bf16 array with the arena's flat layout, refreshed in the same pass.
 static int sgd_step_launch(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
                            int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
-                           int clip_mode, float clip_value, const float* seg_norms, void* stream) {
+                           int clip_mode, float clip_value, const float* seg_norms, const int* guard, void* stream) {
   if (!weights || !momentum_buf || !grads || !segs_dev || nseg < 1) return DRN_ERR_ARG;
   if (shadow && shadow_dtype != DRN_BF16) return DRN_ERR_ARG;
   if (grad_dtype != DRN_F32 && grad_dtype != DRN_BF16) return DRN_ERR_ARG;
@@ -1673,9 +1682,14 @@ static int sgd_step_launch(float* weights, float* momentum_buf, const void* grad
   if (clip_mode != CLIP_NONE && !(clip_value >= 0.f)) return DRN_ERR_ARG;
   dim3 grid(g_tune.sgd_grid, nseg < 32 ? nseg : 32), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define SGD_LAUNCH(SH, GD, CL)                                                                                   \
-  hipLaunchKernelGGL((sgd_kernel<SH, GD, true, CL>), grid, block, 0, st, weights, momentum_buf, grads, grad_off, \
-                     (bf16_t*)shadow, (const SgdSeg*)segs_dev, nseg, momentum, first_step, grad_scale, clip_value, seg_norms)
+#define SGD_LAUNCH_G(SH, GD, CL, GU)                                                                                 \
+  hipLaunchKernelGGL((sgd_kernel<SH, GD, true, CL, GU>), grid, block, 0, st, weights, momentum_buf, grads, grad_off, \
+                     (bf16_t*)shadow, (const SgdSeg*)segs_dev, nseg, momentum, first_step, grad_scale, clip_value,   \
+                     seg_norms, guard)
+#define SGD_LAUNCH(SH, GD, CL)                                                         \
+  do {                                                                                 \
+    if (guard) SGD_LAUNCH_G(SH, GD, CL, true); else SGD_LAUNCH_G(SH, GD, CL, false);   \
+  } while (0)
 #define SGD_LAUNCH_CL(SH, GD)                                        \
   do {                                                               \
     if (clip_mode == CLIP_VALUE) SGD_LAUNCH(SH, GD, CLIP_VALUE);     \
@@ -1686,6 +1700,7 @@ static int sgd_step_launch(float* weights, float* momentum_buf, const void* grad
   else { if (grad_dtype == DRN_BF16) SGD_LAUNCH_CL(false, DRN_BF16); else SGD_LAUNCH_CL(false, DRN_F32); }
 #undef SGD_LAUNCH_CL
 #undef SGD_LAUNCH
+#undef SGD_LAUNCH_G
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
@@ -1694,7 +1709,7 @@ int drn_sgd_step(float* weights, float* momentum_buf, const void* grads, int gra
                  int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
                  void* stream) {
   return sgd_step_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, segs_dev, nseg, momentum,
-                         first_step, grad_scale, CLIP_NONE, 0.f, nullptr, stream);
+                         first_step, grad_scale, CLIP_NONE, 0.f, nullptr, nullptr, stream);
 }
 
 // drn_sgd_step with SOLVER.CLIP_GRADIENTS applied to g * grad_scale, per segment (sgd_kernel's CLIP parameter): clip_mode 0 = none
@@ -1703,7 +1718,18 @@ int drn_sgd_step_clip(float* weights, float* momentum_buf, const void* grads, in
                       int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
                       int clip_mode, float clip_value, const float* seg_norms, void* stream) {
   return sgd_step_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, segs_dev, nseg, momentum,
-                         first_step, grad_scale, clip_mode, clip_value, seg_norms, stream);
+                         first_step, grad_scale, clip_mode, clip_value, seg_norms, nullptr, stream);
+}
+
+// drn_sgd_step_clip under the anomaly guard: guard -> state[0] of drn_loss_guard (device memory).  guard[0] == 0:
+// drn_sgd_step_clip's bits; guard[0] != 0: weights, momentum_buf and shadow keep their bits.  A skipped FIRST step leaves
+// momentum_buf untouched - the caller creates it as zeros, and a later first_step = 0 update on zeros computes what a first step would.
+int drn_sgd_step_guard(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
+                       int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
+                       int clip_mode, float clip_value, const float* seg_norms, const int* guard, void* stream) {
+  if (!guard) return DRN_ERR_ARG;
+  return sgd_step_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, segs_dev, nseg, momentum,
+                         first_step, grad_scale, clip_mode, clip_value, seg_norms, guard, stream);
 }
 
 // workspace of drn_grad_norms: one fp32 partial per (segment, x workgroup).  Host-only.
@@ -1745,7 +1771,7 @@ int drn_grad_norms(const void* grads, int grad_dtype, long grad_off, const void*
 static int sgd_step_block_launch(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off,
                                  void* shadow, int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld,
                                  float momentum, int first_step, float grad_scale, int clip_mode, float clip_value,
-                                 const float* seg_norms, void* stream) {
+                                 const float* seg_norms, const int* guard, void* stream) {
   if (!weights || !momentum_buf || !grads || !seg_dev || r0 < 0 || rows < 0 || c0 < 0 || cols < 0 || ld < c0 + cols)
     return DRN_ERR_ARG;
   if (shadow && shadow_dtype != DRN_BF16) return DRN_ERR_ARG;
@@ -1757,10 +1783,14 @@ static int sgd_step_block_launch(float* weights, float* momentum_buf, const void
   if (rows == 0 || cols == 0) return DRN_OK;
   dim3 grid(g_tune.sgd_grid), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define SGD_LAUNCH(SH, GD, CL)                                                                                          \
-  hipLaunchKernelGGL((sgd_block_kernel<SH, GD, CL>), grid, block, 0, st, weights, momentum_buf, grads, grad_off,        \
+#define SGD_LAUNCH_G(SH, GD, CL, GU)                                                                                    \
+  hipLaunchKernelGGL((sgd_block_kernel<SH, GD, CL, GU>), grid, block, 0, st, weights, momentum_buf, grads, grad_off,    \
                      (bf16_t*)shadow, (const SgdSeg*)seg_dev, r0, rows, c0, cols, ld, momentum, first_step, grad_scale, \
-                     clip_value, seg_norms)
+                     clip_value, seg_norms, guard)
+#define SGD_LAUNCH(SH, GD, CL)                                                         \
+  do {                                                                                 \
+    if (guard) SGD_LAUNCH_G(SH, GD, CL, true); else SGD_LAUNCH_G(SH, GD, CL, false);   \
+  } while (0)
 #define SGD_LAUNCH_CL(SH, GD)                                        \
   do {                                                               \
     if (clip_mode == CLIP_VALUE) SGD_LAUNCH(SH, GD, CLIP_VALUE);     \
@@ -1771,6 +1801,7 @@ static int sgd_step_block_launch(float* weights, float* momentum_buf, const void
   else { if (grad_dtype == DRN_BF16) SGD_LAUNCH_CL(false, DRN_BF16); else SGD_LAUNCH_CL(false, DRN_F32); }
 #undef SGD_LAUNCH_CL
 #undef SGD_LAUNCH
+#undef SGD_LAUNCH_G
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
@@ -1779,7 +1810,7 @@ int drn_sgd_step_block(float* weights, float* momentum_buf, const void* grads, i
                        int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
                        int first_step, float grad_scale, void* stream) {
   return sgd_step_block_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, seg_dev, r0, rows, c0,
-                               cols, ld, momentum, first_step, grad_scale, CLIP_NONE, 0.f, nullptr, stream);
+                               cols, ld, momentum, first_step, grad_scale, CLIP_NONE, 0.f, nullptr, nullptr, stream);
 }
 
 // drn_sgd_step_block with the clipping of drn_sgd_step_clip; seg_norms -> the norm of the ONE tensor seg_dev describes
@@ -1788,15 +1819,66 @@ int drn_sgd_step_block_clip(float* weights, float* momentum_buf, const void* gra
                             int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
                             void* stream) {
   return sgd_step_block_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, seg_dev, r0, rows, c0,
-                               cols, ld, momentum, first_step, grad_scale, clip_mode, clip_value, seg_norms, stream);
+                               cols, ld, momentum, first_step, grad_scale, clip_mode, clip_value, seg_norms, nullptr, stream);
+}
+
+// drn_sgd_step_block_clip under the anomaly guard (as drn_sgd_step_guard)
+int drn_sgd_step_block_guard(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
+                             int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
+                             int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
+                             const int* guard, void* stream) {
+  if (!guard) return DRN_ERR_ARG;
+  return sgd_step_block_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, seg_dev, r0, rows, c0,
+                               cols, ld, momentum, first_step, grad_scale, clip_mode, clip_value, seg_norms, guard, stream);
 }
 
 __global__ void counter_add_kernel(unsigned long long* c, unsigned long long inc) {
   if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += inc;
 }
 
-}  // extern "C"  (kernel above needs C++ linkage)
+// The anomaly guard's check (detectron2/engine/train_loop.py:252-258: `losses = sum(loss_dict.values())`, then
+// `if not torch.isfinite(losses).all(): raise FloatingPointError`): one wave forms the fp32 sum of the step's loss scalars in
+// list order and tests isfinite(sum) - +inf + -inf and an overflowing sum of finite terms are bad, as there.  The pointers
+// travel in the kernel arguments (no device table to keep alive or to re-upload).  state[0] = skip flag (read by the guarded
+// update kernels), [1] = calls seen, [2] = index of the first bad call or -1, [3] = bad calls; written by lane 0 alone.
+enum { GUARD_RAISE = 1, GUARD_SKIP = 2, GUARD_MAX_LOSSES = 16 };
+struct LossPtrs { const float* p[GUARD_MAX_LOSSES]; };
+__global__ __launch_bounds__(64) void loss_guard_kernel(LossPtrs lp, int n, int mode, int window_first, int* state) {
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < GUARD_MAX_LOSSES; ++i)  // (unrolled: static indices into the argument block)
+    if (i < n) sum = sum + lp.p[i][0];
+  const bool bad = (__builtin_bit_cast(unsigned, sum) & 0x7f800000u) == 0x7f800000u;  // !isfinite: inf or NaN
+  if (threadIdx.x == 0) {
+    const int flag = state[0], calls = state[1], first_bad = state[2];
+    // raise: sticky for ever.  skip: a bad micro-step discards its whole accumulation window and nothing more
+    const bool keep = mode == GUARD_RAISE ? flag != 0 : (flag != 0 && !window_first);
+    state[0] = (bad || keep) ? 1 : 0;
+    state[1] = calls + 1;
+    if (bad) {
+      if (first_bad < 0) state[2] = calls;
+      state[3] = state[3] + 1;
+    }
+  }
+}
+
+}  // extern "C"  (kernels above need C++ linkage)
 extern "C" {
+
+// The device-side anomaly guard: losses = HOST array of n <= 16 device pointers to the step's fp32 loss scalars (copied into the
+// launch's arguments); mode 1 = raise (the flag is sticky), 2 = skip (flag = bad_now || (flag && !window_first)); state =
+// int32[4] in device memory, initialised by the caller to {0, 0, -1, 0}.  One launch of one wave; no sync, no allocation.
+int drn_loss_guard(const void* const* losses, int n, int mode, int window_first, int* state, void* stream) {
+  if (!losses || !state || n < 1 || n > GUARD_MAX_LOSSES || (mode != GUARD_RAISE && mode != GUARD_SKIP)) return DRN_ERR_ARG;
+  LossPtrs lp;
+  for (int i = 0; i < GUARD_MAX_LOSSES; ++i) {
+    lp.p[i] = (const float*)losses[i < n ? i : 0];
+    if (!lp.p[i]) return DRN_ERR_ARG;
+  }
+  hipLaunchKernelGGL(loss_guard_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lp, n, mode, window_first ? 1 : 0, state);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
 
 // device-side counter (dropout seed) advanced inside the stream / graph: no host involvement per step
 int drn_counter_add(unsigned long long* counter, unsigned long long inc, void* stream) {

@@ -412,7 +412,7 @@ __global__ __launch_bounds__(512) void pp8_kernel(Pp8Params p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float x = c[i][j][4 * q + e] + bi[e];
-          if (p.relu) x = fmaxf(x, 0.f);
+          if (p.relu) x = relu_nan(x);  // (the heads: a NaN must reach the loss, drn_common.h)
           v[e] = x;
         }
         if (fast_bits) {

@@ -10,7 +10,9 @@
                                tensors and then each fc6-gradient slab are on the wire while the next dW slab is
                                still being computed; unused bbox_pred parameters never enter a bucket.
   Trainer.run_step             projects/WSL/tools/train_net.py:65-117 (ITER_SIZE accumulation, loss dict keys) without
-                               the per-iteration host syncs (anomaly check / metric gather are deferred)."""
+                               the per-iteration host syncs (metric gather is deferred; the anomaly check of
+                               train_loop.py:252-258 is either deferred - check_finite() - or, with
+                               FusedSGD(nonfinite="raise" | "skip"), made on the device in front of every update: LossGuard)."""
 import bisect
 import collections
 import math
@@ -40,12 +42,54 @@ def window_position(it, iter_size, start_iter=0):
     return Window(first=(it == start_iter or (it - 1) % n == 0), closing=(it % n == 0))
 
 
+NONFINITE_MODES = ("off", "raise", "skip")
+_NONFINITE_MSG = "Loss became infinite or NaN at iteration={}!"  # detectron2/engine/train_loop.py:252-258
+
+
+class LossGuard:
+    """Device side of the anomaly guard (FusedSGD(nonfinite=...)): the int32 state drn_loss_guard keeps - [0] the skip flag every
+    guarded update kernel reads, [1] checks seen, [2] first bad check or -1, [3] bad checks - and what the head engine needs to
+    issue the check behind its loss tail.  window_first: whether the NEXT check opens a WSL.ITER_SIZE window (mode "skip": a bad
+    micro-step discards its whole window and nothing more); iter0: the training iteration of check 0, for the message."""
+
+    def __init__(self, mode, device):
+        self.mode = mode
+        self.code = ops.GUARD_RAISE if mode == "raise" else ops.GUARD_SKIP
+        self.state = ops.loss_guard_state(device)
+        self.window_first = True
+        self.iter0 = 0
+
+    def check(self, loss_list):
+        ops.loss_guard(loss_list, self.code, self.window_first, self.state)
+
+    def open_window(self):
+        """a captured check has its window_first frozen: clear the flag on the stream in front of the window's first replay
+        instead (mode "skip"; the flag of "raise" is sticky) and capture every check with window_first = 0 - the same rule,
+        flag = bad_now or (flag and not window_first)"""
+        if self.mode == "skip":
+            self.state[:1].zero_()
+
+    def read(self):
+        flag, calls, first_bad, bad = self.state.cpu().tolist()  # the one small D2H read
+        return {"mode": self.mode, "skip": bool(flag), "calls": calls, "first_bad": first_bad, "bad": bad,
+                "first_bad_iteration": None if first_bad < 0 else self.iter0 + first_bad}
+
+
 class FusedSGD:
     def __init__(self, model, base_lr, momentum, weight_decay, bias_lr_factor=1.0, weight_decay_bias=None,
-                 weight_decay_norm=0.0, nesterov=False, clip_type=None, clip_value=1.0, norm_type=2.0):
+                 weight_decay_norm=0.0, nesterov=False, clip_type=None, clip_value=1.0, norm_type=2.0, nonfinite="off"):
         """clip_type / clip_value / norm_type: SOLVER.CLIP_GRADIENTS (detectron2/solver/build.py:19-90) - every parameter is
         clipped on its own right before the update, on the gradient the update sees (g * grad_scale): "value" clamps to
-        +-clip_value, "norm" scales by min(clip_value / (||g||_norm_type + 1e-6), 1); None = no clipping (every launch as before)."""
+        +-clip_value, "norm" scales by min(clip_value / (||g||_norm_type + 1e-6), 1); None = no clipping (every launch as before).
+        nonfinite: the anomaly guard (detectron2/engine/train_loop.py:252-258 checks every iteration's summed loss in front of
+        the optimizer).  "off" (default): every launch as before.  "raise" / "skip": a one-wave kernel behind the loss tail tests
+        isfinite(sum of the losses) on the device, and every update kernel of the step - the fused fc6 dW + SGD launch included -
+        leaves weights, momentum and shadow bit-unchanged when it is not.  "raise": the flag is sticky, so the state stays that of
+        the last finite iteration until Trainer.check_finite() / state_dict() raise the reference's FloatingPointError with the
+        first bad iteration.  "skip": the bad window is dropped and training goes on; guard_state() reports the counts."""
+        if nonfinite not in NONFINITE_MODES:
+            raise ValueError("nonfinite=%r: one of %s" % (nonfinite, ", ".join(repr(m) for m in NONFINITE_MODES)))
+        self.nonfinite = nonfinite
         if nesterov:
             raise DrnError("nesterov SGD is not used by any DRN-WSOD config")
         if clip_type not in (None, "value", "norm"):
@@ -62,6 +106,9 @@ class FusedSGD:
         self.momentum = momentum
         wdb = weight_decay if weight_decay_bias is None else weight_decay_bias
         self.engine.ensure(next(model.roi_heads.parameters()).device)
+        # (the guard lives on the engine that issues its check; off = the attribute is None and no launch changes)
+        self._guard = LossGuard(nonfinite, self.engine.arena_w.device) if nonfinite != "off" else None
+        self.engine.loss_guard = self._guard
         self.param_groups = []
         for name, p, off, n, used in self.engine.segments:
             is_bias = name.endswith(".bias")
@@ -102,6 +149,29 @@ class FusedSGD:
                 if hasattr(m, "invalidate_packs"):
                     m.invalidate_packs()
 
+    @property
+    def _gs(self):
+        """guard= argument of every update launch: the guard's device state, or None (the unguarded entry points)"""
+        return None if self._guard is None else self._guard.state
+
+    def guard_state(self):
+        """The anomaly guard's device state as a dict (one small D2H read, which waits for the work queued so far): mode, skip
+        (the flag now), calls, first_bad (check index or -1), bad, first_bad_iteration.  None with nonfinite="off"."""
+        return None if self._guard is None else self._guard.read()
+
+    def raise_if_nonfinite(self):
+        """nonfinite="raise": FloatingPointError with the reference's message if a loss has been non-finite since the guard was
+        enabled - naming the FIRST such iteration, whose update and every later one were skipped.  Returns guard_state()."""
+        st = self.guard_state()
+        if st is not None and st["mode"] == "raise" and st["first_bad"] >= 0:
+            raise FloatingPointError(_NONFINITE_MSG.format(st["first_bad_iteration"]))
+        return st
+
+    def _refuse_guard_multi_rank(self, what):
+        raise DrnError("FusedSGD(nonfinite=%r) with %s: the ranks would have to agree on the skip flag before any of them "
+                       "updates, which is not built (single process only; use nonfinite='off' and Trainer.check_finite())"
+                       % (self.nonfinite, what))
+
     def _segs_bb(self):
         bb = self._bb
         key = tuple((g["lr"], g["weight_decay"]) for g in bb["groups"])
@@ -123,7 +193,7 @@ class FusedSGD:
             bb["mom"] = torch.zeros_like(bb["w"])
         segs, nseg = self._segs_bb()
         ops.sgd_step(bb["w"], bb["mom"], bb["g"], segs, nseg, self.momentum, self._steps == 0, grad_scale,
-                     clip=self._clip(bb["g"], segs, nseg, grad_scale, self._nseg))
+                     clip=self._clip(bb["g"], segs, nseg, grad_scale, self._nseg), guard=self._gs)
         for m in self.model.backbone.modules():
             if hasattr(m, "invalidate_packs"):
                 m.invalidate_packs()  # updated in place: the packed compute copies of the conv weights are stale
@@ -219,6 +289,11 @@ class FusedSGD:
         iter_size = int(iter_size)
         if iter_size < 1:
             raise DrnError("iter_size must be >= 1")
+        if self._guard is not None:
+            if dp is not None and dp.exchange:
+                self._refuse_guard_multi_rank("a gradient exchange")
+            if exchange == "fc6_kshard":
+                self._refuse_guard_multi_rank("the K-sharded fc6")
         self._bucket_clip = None
         if self.clip_type is not None:
             # SOLVER.CLIP_GRADIENTS on this schedule: value clipping, single process, iter_size 1, fc6 dW unfused (the fused
@@ -380,7 +455,7 @@ class FusedSGD:
         k1 = n // D1
         view = lambda t: t[o: o + n].view(D1, k1)[:, :n_main]
         return ops.gemm_tn_sgd(dPT, A[:, :n_main], D1, n_main, Mp, M, gw[:, :n_main], view(e.arena_w), view(self._mom),
-                               view(e.arena_s), segs, self.momentum, self._steps == 0, 1.0)
+                               view(e.arena_s), segs, self.momentum, self._steps == 0, 1.0, guard=self._gs)
 
     def _fused_fc1_tn_acc(self, dPT, A, D1, n_main, Mp, M, ga, gw):
         """closing micro-iteration of a window: bucket = bf16(fp32 accumulator + dW) and the update, one launch
@@ -395,7 +470,8 @@ class FusedSGD:
         k1 = n // D1
         view = lambda t: t[o: o + n].view(D1, k1)[:, :n_main]
         return ops.gemm_tn_acc_sgd(dPT, A[:, :n_main], D1, n_main, Mp, M, ga[:, :n_main], gw[:, :n_main], view(e.arena_w),
-                                   view(self._mom), view(e.arena_s), segs, self.momentum, self._steps == 0, 1.0)
+                                   view(self._mom), view(e.arena_s), segs, self.momentum, self._steps == 0, 1.0,
+                                   guard=self._gs)
 
     def _fused_fc1_cols(self, dPT, A, D1, k0, k1, Kp, kb, gw):
         """K-sharded fc6: dW of the owned columns k0:k1 and their update as one launch (drn_gemm_tn_sgd; N = 2 / 4: the
@@ -648,7 +724,7 @@ class FusedSGD:
             k1 = self.model.roi_heads.box_head.fc1.weight.shape[1]
             ops.sgd_step_block(e.arena_w, self._mom, bucket if bucket is not None else e.arena_g, segs, r0, r1 - r0, c0,
                                c1 - c0, k1, self.momentum, self._steps == 0, 1.0 / world, shadow=e.arena_s,
-                               grad_off=e._seg["fc1.weight"][0] if bucket is not None else 0, clip=clip)
+                               grad_off=e._seg["fc1.weight"][0] if bucket is not None else 0, clip=clip, guard=self._gs)
             if getattr(self, "_kshard", False):
                 self._master_stale = True  # the other ranks' columns of fc1.weight / momentum / shadow live on those ranks
             return
@@ -658,15 +734,16 @@ class FusedSGD:
             k1 = self.model.roi_heads.box_head.fc1.weight.shape[1]
             segs, nseg = self._bucket_table(("fc1", a, b))
             ops.sgd_step(e.arena_w, self._mom, bucket, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
-                         shadow=e.arena_s, grad_off=e._seg["fc1.weight"][0] + a * k1, clip=clip)
+                         shadow=e.arena_s, grad_off=e._seg["fc1.weight"][0] + a * k1, clip=clip, guard=self._gs)
             self._master_stale = True  # momentum (and, with a bf16 shadow, the fp32 master) of the other ranks' rows
             return
         if bucket is not None:
             ops.sgd_step(e.arena_w, self._mom, bucket, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
-                         shadow=e.arena_s, grad_off=0 if what == "small" else e._seg["fc1.weight"][0], clip=clip)
+                         shadow=e.arena_s, grad_off=0 if what == "small" else e._seg["fc1.weight"][0], clip=clip,
+                         guard=self._gs)
         else:
             ops.sgd_step(e.arena_w, self._mom, e.arena_g, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
-                         shadow=e.arena_s, clip=clip)
+                         shadow=e.arena_s, clip=clip, guard=self._gs)
         if what == "small" and hasattr(e, "sh"):
             e.refresh_transposes()  # fc7 / predictor weights are final for this step: rebuild their K-major twins here
             e._transposes_fresh = True
@@ -715,7 +792,7 @@ class FusedSGD:
             self._mom = torch.zeros_like(e.arena_w)
         segs, nseg = self._segs()
         ops.sgd_step(e.arena_w, self._mom, e.arena_g, segs, nseg, self.momentum, self._steps == 0, grad_scale,
-                     shadow=e.arena_s, clip=self._clip(e.arena_g, segs, nseg, grad_scale, 0))
+                     shadow=e.arena_s, clip=self._clip(e.arena_g, segs, nseg, grad_scale, 0), guard=self._gs)
         if self._bb is not None:
             self._step_bb(grad_scale)
         self._steps += 1
@@ -725,6 +802,7 @@ class FusedSGD:
         """torch.optim.SGD's checkpoint content in this optimizer's flat form: the momentum arena of the heads, the
         momentum arena of a trainable trunk (FREEZE_AT < 5), the step count and the per-group hyper-parameters."""
         bb = self._bb
+        self.raise_if_nonfinite()  # nonfinite="raise": a run whose loss went non-finite is not saved as healthy
         self.sync_master()  # sharded exchange: collect the rows the other ranks own
         return {"momentum_buffer": None if self._mom is None else self._mom.detach().cpu(),
                 "bb_momentum_buffer": None if bb is None or bb["mom"] is None else bb["mom"].detach().cpu(),
@@ -782,12 +860,14 @@ class FusedSGD:
             self._segs_bb()
 
 
-def build_optimizer(cfg, model):
-    """detectron2/solver/build.py:93-137, with maybe_add_gradient_clipping (:62-90) folded into the optimizer's own kernels."""
+def build_optimizer(cfg, model, nonfinite="off"):
+    """detectron2/solver/build.py:93-137, with maybe_add_gradient_clipping (:62-90) folded into the optimizer's own kernels.
+    nonfinite: FusedSGD's anomaly guard ("off" / "raise" / "skip"); an argument, not a config key - the merged configs are the
+    reference's."""
     clip = cfg.SOLVER.CLIP_GRADIENTS
-    kw = {}
+    kw = {"nonfinite": nonfinite}
     if clip.ENABLED:
-        kw = dict(clip_type=clip.CLIP_TYPE, clip_value=clip.CLIP_VALUE, norm_type=clip.NORM_TYPE)
+        kw.update(clip_type=clip.CLIP_TYPE, clip_value=clip.CLIP_VALUE, norm_type=clip.NORM_TYPE)
     return FusedSGD(model, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, cfg.SOLVER.WEIGHT_DECAY, cfg.SOLVER.BIAS_LR_FACTOR,
                     cfg.SOLVER.WEIGHT_DECAY_BIAS, cfg.SOLVER.WEIGHT_DECAY_NORM, cfg.SOLVER.NESTEROV, **kw)
 
@@ -1085,6 +1165,15 @@ class Trainer:
         self.iter = self.start_iter = int(start_iter)
         self.storage = EventStorage(self.start_iter)
         self.last_losses = None
+        self._guard = getattr(self.optimizer, "_guard", None)
+        if self._guard is not None:
+            if getattr(self.dp, "exchange", False):
+                self.optimizer._refuse_guard_multi_rank("a gradient exchange")
+            self._anchor_guard()
+
+    def _anchor_guard(self):
+        """the guard counts checks; the next one is iteration self.iter"""
+        self._guard.iter0 = self.iter - self._guard.read()["calls"]
 
     def resume_or_load(self, checkpointer, path="", resume=True):
         """DefaultTrainer.resume_or_load (detectron2/engine/defaults.py:304-319): load `path` or, with resume=True and a
@@ -1094,6 +1183,8 @@ class Trainer:
         if resume and checkpointer.has_checkpoint():
             self.iter = self.start_iter = int(extra.get("iteration", -1)) + 1
             self.storage = EventStorage(self.start_iter)
+            if self._guard is not None:
+                self._anchor_guard()
         return extra
 
     def run_step(self):
@@ -1106,6 +1197,8 @@ class Trainer:
 
         data = self._lookahead if getattr(self, "_lookahead", None) is not None else draw()
         self._lookahead = draw()
+        if self._guard is not None:  # the check is issued behind the loss tail, inside the forward
+            self._guard.window_first = window_position(self.iter, self.iter_size, self.start_iter).first
         with self.storage:
             loss_dict = self.model(data)
         if hasattr(self.model, "prefetch_features"):
@@ -1137,7 +1230,12 @@ class Trainer:
         return loss_dict
 
     def check_finite(self):
-        """SimpleTrainer._detect_anomaly (train_loop.py:252-258), on demand instead of every iteration."""
+        """SimpleTrainer._detect_anomaly (train_loop.py:252-258), on demand instead of every iteration.  With the optimizer's
+        anomaly guard on (FusedSGD(nonfinite=...)) the device state is read instead of the last losses: "raise" raises the
+        reference's message with the FIRST bad iteration (whose update, and every later one, was skipped); "skip" never raises.
+        Returns the guard's state (None with the guard off)."""
+        if self._guard is not None:
+            return self.optimizer.raise_if_nonfinite()
         if self.last_losses is not None:
             tot = float(sum(v.detach() for v in self.last_losses.values()))
             if not math.isfinite(tot):

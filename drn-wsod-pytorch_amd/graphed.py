@@ -239,6 +239,13 @@ class GraphedTrainStep(_StaticInputs):
             raise DrnError("K-sharded fc6 holds collectives in the pooling piece, behind the fc6 GEMM and in the dW tail: "
                            "GraphedTrainStep(split_tail=True, eager_fc6=True, lookahead >= 2 or trunk_pairs)")
         self.engine.defer_fc1_tail = self.split_tail
+        # the anomaly guard (FusedSGD(nonfinite=...)): its check and the guard pointer of every update are captured with the
+        # heads graph.  ITER_SIZE 1: every step opens its window.  N > 1: ONE captured graph serves every position of the window,
+        # so the position cannot be a captured argument - the host opens the window instead (LossGuard.open_window)
+        self._guard = getattr(optimizer, "_guard", None)
+        if self._guard is not None:
+            self._guard.window_first = self.iter_size == 1
+            self._guard.iter0 = self._start_iter - self._guard.read()["calls"]
 
     def release(self):
         """give the fc6 operand sets back (they may grow again); the captured graphs of this object must not be replayed
@@ -528,6 +535,8 @@ class GraphedTrainStep(_StaticInputs):
             self._win = window_position(self._iter, self.iter_size, self._start_iter)
             self.opt.set_window(self._win)
             self._iter += 1
+            if self._guard is not None and self._win.first:
+                self._guard.open_window()
         if self._GA is None:
             if not self._primed:
                 return self.prime(batch, next_batch)
@@ -574,6 +583,13 @@ class GraphedFullStep(_StaticInputs):
                            "train on their local gradients and diverge" % dist.get_world_size())
         self.dp = parallel if (parallel is not None and parallel.exchange) else None
         self._comm = None
+        # the anomaly guard: the check (heads forward) and the guard pointer of both arenas' updates are captured; ITER_SIZE 1
+        # here, so every step opens its window
+        self._guard = getattr(optimizer, "_guard", None)
+        if self._guard is not None:
+            if self.dp is not None:
+                optimizer._refuse_guard_multi_rank("a gradient exchange")
+            self._guard.window_first = True
 
     def _stage(self, batch):
         self._stage_labels(batch)

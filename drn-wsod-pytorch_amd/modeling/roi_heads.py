@@ -994,8 +994,16 @@ class _HeadEngine:
             state["fg"] = dict(hook=fg_hook, rois=rois, obj=objectness, feat_shape=tuple(feat_nhwc.shape),
                                argmax=pooled.get("argmax"))
         self._last_state = state
+        self._guard_check(state["loss_list"])
         outs = _TrainFn.apply(self.anchor, self, state)
         return dict(zip(loss_names, outs)), state
+
+    def _guard_check(self, loss_list):
+        """the anomaly guard's check (FusedSGD(nonfinite=...); drn_loss_guard), right behind the loss tail: on the stream that
+        computed the losses and in front of the first event an optimizer stream waits on (the backward records those)"""
+        g = getattr(self, "loss_guard", None)
+        if g is not None:
+            g.check(loss_list)
 
     # ---- CSCROIHeads -----------------------------------------------------------------------------------
     def _forward_csc(self, w, col, M, dtype, rois, objectness, feat_nhwc, pooled, gt, img_off, n_img, masks, drop_p,
@@ -1020,6 +1028,7 @@ class _HeadEngine:
         if fg_hook is not None:
             state["fg"] = dict(fg, hook=fg_hook)
         self._last_state = state
+        self._guard_check(state["loss_list"])
         outs = _TrainFn.apply(self.anchor, self, state)
         return dict(zip(["loss_cls_pos", "loss_cls_neg"], outs)), state
 

@@ -159,19 +159,24 @@ def gemm_tn(A, Bt, M, N, K, kb_rows, out=None, splits=1, accumulate=False):
     return out
 
 
-def gemm_tn_sgd(A, Bt, M, N, K, kb_rows, bucket, weights, mom, shadow, seg_dev, momentum, first_step, grad_scale=1.0):
+def gemm_tn_sgd(A, Bt, M, N, K, kb_rows, bucket, weights, mom, shadow, seg_dev, momentum, first_step, grad_scale=1.0,
+                guard=None):
     """drn_gemm_tn_sgd: bucket[M, N] (bf16) = A[M,:K] @ Bt[:K,:N] and, in the same launch, the SGD step of weights[M, N] /
     mom / shadow (2-D views with a common row pitch) with that gradient.  Returns False when the shape is outside the
-    kernel's class (nothing was launched: run gemm_tn + sgd_step_block instead)."""
+    kernel's class (nothing was launched: run gemm_tn + sgd_step_block instead).  guard: the int32 state of loss_guard()
+    (drn_gemm_tn_sgd_guard: a set flag leaves weights / mom / shadow bit-unchanged); None = the unguarded entry point."""
     assert A.dtype == torch.bfloat16 and Bt.dtype == torch.bfloat16 and bucket.dtype == torch.bfloat16
     assert weights.dtype == torch.float32 and mom.dtype == torch.float32 and shadow.dtype == torch.bfloat16
     assert _2d(weights) == _2d(mom) == _2d(shadow)
     if GEMM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = C.lib().drn_gemm_tn_sgd(C.ptr(A), C.ptr(Bt), C.ptr(bucket), M, N, K, int(kb_rows), _2d(A), _2d(Bt), _2d(bucket),
-                                 C.ptr(weights), C.ptr(mom), C.ptr(shadow), _2d(weights), C.ptr(seg_dev), float(momentum),
-                                 int(bool(first_step)), float(grad_scale), C.stream())
+    args = (C.ptr(A), C.ptr(Bt), C.ptr(bucket), M, N, K, int(kb_rows), _2d(A), _2d(Bt), _2d(bucket), C.ptr(weights),
+            C.ptr(mom), C.ptr(shadow), _2d(weights), C.ptr(seg_dev), float(momentum), int(bool(first_step)), float(grad_scale))
+    if guard is None:
+        rc = C.lib().drn_gemm_tn_sgd(*args, C.stream())
+    else:
+        rc = C.lib().drn_gemm_tn_sgd_guard(*args, _guard_ptr(guard), C.stream())
     if rc == -3:
         return False
     if rc != 0:
@@ -183,10 +188,10 @@ def gemm_tn_sgd(A, Bt, M, N, K, kb_rows, bucket, weights, mom, shadow, seg_dev, 
 
 
 def gemm_tn_acc_sgd(A, Bt, M, N, K, kb_rows, grad_acc, bucket, weights, mom, shadow, seg_dev, momentum, first_step,
-                    grad_scale=1.0):
+                    grad_scale=1.0, guard=None):
     """drn_gemm_tn_acc_sgd: gemm_tn_sgd with bucket = bf16(grad_acc + A @ Bt) - the closing micro-step of a gradient-accumulation
     window; grad_acc [M, N] fp32 (a 2-D view, read only).  Returns False outside the kernel's shape class (nothing was launched:
-    run gemm_tn(accumulate=True) + cast2d + sgd_step_block instead)."""
+    run gemm_tn(accumulate=True) + cast2d + sgd_step_block instead).  guard as in gemm_tn_sgd (drn_gemm_tn_acc_sgd_guard)."""
     assert A.dtype == torch.bfloat16 and Bt.dtype == torch.bfloat16 and bucket.dtype == torch.bfloat16
     assert grad_acc.dtype == torch.float32 and grad_acc.dim() == 2 and grad_acc.stride(1) == 1
     assert weights.dtype == torch.float32 and mom.dtype == torch.float32 and shadow.dtype == torch.bfloat16
@@ -194,9 +199,13 @@ def gemm_tn_acc_sgd(A, Bt, M, N, K, kb_rows, grad_acc, bucket, weights, mom, sha
     if GEMM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = C.lib().drn_gemm_tn_acc_sgd(C.ptr(A), C.ptr(Bt), C.ptr(grad_acc), C.ptr(bucket), M, N, K, int(kb_rows), _2d(A), _2d(Bt),
-                                     _2d(grad_acc), _2d(bucket), C.ptr(weights), C.ptr(mom), C.ptr(shadow), _2d(weights),
-                                     C.ptr(seg_dev), float(momentum), int(bool(first_step)), float(grad_scale), C.stream())
+    args = (C.ptr(A), C.ptr(Bt), C.ptr(grad_acc), C.ptr(bucket), M, N, K, int(kb_rows), _2d(A), _2d(Bt), _2d(grad_acc),
+            _2d(bucket), C.ptr(weights), C.ptr(mom), C.ptr(shadow), _2d(weights), C.ptr(seg_dev), float(momentum),
+            int(bool(first_step)), float(grad_scale))
+    if guard is None:
+        rc = C.lib().drn_gemm_tn_acc_sgd(*args, C.stream())
+    else:
+        rc = C.lib().drn_gemm_tn_acc_sgd_guard(*args, _guard_ptr(guard), C.stream())
     if rc == -3:
         return False
     if rc != 0:
@@ -835,6 +844,36 @@ def sum_small(x, scale=1.0):
     return out
 
 
+GUARD_RAISE, GUARD_SKIP = 1, 2  # mode of drn_loss_guard
+GUARD_MAX_LOSSES = 16
+
+
+def loss_guard_state(device):
+    """int32[4] state of loss_guard() as the first call expects it: {skip flag 0, calls 0, first bad call -1, bad calls 0}"""
+    return torch.tensor([0, 0, -1, 0], dtype=torch.int32, device=device)
+
+
+def _guard_ptr(state):
+    assert state.dtype == torch.int32 and state.numel() >= 1 and state.is_contiguous()
+    return C.ptr(state)
+
+
+def loss_guard(losses, mode, window_first, state):
+    """drn_loss_guard: one wave sums the step's fp32 loss scalars (device tensors of one element, at most 16) in list order and
+    folds isfinite(sum) into `state` (loss_guard_state()): [0] the skip flag the guarded updates read, [1] calls, [2] first bad
+    call or -1, [3] bad calls.  mode GUARD_RAISE: sticky flag; GUARD_SKIP: flag = bad_now or (flag and not window_first).  No
+    synchronisation; capturable."""
+    n = len(losses)
+    if not 1 <= n <= GUARD_MAX_LOSSES:
+        raise C.DrnError("loss_guard(): %d loss scalars (1 .. %d are built)" % (n, GUARD_MAX_LOSSES))
+    for t in losses:
+        assert t.dtype == torch.float32 and t.numel() == 1 and t.is_cuda
+    assert state.dtype == torch.int32 and state.numel() == 4 and state.is_contiguous()
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in losses])
+    C.call("drn_loss_guard", ctypes.cast(ptrs, ctypes.c_void_p), n, int(mode), int(bool(window_first)), C.ptr(state),
+           C.stream())
+
+
 CLIP_NONE, CLIP_VALUE, CLIP_NORM = 0, 1, 2  # clip_mode of drn_sgd_step_clip / drn_sgd_step_block_clip
 _NORM_TYPES = {1.0: 1, 2.0: 2, float("inf"): 0}  # NORM_TYPE -> norm_type of drn_grad_norms
 
@@ -876,14 +915,20 @@ def _clip_args(clip):
 
 
 def sgd_step(weights, momentum_buf, grads, segs_dev, nseg, momentum, first_step, grad_scale=1.0, shadow=None,
-             grad_off=0, clip=None):
+             grad_off=0, clip=None, guard=None):
     """grads: the fp32 gradient arena, or (grad_off > 0) a bucket buffer - fp32 or bf16 - whose element 0 is arena
     element grad_off.  clip = (mode, value, norms): SOLVER.CLIP_GRADIENTS per segment on g * grad_scale (drn_sgd_step_clip;
-    norms = grad_norms() over the same table for CLIP_NORM); None = drn_sgd_step."""
+    norms = grad_norms() over the same table for CLIP_NORM); None = drn_sgd_step.  guard: the int32 state of loss_guard()
+    (drn_sgd_step_guard: a set flag leaves weights / momentum_buf / shadow bit-unchanged); None = the unguarded entry points."""
     if HBM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    if clip is None:
+    if guard is not None:
+        C.call("drn_sgd_step_guard", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
+               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
+               int(first_step), float(grad_scale), *_clip_args(clip if clip is not None else (CLIP_NONE, 0.0, None)),
+               _guard_ptr(guard), C.stream())
+    elif clip is None:
         C.call("drn_sgd_step", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
                C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
                int(first_step), float(grad_scale), C.stream())
@@ -898,14 +943,20 @@ def sgd_step(weights, momentum_buf, grads, segs_dev, nseg, momentum, first_step,
 
 
 def sgd_step_block(weights, momentum_buf, grads, seg_dev, r0, rows, c0, cols, ld, momentum, first_step, grad_scale=1.0,
-                   shadow=None, grad_off=0, clip=None):
+                   shadow=None, grad_off=0, clip=None, guard=None):
     """drn_sgd_step on rows r0 .. r0+rows, columns c0 .. c0+cols of the [., ld] tensor described by seg_dev (ONE
     {offset, count, lr, wd} entry on the device); weights / momentum_buf / shadow are the flat arenas, grads as in
-    sgd_step.  clip as in sgd_step (drn_sgd_step_block_clip); its norms = ONE element, the norm of that tensor."""
+    sgd_step.  clip as in sgd_step (drn_sgd_step_block_clip); its norms = ONE element, the norm of that tensor; guard as in
+    sgd_step (drn_sgd_step_block_guard)."""
     if HBM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    if clip is None:
+    if guard is not None:
+        C.call("drn_sgd_step_block_guard", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype),
+               int(grad_off), C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0),
+               int(rows), int(c0), int(cols), int(ld), float(momentum), int(first_step), float(grad_scale),
+               *_clip_args(clip if clip is not None else (CLIP_NONE, 0.0, None)), _guard_ptr(guard), C.stream())
+    elif clip is None:
         C.call("drn_sgd_step_block", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
                C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0), int(rows), int(c0),
                int(cols), int(ld), float(momentum), int(first_step), float(grad_scale), C.stream())

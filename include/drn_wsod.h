@@ -532,6 +532,47 @@ int drn_sgd_step_block_clip(float* weights, float* momentum_buf, const void* gra
                             int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
                             void* stream);
 
+/* ---- the anomaly guard: skip the update on a non-finite loss -----------------------------------------------------------------
+ * The reference checks every iteration's summed loss on the host in front of the optimizer (detectron2/engine/train_loop.py:252-258:
+ * `losses = sum(loss_dict.values())`, `if not torch.isfinite(losses).all(): raise FloatingPointError(...)`), so its weights and
+ * momentum are always those of the last finite iteration.  Here the update runs inside the backward, so the check runs on the device
+ * and the update kernels read its verdict.
+ *
+ * drn_loss_guard: losses = HOST array of n (1 .. 16) device pointers to the step's fp32 loss scalars, copied into the launch's
+ * arguments.  One wave forms their fp32 sum in list order and tests isfinite(sum) - NaN, +-inf, inf + -inf and an overflowing sum of
+ * finite terms are bad, as in the reference.  state = int32[4] in device memory, set to {0, 0, -1, 0} by the caller before the first call:
+ *   state[0]  skip flag, read by the guarded update kernels below       state[1]  calls seen
+ *   state[2]  index (0-based) of the first bad call, or -1              state[3]  number of bad calls
+ * mode 1 (raise): the flag, once set, stays set.  mode 2 (skip): flag = bad_now || (flag && !window_first) - window_first marks the
+ * first micro-step of a WSL.ITER_SIZE window, so a bad micro-step discards its whole window and nothing more.  state is written with
+ * ordinary stores by one lane.  No synchronisation, no allocation, capturable (the pointers, mode and window_first are frozen into a
+ * captured launch).  Errors: DRN_ERR_ARG (null pointer, n outside 1 .. 16, mode outside 1 .. 2).
+ *
+ * The guarded updates take one more argument, guard -> state[0] (device memory; NULL is DRN_ERR_ARG), and are otherwise
+ * drn_sgd_step_clip / drn_sgd_step_block_clip / drn_gemm_tn_sgd / drn_gemm_tn_acc_sgd - shape classes and errors included:
+ *   guard[0] == 0   bit-identical to the unguarded entry point
+ *   guard[0] != 0   weights, momentum_buf and shadow keep their bits; the GEMM forms still write grad_bucket
+ * The flat and block kernels leave by a wave-uniform early exit.  The fused dW + SGD launch keeps all three loads and three stores of
+ * every chunk (its mainloop's counted waits depend on them) and stores back what it loaded: w, momentum, and bf16(w) for the shadow -
+ * the shadow must hold bf16(weights) on entry, which is what every update entry point leaves there.
+ * A skipped FIRST step (first_step = 1) leaves momentum_buf untouched: callers create it as zeros, and a later first_step = 0 update
+ * on zeros computes exactly what a first step would (momentum * 0 + d == d). */
+int drn_loss_guard(const void* const* losses, int n, int mode, int window_first, int* state, void* stream);
+int drn_sgd_step_guard(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
+                       int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
+                       int clip_mode, float clip_value, const float* seg_norms, const int* guard, void* stream);
+int drn_sgd_step_block_guard(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
+                             int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
+                             int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
+                             const int* guard, void* stream);
+int drn_gemm_tn_sgd_guard(const void* A, const void* Bt, void* grad_bucket, int M, int N, int K, int kb_rows, long lda, long ldb,
+                          long ldc, float* weights, float* momentum_buf, void* shadow, long ld_w, const void* seg_dev,
+                          float momentum, int first_step, float grad_scale, const int* guard, void* stream);
+int drn_gemm_tn_acc_sgd_guard(const void* A, const void* Bt, const float* grad_acc, void* grad_bucket, int M, int N, int K,
+                              int kb_rows, long lda, long ldb, long ld_acc, long ldc, float* weights, float* momentum_buf,
+                              void* shadow, long ld_w, const void* seg_dev, float momentum, int first_step, float grad_scale,
+                              const int* guard, void* stream);
+
 /* ---- inference tail -------------------------------------------------------------------------- */
 
 /* fast_rcnn_inference_single_image, fast_rcnn.py:88-141 + batched_nms, detectron2/layers/nms.py:10-29. */
