@@ -76,6 +76,8 @@ _SIGS = {
     "drn_gemm_tn_acc_sgd_guard": "pppp" + "iiii" + "llll" + "ppplp" + "fif" + "pp",
     "drn_detect_topk": "ppiii" + "ffff" + "i" + "pl" + "i" + "ppp",
     "drn_detect_gather": "plippippppp",
+    "drn_coco_match": "pppi" + "pppp" + "iii" + "pi" + "pi" + "i" + "pli" + "pppppppp" + "p",
+    "drn_coco_accumulate": "pppppi" + "piiii" + "pi" + "pi" + "pli" + "ppp" + "p",
     "drn_csc_cpg": "piiiiippp",
     "drn_csc_weights": "piifpipiiifppp",
     "drn_csc_loss": "pliiiippppiiipplp",

@@ -7,14 +7,22 @@ Same arithmetic, different plumbing: predictions stay in memory (the reference w
 it back); they still go through the reference's text quantisation (score %.3f, box %.1f after the +1 shift of
 xmin / ymin, :58-66) because the ranking and the overlaps are computed on those rounded numbers.  Ground truth is read
 from VOC XML files or handed over as {image_id: [(class name, difficult, [xmin, ymin, xmax, ymax])]}.
-Pinned by tests/golden/voc_eval.npz (the reference's functions on a synthetic annotation set)."""
+Pinned by tests/golden/voc_eval.npz (the reference's functions on a synthetic annotation set).
+
+COCO box AP: `COCOEvaluator` (detectron2/evaluation/coco_evaluation.py:33-306, bbox only) and `instances_to_coco_json`
+(:308-367).  The reference hands its predictions to COCOeval_opt, whose two expensive stages are native C++
+(detectron2/layers/csrc/cocoeval/cocoeval.cpp); here both run on the device (ops.coco_match / ops.coco_accumulate,
+csrc/cocoeval.hip) and the predictions never leave it before the three result arrays are read back.  Pinned by
+tests/golden/coco_eval.npz (the unmodified C++ on synthetic, tie-heavy annotation sets)."""
+import json
 import os
 import xml.etree.ElementTree as ET
 from collections import OrderedDict, defaultdict
 
 import numpy as np
 
-__all__ = ["PascalVOCDetectionEvaluator", "parse_rec", "voc_ap", "voc_eval", "voc_eval_corloc", "format_prediction"]
+__all__ = ["PascalVOCDetectionEvaluator", "parse_rec", "voc_ap", "voc_eval", "voc_eval_corloc", "format_prediction",
+           "COCOEvaluator", "instances_to_coco_json", "coco_params", "coco_summarize", "derive_coco_results"]
 
 
 def parse_rec(filename):
@@ -175,3 +183,174 @@ class PascalVOCDetectionEvaluator:
         ret["bbox CorLoc"] = {"CL": np.mean(list(m.values())), "CL50": m[50], "CL75": m[75]}
         ret["per_class"] = {"AP50": dict(zip(self._class_names, aps[50])), "CL50": dict(zip(self._class_names, cls_[50]))}
         return ret
+
+
+# ---- COCO box AP ------------------------------------------------------------------------------------------------------
+
+def coco_params():
+    """pycocotools' Params for iouType = 'bbox' (cocoeval.py), to the letter, in fp64: IoU thresholds, recall thresholds,
+    maxDets, area ranges.  The kernels hard-code none of them."""
+    return dict(iouThrs=np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True),
+                recThrs=np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True),
+                maxDets=[1, 10, 100],
+                areaRng=[[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]])
+
+
+def coco_summarize(precision, recall, params=None):
+    """the 12 `stats` of pycocotools' COCOeval.summarize: the mean over the entries > -1, -1 if there are none"""
+    p = params or coco_params()
+    iou, last = np.asarray(p["iouThrs"]), len(p["maxDets"]) - 1
+
+    def one(ap, thr=None, a=0, m=last):
+        s = precision if ap else recall
+        if thr is not None:
+            s = s[np.where(thr == iou)[0]]
+        s = s[:, :, :, a, m] if ap else s[:, :, a, m]
+        s = s[s > -1]
+        return -1.0 if s.size == 0 else float(np.mean(s))
+
+    return np.array([one(1), one(1, .5), one(1, .75), one(1, a=1), one(1, a=2), one(1, a=3), one(0, m=0), one(0, m=1),
+                     one(0), one(0, a=1), one(0, a=2), one(0, a=3)])
+
+
+def derive_coco_results(stats, precision, class_names=None):
+    """COCOEvaluator._derive_coco_results for 'bbox' (coco_evaluation.py:239-306): x 100, NaN for -1, per-category AP"""
+    metrics = ["AP", "AP50", "AP75", "APs", "APm", "APl"]
+    results = {m: float(stats[i] * 100 if stats[i] >= 0 else "nan") for i, m in enumerate(metrics)}
+    if class_names is None or len(class_names) <= 1:
+        return results
+    assert len(class_names) == precision.shape[2]
+    for idx, name in enumerate(class_names):
+        pr = precision[:, :, idx, 0, -1]  # area range "all", the largest maxDets
+        pr = pr[pr > -1]
+        results["AP-" + "{}".format(name)] = float(np.mean(pr) * 100) if pr.size else float("nan")
+    return results
+
+
+def instances_to_coco_json(instances, img_id):
+    """coco_evaluation.py:308-367 for boxes: [{"image_id", "category_id" (the contiguous class), "bbox" (XYWH, converted in
+    float32), "score"}] for writing result files"""
+    if len(instances) == 0:
+        return []
+    b = instances.pred_boxes.tensor.detach().cpu().numpy().astype(np.float32)
+    xywh = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1).tolist()
+    scores, classes = instances.scores.tolist(), instances.pred_classes.tolist()
+    return [{"image_id": img_id, "category_id": classes[k], "bbox": xywh[k], "score": scores[k]} for k in range(len(scores))]
+
+
+class COCOEvaluator:
+    """reset() / process(inputs, outputs) / evaluate() like the reference's COCOEvaluator, box AP only (useCats = 1).
+
+    `annotations`: a COCO-format dict or the path of a json file; `images[*].id`, `categories[*].{id, name}` and
+    `annotations[*].{image_id, category_id, bbox, area, iscrowd}` are used.  Every image of the file counts, with or
+    without detections.  The predicted contiguous class c stands for the c-th smallest dataset category id (detectron2's
+    thing_dataset_id_to_contiguous_id); `class_names` defaults to the categories' names in that order.
+    `gather`: callable(per-rank dict of host arrays) -> list of such dicts on the main process, None elsewhere.
+
+    process() keeps the predictions as device tensors and never synchronises; evaluate() concatenates them, converts the
+    boxes XYXY -> XYWH in float32 (coco_evaluation.py:323-325) and widens them to fp64, uploads the ground truth once,
+    runs order -> match -> order -> accumulate on the device and reads `precision` / `recall` / `scores` back."""
+
+    def __init__(self, annotations, class_names=None, gather=None, device="cuda"):
+        if not isinstance(annotations, dict):
+            with open(annotations) as f:
+                annotations = json.load(f)
+        self._img_ids = sorted(int(im["id"]) for im in annotations["images"])
+        cats = sorted(annotations["categories"], key=lambda c: int(c["id"]))
+        self._cat_ids = [int(c["id"]) for c in cats]
+        self._class_names = list(class_names) if class_names is not None else [str(c.get("name", c["id"])) for c in cats]
+        self._img_index = {iid: i for i, iid in enumerate(self._img_ids)}
+        cat_index = {cid: k for k, cid in enumerate(self._cat_ids)}
+        I, K = len(self._img_ids), len(self._cat_ids)
+        anns = [a for a in annotations["annotations"] if int(a["image_id"]) in self._img_index
+                and int(a["category_id"]) in cat_index]
+        pair = np.array([self._img_index[int(a["image_id"])] * K + cat_index[int(a["category_id"])] for a in anns], np.int64)
+        o = np.argsort(pair, kind="stable")  # grouped by (image, category); annotation order inside a pair
+        self._gt = dict(
+            box=np.array([anns[j]["bbox"] for j in o], np.float64).reshape(-1, 4),
+            area=np.array([anns[j]["area"] for j in o], np.float64),
+            crowd=np.array([1 if anns[j].get("iscrowd", 0) else 0 for j in o], np.uint8),
+            off=np.concatenate([[0], np.cumsum(np.bincount(pair, minlength=I * K))]).astype(np.int32))
+        self._gather, self._device = gather, device
+        self.params = coco_params()
+        self.stats, self.eval, self._mark = None, None, None
+        self.reset()
+
+    def reset(self):
+        self._boxes, self._scores, self._classes, self._images = [], [], [], []
+
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            iid = int(inp["image_id"])
+            if iid not in self._img_index:
+                raise ValueError("image_id %r is not in the annotation file" % (inp["image_id"],))
+            inst = out["instances"]
+            self._boxes.append(inst.pred_boxes.tensor.detach())
+            self._scores.append(inst.scores.detach())
+            self._classes.append(inst.pred_classes.detach())
+            self._images.append(self._img_index[iid])
+
+    def _local(self):
+        """this rank's predictions, concatenated on the device: boxes [n, 4] f32 XYXY, scores [n] f32, classes, image index"""
+        import torch
+
+        dev = self._boxes[0].device if self._boxes else torch.device(self._device)
+        if not self._boxes:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            return z((0, 4), torch.float32), z((0,), torch.float32), z((0,), torch.int32), z((0,), torch.int32)
+        counts = torch.tensor([b.shape[0] for b in self._boxes])
+        img = torch.repeat_interleave(torch.tensor(self._images, dtype=torch.int32), counts).to(dev)
+        return (torch.cat(self._boxes).float().reshape(-1, 4), torch.cat(self._scores).float(),
+                torch.cat(self._classes).to(torch.int32), img)
+
+    def evaluate(self):
+        import torch
+
+        from . import ops
+        from ._cabi import DrnError
+
+        box, score, cls, img = self._local()
+        if self._gather is not None:
+            parts = self._gather({"boxes": box.cpu().numpy(), "scores": score.cpu().numpy(), "classes": cls.cpu().numpy(),
+                                  "images": img.cpu().numpy()})
+            if parts is None:
+                return None  # not the main process
+            dev = torch.device(self._device)
+            up = lambda k, dt: torch.from_numpy(np.concatenate([np.asarray(p[k]) for p in parts])).to(dt).to(dev)
+            box, score = up("boxes", torch.float32).reshape(-1, 4), up("scores", torch.float32)
+            cls, img = up("classes", torch.int32), up("images", torch.int32)
+        dev = box.device
+        I, K, gt, p = len(self._img_ids), len(self._cat_ids), self._gt, self.params
+        ngt = np.diff(gt["off"])
+        max_gt = int(ngt.max()) if ngt.size else 0
+        if max_gt > ops.COCO_MAX_GT:
+            worst = int(ngt.argmax())
+            raise DrnError("COCOEvaluator: image %d / category %d has %d ground-truth boxes; the device matcher holds at most "
+                           "%d per (image, category) pair" % (self._img_ids[worst // K], self._cat_ids[worst % K], max_gt,
+                                                              ops.COCO_MAX_GT))
+        # coco_evaluation.py:323-325: XYXY -> XYWH in float32; the json round trip then makes python floats (fp64) of them
+        xywh = torch.stack([box[:, 0], box[:, 1], box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]], 1).double().contiguous()
+        pair = (img * K + cls).contiguous()
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)
+        iou_thr, rec_thr = t(p["iouThrs"], torch.float64), t(p["recThrs"], torch.float64)
+        area = t(np.array(p["areaRng"], np.float64), torch.float64)
+        max_dets = t(np.array(p["maxDets"], np.int32), torch.int32)
+        mark = self._mark or (lambda name: None)  # tools/coco_eval_bench.py records a HIP event per stage here
+        margs = (xywh, score.contiguous(), pair, t(gt["box"], torch.float64), t(gt["area"], torch.float64),
+                 t(gt["crowd"], torch.uint8), t(gt["off"], torch.int32), K, max_gt, iou_thr, area)
+        mark("start")
+        m = ops.coco_match(*margs, max_det=int(p["maxDets"][-1]), stages=1)
+        mark("sort (image, category)")
+        ops.coco_match(*margs, max_det=int(p["maxDets"][-1]), stages=2, out=m)
+        mark("match")
+        aargs = (m["s_score"], m["s_cat"], m["s_rank"], m["dm"], m["di"], m["npig"], I, K, iou_thr.shape[0], max_dets, rec_thr)
+        acc = ops.coco_accumulate(*aargs, stages=1)
+        mark("sort (category)")
+        ops.coco_accumulate(*aargs, stages=2, out=acc)
+        mark("accumulate")
+        precision, recall, scores = (acc[k].cpu().numpy() for k in ("precision", "recall", "scores"))  # the only sync
+        mark("read-back")
+        self.eval = {"params": p, "counts": [int(v) for v in precision.shape], "precision": precision, "recall": recall,
+                     "scores": scores}
+        self.stats = coco_summarize(precision, recall, p)
+        return OrderedDict(bbox=derive_coco_results(self.stats, precision, self._class_names))

@@ -1040,3 +1040,63 @@ def pcl_refine(logits, col0s, K, wsddn_scores, boxes, adj, onehot, dlogits):
         d.update(n_pc=n_pc[b: b + 1], probs=probs[b], loss=losses[b: b + 1])
         out.append(d)
     return out
+
+
+COCO_MAX_GT, COCO_MAX_AREAS, COCO_MAX_REC = 512, 4, 128  # include/drn_wsod.h DRN_COCO_MAX_*
+
+
+def _coco_ws_bytes(n, segments):
+    """DRN_COCO_WS_BYTES of include/drn_wsod.h"""
+    return 40 * (n + 4) + 8192 * ((n + 4095) // 4096 + 1) + 32 * segments + 1024
+
+
+def coco_match(det_box, det_score, det_pair, gt_box, gt_area, gt_crowd, gt_off, num_cats, max_gt, iou_thr, area_rng,
+               max_det=100, stages=3, out=None):
+    """COCO per-(image, category) matching (see include/drn_wsod.h, drn_coco_match).  det_box [n, 4] f64 XYWH, det_score
+    [n] f32, det_pair [n] i32 = image index * num_cats + category index; gt_box [G, 4] f64, gt_area [G] f64, gt_crowd [G]
+    u8, gt_off [P + 1] i32, all on the device; max_gt = most GT of one pair (a host number).  Returns a dict: order,
+    s_score, s_cat, s_rank, dm, di (int64 tensors holding the 64-bit words), npig [P, A], gt_ign [G].  stages = 1 / 2
+    with out = the dict of the stages = 1 call runs the ordering and the matching apart."""
+    dev = det_box.device
+    n, P, T, A = det_score.shape[0], gt_off.shape[0] - 1, iou_thr.shape[0], area_rng.shape[0]
+    assert det_box.dtype == torch.float64 and det_box.is_contiguous() and det_box.shape == (n, 4)
+    assert det_score.dtype == torch.float32 and det_pair.dtype == torch.int32 and det_pair.shape[0] == n
+    assert gt_box.dtype == torch.float64 and gt_area.dtype == torch.float64 and gt_crowd.dtype == torch.uint8
+    assert gt_off.dtype == torch.int32 and iou_thr.dtype == torch.float64 and area_rng.dtype == torch.float64
+    assert gt_box.is_contiguous() and area_rng.is_contiguous() and area_rng.shape == (A, 2) and P % num_cats == 0
+    G = gt_area.shape[0]
+    if out is None:
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        nbytes = _coco_ws_bytes(n, P)
+        out = dict(ws=e((nbytes,), torch.uint8), order=e((n,), torch.int32), s_score=e((n,), torch.float32),
+                   s_cat=e((n,), torch.int32), s_rank=e((n,), torch.int32), dm=e((n,), torch.int64),
+                   di=e((n,), torch.int64), npig=e((P, A), torch.int32), gt_ign=e((G,), torch.uint8))
+    o = out
+    C.call("drn_coco_match", C.ptr(det_box), C.ptr(det_score), C.ptr(det_pair), n, C.ptr(gt_box), C.ptr(gt_area),
+           C.ptr(gt_crowd), C.ptr(gt_off), P, int(num_cats), int(max_gt), C.ptr(iou_thr), T, C.ptr(area_rng), A,
+           int(max_det), C.ptr(o["ws"]), o["ws"].numel(), int(stages), C.ptr(o["order"]), C.ptr(o["s_score"]),
+           C.ptr(o["s_cat"]), C.ptr(o["s_rank"]), C.ptr(o["dm"]), C.ptr(o["di"]), C.ptr(o["npig"]), C.ptr(o["gt_ign"]),
+           C.stream())
+    return out
+
+
+def coco_accumulate(s_score, s_cat, s_rank, dm, di, npig, num_images, num_cats, num_iou, max_dets, rec_thr, stages=3,
+                    out=None):
+    """COCO precision / recall accumulation (drn_coco_accumulate) over the records coco_match returns.  npig [I * K, A]
+    i32, max_dets [M] i32, rec_thr [R] f64 on the device.  Returns a dict with precision / scores [T, R, K, A, M] and
+    recall [T, K, A, M] (f64, -1 where a category has no countable GT)."""
+    dev = npig.device
+    n, A, M, R, T, K = s_score.shape[0], npig.shape[1], max_dets.shape[0], rec_thr.shape[0], int(num_iou), int(num_cats)
+    assert s_score.dtype == torch.float32 and s_cat.dtype == torch.int32 and s_rank.dtype == torch.int32
+    assert dm.dtype == torch.int64 and di.dtype == torch.int64 and npig.dtype == torch.int32 and npig.is_contiguous()
+    assert max_dets.dtype == torch.int32 and rec_thr.dtype == torch.float64 and npig.shape[0] == num_images * K
+    assert s_cat.shape[0] == n and s_rank.shape[0] == n and dm.shape[0] == n and di.shape[0] == n
+    if out is None:
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(ws=e((_coco_ws_bytes(n, K),), torch.uint8), precision=e((T, R, K, A, M), torch.float64),
+                   scores=e((T, R, K, A, M), torch.float64), recall=e((T, K, A, M), torch.float64))
+    o = out
+    C.call("drn_coco_accumulate", C.ptr(s_score), C.ptr(s_cat), C.ptr(s_rank), C.ptr(dm), C.ptr(di), n, C.ptr(npig),
+           int(num_images), K, T, A, C.ptr(max_dets), M, C.ptr(rec_thr), R, C.ptr(o["ws"]), o["ws"].numel(), int(stages),
+           C.ptr(o["precision"]), C.ptr(o["scores"]), C.ptr(o["recall"]), C.stream())
+    return out

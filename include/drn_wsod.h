@@ -594,6 +594,51 @@ int drn_detect_gather(const void* workspace, long workspace_bytes, int cap, cons
 int drn_tta_accumulate(const float* boxes, const float* scores, float* acc_boxes, float* acc_scores, long n_boxes,
                        long n_scores, float sx, float sy, float flip_w, int first, int n_final, void* stream);
 
+/* ---- COCO box-AP evaluation (COCOEvaluator -> COCOeval_opt; detectron2/layers/csrc/cocoeval/cocoeval.cpp) -----------
+ * The two native stages of the reference's evaluator, EvaluateImages (:141-198) and Accumulate (:371-497), on the device
+ * and bit-identical to the C++: integer counts and single IEEE fp64 operations in its order.  The IoU is pycocotools'
+ * bbIou on [x, y, w, h] in fp64 (w = min(dx + dw, gx + gw) - max(dx, gx), zero overlap -> 0, i = w * h,
+ * u = crowd ? da : da + ga - i, i / u, uncontracted), restated because the reference tree does not hold it.  No threshold
+ * is built in: IoU thresholds, area ranges, maxDets and recall thresholds are device arrays the caller computes in fp64.
+ *
+ * Caps: at most DRN_COCO_MAX_GT ground-truth boxes per (image, category) pair (the pair's LDS layout), A <=
+ * DRN_COCO_MAX_AREAS area ranges with A * T <= 64 (one lane per (area range, IoU threshold)), R <= DRN_COCO_MAX_REC
+ * recall thresholds; beyond a cap both entry points answer DRN_ERR_UNSUPPORTED before anything is launched - nothing is
+ * truncated.  Scores are float32 (what a detector emits; the reference widens them to double, which keeps their order) and
+ * must not be NaN.  Workspaces: 16-byte aligned, DRN_COCO_WS_BYTES(n, segments) bytes, segments = P for the matching and
+ * K for the accumulation.  stages: bit 0 = the ordering passes, bit 1 = the matching / curve kernels; 3 runs both, and a
+ * call with bit 1 alone continues from the same workspace that a call with bit 0 alone left (used to time them apart).
+ *
+ * drn_coco_match: n detections in input order: det_box [n][4] fp64 XYWH, det_score [n], det_pair [n] = image index * K +
+ * category index (P = images * K pairs; indices are ranks of the ascending image / category ids).  Ground truth grouped
+ * by pair in annotation order: gt_box [G][4] fp64 XYWH, gt_area [G] (the annotation's area field), gt_crowd [G], gt_off
+ * [P + 1]; max_gt = the largest gt_off[p + 1] - gt_off[p], which the caller knows on the host.  iou_thr [T], area_rng
+ * [A][2] (inclusive bounds).  Output, detections ordered by (pair, descending score, input order - stable): order [n]
+ * (input index), s_score / s_cat / s_rank [n] (score, category index, rank inside the pair); dm / di [n]: bit a * T + t
+ * of dm = matched, of di = ignored, for area range a and threshold t (both 0 for rank >= max_det: the reference drops
+ * those detections); npig [P][A] = GT of the pair not ignored in area range a; gt_ign [G]: bit a = GT ignored
+ * (iscrowd || area < lo || area > hi). */
+#define DRN_COCO_MAX_GT 512
+#define DRN_COCO_MAX_AREAS 4
+#define DRN_COCO_MAX_REC 128
+#define DRN_COCO_WS_BYTES(n, segments) (40L * ((n) + 4) + 8192L * (((n) + 4095) / 4096 + 1) + 32L * (segments) + 1024L)
+int drn_coco_match(const double* det_box, const float* det_score, const int* det_pair, int n, const double* gt_box,
+                   const double* gt_area, const unsigned char* gt_crowd, const int* gt_off, int P, int K, int max_gt,
+                   const double* iou_thr, int T, const double* area_rng, int A, int max_det, void* workspace,
+                   long workspace_bytes, int stages, int* order, float* s_score, int* s_cat, int* s_rank,
+                   unsigned long long* dm, unsigned long long* di, int* npig, unsigned char* gt_ign, void* stream);
+/* drn_coco_accumulate: the records drn_coco_match left (any order that lists every image's pairs by ascending image index
+ * and every pair's detections by rank) and npig [I * K][A].  Per (category k, area range a, maxDet m, threshold t): the
+ * detections of category k with rank < max_dets[m] (max_dets [M], none above the matching's max_det), by descending score
+ * (stable), tp / fp counted over the not-ignored ones, recall = tp / npig, precision = tp / (tp + fp) (no eps: the C++,
+ * not pycocotools), the backward running-max envelope, sampled at lower_bound(recall, rec_thr[r]) (0 beyond the end).
+ * Writes precision / scores [T][R][K][A][M] and recall [T][K][A][M], fp64; entries stay -1 where the category has no
+ * not-ignored GT in the area range. */
+int drn_coco_accumulate(const float* s_score, const int* s_cat, const int* s_rank, const unsigned long long* dm,
+                        const unsigned long long* di, int n, const int* npig, int I, int K, int T, int A,
+                        const int* max_dets, int M, const double* rec_thr, int R, void* workspace, long workspace_bytes,
+                        int stages, double* precision, double* scores, double* recall, void* stream);
+
 /* ---- PCL refinement (PCLROIHeads) ------------------------------------------------------------------
  * The reference computes these on the HOST: the targets in numpy + scikit-learn after a device->host copy of the scores
  * (projects/WSL/wsl/modeling/roi_heads/third_party/pcl.py:26-200, called from fast_rcnn.py:1725-1745), the loss in C++ on
