@@ -78,6 +78,8 @@ _SIGS = {
     "drn_detect_gather": "plippippppp",
     "drn_coco_match": "pppi" + "pppp" + "iii" + "pi" + "pi" + "i" + "pli" + "pppppppp" + "p",
     "drn_coco_accumulate": "pppppi" + "piiii" + "pi" + "pi" + "pli" + "ppp" + "p",
+    "drn_voc_match": "pppi" + "ppp" + "iii" + "pi" + "pli" + "pppppppp" + "p",
+    "drn_voc_accumulate": "ppi" + "pppp" + "iii" + "pi" + "ii" + "pppp" + "p",
     "drn_csc_cpg": "piiiiippp",
     "drn_csc_weights": "piifpipiiifppp",
     "drn_csc_loss": "pliiiippppiiipplp",

@@ -8,6 +8,8 @@ it back); they still go through the reference's text quantisation (score %.3f, b
 xmin / ymin, :58-66) because the ranking and the overlaps are computed on those rounded numbers.  Ground truth is read
 from VOC XML files or handed over as {image_id: [(class name, difficult, [xmin, ymin, xmax, ymax])]}.
 Pinned by tests/golden/voc_eval.npz (the reference's functions on a synthetic annotation set).
+`PascalVOCDetectionEvaluator(..., device="cuda")` computes the same numbers on the device (ops.voc_match /
+ops.voc_accumulate, csrc/voceval.hip): the quantisation by formula, ties in processing order.
 
 COCO box AP: `COCOEvaluator` (detectron2/evaluation/coco_evaluation.py:33-306, bbox only) and `instances_to_coco_json`
 (:308-367).  The reference hands its predictions to COCOeval_opt, whose two expensive stages are native C++
@@ -138,9 +140,25 @@ def voc_eval_corloc(lines, annos, classname, ovthresh=0.5, use_07_metric=False):
 class PascalVOCDetectionEvaluator:
     """reset() / process(inputs, outputs) / evaluate() like the reference's evaluator.  `annotations` is either the
     dict described above or None, in which case `dirname/Annotations/{id}.xml` of the ids listed in
-    `dirname/ImageSets/Main/{split}.txt` are parsed."""
+    `dirname/ImageSets/Main/{split}.txt` are parsed.
 
-    def __init__(self, class_names, dirname=None, split="test", year=2007, annotations=None, gather=None):
+    `device=None` is the host path: process() copies every image's predictions to the host and formats the reference's
+    text lines, evaluate() runs voc_eval / voc_eval_corloc.  With a device ("cuda") the evaluator stays on it: process()
+    keeps the prediction tensors and never synchronises; evaluate() concatenates them, uploads the ground truth, runs
+    ops.voc_match / ops.voc_accumulate (csrc/voceval.hip) and reads `ap` / `corloc` back, its only synchronisation.  The
+    device path differs from the host path in what it defines and what it refuses:
+      * equal quantised ("%.3f") scores of a class rank in processing order - process() call order, then row order
+        (the line order of the reference's per-class file).  The host path's np.argsort is not stable, so on ties its
+        result is not a function of its inputs; without ties the two paths agree bit for bit (area AP: to summation order);
+      * boxes and scores must be float32 or narrower (fp64 raises TypeError: the exact quantisation needs a 24-bit
+        significand) and finite - the inference tail never emits a non-finite score, its `score > thresh` drops NaN;
+      * predicted classes must lie in [0, len(class_names));
+      * an unknown image_id raises ValueError in process() (host path: KeyError in evaluate());
+      * at most ops.VOC_MAX_GT ground-truth boxes per (image, class): evaluate() raises DrnError beyond.
+    `gather`: host path: callable(list-per-class dict) -> list of such dicts (one per rank); device path: callable(dict of
+    this rank's host arrays) -> list of such dicts in rank order; both: None on every process but the main one."""
+
+    def __init__(self, class_names, dirname=None, split="test", year=2007, annotations=None, gather=None, device=None):
         assert year in (2007, 2012), year
         self._class_names, self._is_2007 = list(class_names), year == 2007
         if annotations is None:
@@ -148,20 +166,63 @@ class PascalVOCDetectionEvaluator:
                 ids = [x.strip() for x in f.readlines()]
             annotations = {i: parse_rec(os.path.join(dirname, "Annotations", i + ".xml")) for i in ids}
         self._annos = annotations
-        self._gather = gather  # callable(list-per-class dict) -> list of such dicts (one per rank); None = single process
+        self._gather = gather  # None = single process
+        self._device, self._mark = device, None
+        if device is not None:
+            self._index_ground_truth()
         self.reset()
+
+    def _index_ground_truth(self):
+        """ground truth grouped by (image, class) pair - images in annotation-dict order, annotation order inside a pair -
+        with the pairs' offsets, and per class npos / npos_im as _class_gt counts them"""
+        self._img_ids = list(self._annos)
+        self._img_index = {iid: i for i, iid in enumerate(self._img_ids)}
+        cls_index = {name: k for k, name in enumerate(self._class_names)}
+        I, K = len(self._img_ids), len(self._class_names)
+        objs = [(i * K + cls_index[o[0]], o[1], o[2]) for i, iid in enumerate(self._img_ids) for o in self._annos[iid]
+                if o[0] in cls_index]
+        pair = np.array([o[0] for o in objs], np.int64)
+        o = np.argsort(pair, kind="stable")
+        diff = np.array([1 if objs[j][1] else 0 for j in o], np.uint8)
+        count = np.bincount(pair, minlength=I * K)
+        easy = np.bincount(pair[o], weights=1 - diff.astype(np.float64), minlength=I * K).astype(np.int64).reshape(I, K)
+        self._gt = dict(box=np.array([objs[j][2] for j in o], np.float64).reshape(-1, 4), diff=diff,
+                        off=np.concatenate([[0], np.cumsum(count)]).astype(np.int32),
+                        npos=easy.sum(0).astype(np.int32), npos_im=(easy > 0).sum(0).astype(np.int32))
 
     def reset(self):
         self._predictions = defaultdict(list)
+        self._boxes, self._scores, self._classes, self._images = [], [], [], []
 
     def process(self, inputs, outputs):
+        if self._device is not None:
+            return self._process_device(inputs, outputs)
         for inp, out in zip(inputs, outputs):
             inst = out["instances"]
             boxes = inst.pred_boxes.tensor.detach().cpu().numpy()
             for box, score, cls in zip(boxes, inst.scores.tolist(), inst.pred_classes.tolist()):
                 self._predictions[cls].append(format_prediction(inp["image_id"], score, box))
 
+    def _process_device(self, inputs, outputs):
+        import torch
+
+        narrow = (torch.float32, torch.float16, torch.bfloat16)
+        for inp, out in zip(inputs, outputs):
+            if inp["image_id"] not in self._img_index:
+                raise ValueError("image_id %r is not in the annotations" % (inp["image_id"],))
+            inst = out["instances"]
+            box, score = inst.pred_boxes.tensor.detach(), inst.scores.detach()
+            if box.dtype not in narrow or score.dtype not in narrow:
+                raise TypeError("PascalVOCDetectionEvaluator(device=...): boxes and scores must be float32 or narrower, got "
+                                "%s / %s" % (box.dtype, score.dtype))
+            self._boxes.append(box)
+            self._scores.append(score)
+            self._classes.append(inst.pred_classes.detach())
+            self._images.append(self._img_index[inp["image_id"]])
+
     def evaluate(self):
+        if self._device is not None:
+            return self._evaluate_device()
         parts = self._gather(self._predictions) if self._gather is not None else [self._predictions]
         if parts is None:
             return None  # not the main process
@@ -176,6 +237,9 @@ class PascalVOCDetectionEvaluator:
                 ap = voc_eval(lines, self._annos, name, thr / 100.0, self._is_2007)[2] if lines else 0.0
                 aps[thr].append(ap * 100)
                 cls_[thr].append(voc_eval_corloc(lines, self._annos, name, thr / 100.0, self._is_2007) * 100)
+        return self._results(aps, cls_)
+
+    def _results(self, aps, cls_):
         ret = OrderedDict()
         m = {t: np.mean(x) for t, x in aps.items()}
         ret["bbox"] = {"AP": np.mean(list(m.values())), "AP50": m[50], "AP75": m[75]}
@@ -183,6 +247,66 @@ class PascalVOCDetectionEvaluator:
         ret["bbox CorLoc"] = {"CL": np.mean(list(m.values())), "CL50": m[50], "CL75": m[75]}
         ret["per_class"] = {"AP50": dict(zip(self._class_names, aps[50])), "CL50": dict(zip(self._class_names, cls_[50]))}
         return ret
+
+    def _local(self):
+        """this rank's predictions, concatenated on the device in processing order: boxes [n, 4] f32 XYXY, scores [n] f32
+        (both widened exactly), classes, image index"""
+        import torch
+
+        dev = self._boxes[0].device if self._boxes else torch.device(self._device)
+        if not self._boxes:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            return z((0, 4), torch.float32), z((0,), torch.float32), z((0,), torch.int32), z((0,), torch.int32)
+        counts = torch.tensor([b.shape[0] for b in self._boxes])
+        img = torch.repeat_interleave(torch.tensor(self._images, dtype=torch.int32), counts).to(dev)
+        return (torch.cat([b.float().reshape(-1, 4) for b in self._boxes]), torch.cat([s.float() for s in self._scores]),
+                torch.cat(self._classes).to(torch.int32), img)
+
+    def _evaluate_device(self):
+        import torch
+
+        from . import ops
+        from ._cabi import DrnError
+
+        box, score, cls, img = self._local()
+        if self._gather is not None:
+            parts = self._gather({"boxes": box.cpu().numpy(), "scores": score.cpu().numpy(), "classes": cls.cpu().numpy(),
+                                  "images": img.cpu().numpy()})
+            if parts is None:
+                return None  # not the main process
+            dev = torch.device(self._device)
+            up = lambda k, dt: torch.from_numpy(np.concatenate([np.asarray(p[k]) for p in parts])).to(dt).to(dev)
+            box, score = up("boxes", torch.float32).reshape(-1, 4), up("scores", torch.float32)
+            cls, img = up("classes", torch.int32), up("images", torch.int32)
+        dev = box.device
+        K, gt = len(self._class_names), self._gt
+        ngt = np.diff(gt["off"])
+        max_gt = int(ngt.max()) if ngt.size else 0
+        if max_gt > ops.VOC_MAX_GT:
+            worst = int(ngt.argmax())
+            raise DrnError("PascalVOCDetectionEvaluator: image %s / class %s has %d ground-truth boxes; the device matcher "
+                           "holds at most %d per (image, class) pair" % (self._img_ids[worst // K],
+                                                                         self._class_names[worst % K], max_gt, ops.VOC_MAX_GT))
+        thrs = list(range(50, 100, 5))
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)
+        iou_thr = t(np.array([thr / 100.0 for thr in thrs], np.float64), torch.float64)
+        rec_thr = t(np.arange(0.0, 1.1, 0.1), torch.float64)  # voc_ap's own expression: not i / 10
+        margs = (box.contiguous(), score.contiguous(), (img * K + cls).contiguous(), t(gt["box"], torch.float64),
+                 t(gt["diff"], torch.uint8), t(gt["off"], torch.int32), K, max_gt, iou_thr)
+        npos, npos_im = t(gt["npos"], torch.int32), t(gt["npos_im"], torch.int32)
+        mark = self._mark or (lambda name: None)  # tools/voc_eval_bench.py records a HIP event per stage here
+        mark("start")
+        m = ops.voc_match(*margs, stages=1)
+        mark("quantise + rank")
+        ops.voc_match(*margs, stages=2, out=m)
+        mark("match")
+        acc = ops.voc_accumulate(m["tp"], m["fp"], m["cls_off"], m["hit"], npos, npos_im, len(thrs), rec_thr, self._is_2007)
+        mark("accumulate")
+        ap, corloc = acc["ap"].cpu().numpy(), acc["corloc"].cpu().numpy()  # the only sync
+        mark("read-back")
+        aps = {thr: [ap[ti, k] * 100 for k in range(K)] for ti, thr in enumerate(thrs)}
+        cls_ = {thr: [corloc[ti, k] * 100 for k in range(K)] for ti, thr in enumerate(thrs)}
+        return self._results(aps, cls_)
 
 
 # ---- COCO box AP ------------------------------------------------------------------------------------------------------

@@ -1100,3 +1100,58 @@ def coco_accumulate(s_score, s_cat, s_rank, dm, di, npig, num_images, num_cats, 
            int(num_images), K, T, A, C.ptr(max_dets), M, C.ptr(rec_thr), R, C.ptr(o["ws"]), o["ws"].numel(), int(stages),
            C.ptr(o["precision"]), C.ptr(o["scores"]), C.ptr(o["recall"]), C.stream())
     return out
+
+
+VOC_MAX_GT, VOC_MAX_REC = 128, 16  # include/drn_wsod.h DRN_VOC_MAX_*
+
+
+def _voc_ws_bytes(n, pairs):
+    """DRN_VOC_WS_BYTES of include/drn_wsod.h"""
+    return 24 * (n + 4) + 8192 * ((n + 4095) // 4096 + 1) + 4 * pairs + 1024
+
+
+def voc_match(det_box, det_score, det_pair, gt_box, gt_diff, gt_off, num_classes, max_gt, iou_thr, stages=3, out=None):
+    """PASCAL VOC ranking and matching (see include/drn_wsod.h, drn_voc_match).  det_box [n, 4] f32 XYXY as predicted,
+    det_score [n] f32, det_pair [n] i32 = image index * num_classes + class, in processing order; gt_box [G, 4] f64,
+    gt_diff [G] u8, gt_off [P + 1] i32, iou_thr [T] f64, all on the device; max_gt = most GT of one pair (a host number).
+    Returns a dict in rank order (class, descending quantised score, processing order on ties): order, s_score, ovmax,
+    jmax, tp / fp (int64 tensors holding the 64-bit words, bit t = threshold t), plus cls_off [K + 1] and hit [P].
+    stages = 1 / 2 with out = the dict of the stages = 1 call runs the ranking and the matching apart."""
+    dev = det_box.device
+    n, P, T = det_score.shape[0], gt_off.shape[0] - 1, iou_thr.shape[0]
+    K = int(num_classes)
+    assert det_box.dtype == torch.float32 and det_box.is_contiguous() and det_box.shape == (n, 4)
+    assert det_score.dtype == torch.float32 and det_pair.dtype == torch.int32 and det_pair.shape[0] == n
+    assert det_score.is_contiguous() and det_pair.is_contiguous() and gt_box.is_contiguous()
+    assert gt_box.dtype == torch.float64 and gt_diff.dtype == torch.uint8 and gt_box.shape == (gt_diff.shape[0], 4)
+    assert gt_off.dtype == torch.int32 and iou_thr.dtype == torch.float64 and P % K == 0
+    if out is None:
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(ws=e((_voc_ws_bytes(n, P),), torch.uint8), order=e((n,), torch.int32), s_score=e((n,), torch.float64),
+                   cls_off=e((K + 1,), torch.int32), ovmax=e((n,), torch.float64), jmax=e((n,), torch.int32),
+                   tp=e((n,), torch.int64), fp=e((n,), torch.int64), hit=e((P,), torch.int64))
+    o = out
+    C.call("drn_voc_match", C.ptr(det_box), C.ptr(det_score), C.ptr(det_pair), n, C.ptr(gt_box), C.ptr(gt_diff),
+           C.ptr(gt_off), P, K, int(max_gt), C.ptr(iou_thr), T, C.ptr(o["ws"]), o["ws"].numel(), int(stages),
+           C.ptr(o["order"]), C.ptr(o["s_score"]), C.ptr(o["cls_off"]), C.ptr(o["ovmax"]), C.ptr(o["jmax"]), C.ptr(o["tp"]),
+           C.ptr(o["fp"]), C.ptr(o["hit"]), C.stream())
+    return out
+
+
+def voc_accumulate(tp, fp, cls_off, hit, npos, npos_im, num_iou, rec_thr, use_07_metric, curve_at=None):
+    """PASCAL VOC AP and CorLoc (drn_voc_accumulate) over the records voc_match returns.  npos / npos_im [K] i32 and
+    rec_thr [R] f64 (np.arange(0.0, 1.1, 0.1); read by the VOC07 metric only) on the device.  Returns a dict with ap and
+    corloc [T, K] f64 and, with curve_at = a threshold index, rec / prec [n] of that threshold in rank order."""
+    dev = cls_off.device
+    n, K, T, R = tp.shape[0], cls_off.shape[0] - 1, int(num_iou), rec_thr.shape[0]
+    assert tp.dtype == torch.int64 and fp.dtype == torch.int64 and hit.dtype == torch.int64 and fp.shape[0] == n
+    assert cls_off.dtype == torch.int32 and npos.dtype == torch.int32 and npos_im.dtype == torch.int32
+    assert npos.shape[0] == K and npos_im.shape[0] == K and rec_thr.dtype == torch.float64 and hit.shape[0] % K == 0
+    e = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    out = dict(ap=e((T, K)), corloc=e((T, K)))
+    if curve_at is not None:
+        out.update(rec=e((n,)), prec=e((n,)))
+    C.call("drn_voc_accumulate", C.ptr(tp), C.ptr(fp), n, C.ptr(cls_off), C.ptr(hit), C.ptr(npos), C.ptr(npos_im),
+           hit.shape[0] // K, K, T, C.ptr(rec_thr), R, int(bool(use_07_metric)), -1 if curve_at is None else int(curve_at),
+           C.ptr(out["ap"]), C.ptr(out["corloc"]), C.ptr(out.get("rec")), C.ptr(out.get("prec")), C.stream())
+    return out

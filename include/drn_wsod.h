@@ -639,6 +639,49 @@ int drn_coco_accumulate(const float* s_score, const int* s_cat, const int* s_ran
                         const int* max_dets, int M, const double* rec_thr, int R, void* workspace, long workspace_bytes,
                         int stages, double* precision, double* scores, double* recall, void* stream);
 
+/* ---- PASCAL VOC evaluation: AP and CorLoc (PascalVOCDetectionEvaluator; detectron2/evaluation/pascal_voc_evaluation.py) -
+ * voc_eval (:237-350), voc_eval_corloc (:353-447) and voc_ap (:182-234) on the device, in fp64, operation for operation
+ * (uncontracted), on the numbers the reference's text files hold: score "%.3f" = rint((double)s * 1000) / 1000, xmin / ymin
+ * "%.1f" after an fp32 + 1, xmax / ymax "%.1f" = rint((double)x * 10) / 10 - exact for fp32 inputs.  Scores
+ * and boxes must be finite.  Tie order is a definition: within a class, equal quantised scores keep their input order
+ * (the reference's np.argsort is not stable, so its answer on ties is not a function of its inputs).  No threshold is built
+ * in: the IoU thresholds and the VOC07 recall thresholds are device arrays the caller computes in fp64.
+ *
+ * Caps: at most DRN_VOC_MAX_GT ground-truth boxes per (image, class) pair (the per-lane `det` flag registers), T <= 64
+ * (one lane per IoU threshold), R <= DRN_VOC_MAX_REC recall thresholds; beyond a cap the entry points answer
+ * DRN_ERR_UNSUPPORTED before anything is launched - nothing is truncated.  Workspace: 16-byte aligned,
+ * DRN_VOC_WS_BYTES(n, P) bytes.  stages: bit 0 = quantise + rank, bit 1 = overlaps + the per-pair walk; 3 runs both, and
+ * one call with bit 1 alone continues from the workspace that a call with bit 0 alone left (used to time them apart).
+ *
+ * drn_voc_match: n detections in processing order: det_box [n][4] fp32 XYXY as predicted (0-based), det_score [n], det_pair
+ * [n] = image index * K + class (P = images * K pairs).  Ground truth grouped by pair in annotation order: gt_box [G][4]
+ * fp64, gt_diff [G] (difficult), gt_off [P + 1]; max_gt = the largest gt_off[p + 1] - gt_off[p], known on the host.
+ * iou_thr [T].  Output in rank order - class ascending, quantised score descending, input order on ties: order [n] (input
+ * index), s_score [n] (quantised), cls_off [K + 1] (the classes' segments), ovmax [n] / jmax [n] (_max_overlap over the
+ * pair's GT, first index on equal maxima, -inf / -1 without GT), tp / fp [n]: bit t = the detection is a true / false
+ * positive at iou_thr[t] (strict >; a match with a difficult box is neither; a second match with a box is a false
+ * positive).  hit [P]: bit t = the pair has a box that is not difficult and its top-ranked detection has ovmax >
+ * iou_thr[t] (0 for every other pair). */
+#define DRN_VOC_MAX_GT 128
+#define DRN_VOC_MAX_REC 16
+#define DRN_VOC_WS_BYTES(n, P) (24L * ((n) + 4) + 8192L * (((n) + 4095) / 4096 + 1) + 4L * (P) + 1024L)
+int drn_voc_match(const float* det_box, const float* det_score, const int* det_pair, int n, const double* gt_box,
+                  const unsigned char* gt_diff, const int* gt_off, int P, int K, int max_gt, const double* iou_thr, int T,
+                  void* workspace, long workspace_bytes, int stages, int* order, double* s_score, int* cls_off,
+                  double* ovmax, int* jmax, unsigned long long* tp, unsigned long long* fp, unsigned long long* hit,
+                  void* stream);
+/* drn_voc_accumulate: the tp / fp words, cls_off and hit that drn_voc_match left; npos [K] (boxes that are not difficult)
+ * and npos_im [K] (images with such a box) from the annotations.  Per (class k, threshold t), in rank order: cumulative tp
+ * / fp, rec = tp / npos (0 when npos = 0), prec = tp / max(tp + fp, DBL_EPSILON); use_07_metric != 0: for r in rec_thr [R]
+ * (np.arange(0.0, 1.1, 0.1), R = 11) p = max prec over rec >= rec_thr[r] (0 if none), ap = ap + p / R in that order; else
+ * the area under the monotone envelope, one term per recall step, summed in a fixed order (rec_thr unused).  Writes ap
+ * [T][K] and corloc [T][K] = set hit bits / npos_im (0 for a class without detections or with npos_im = 0) and, when rec
+ * and prec are given, the curves [n] (rank order) of threshold index t_curve. */
+int drn_voc_accumulate(const unsigned long long* tp, const unsigned long long* fp, int n, const int* cls_off,
+                       const unsigned long long* hit, const int* npos, const int* npos_im, int I, int K, int T,
+                       const double* rec_thr, int R, int use_07_metric, int t_curve, double* ap, double* corloc,
+                       double* rec, double* prec, void* stream);
+
 /* ---- PCL refinement (PCLROIHeads) ------------------------------------------------------------------
  * The reference computes these on the HOST: the targets in numpy + scikit-learn after a device->host copy of the scores
  * (projects/WSL/wsl/modeling/roi_heads/third_party/pcl.py:26-200, called from fast_rcnn.py:1725-1745), the loss in C++ on
