@@ -484,6 +484,28 @@ __device__ __forceinline__ void ws_combine(const WsddnParams& p, int img, int nb
   ws_colreduce<LPR, false>(csum, col, ph, red);
 }
 
+// An image without proposals (img_off[i] == img_off[i + 1]), as predict_probs_img sees an empty split: a zero sum in every
+// class, clamped to 1e-6, and its BCE; no rows, so no gradient.  Run by block 0 of the image in stage 2 (the grid has it:
+// max_rows >= 1); the same expressions as the stage's own, on S = 0.
+template <int LPR>
+__device__ __forceinline__ void ws_empty_image(const WsddnParams& p, int img) {
+  using L = WsLanes<LPR>;
+  const int K = p.K, l = threadIdx.x % LPR, ph = threadIdx.x / LPR;
+  const float norm = (p.mean_loss ? 1.f / (float)(p.n_img * K) : 1.f) / (float)p.n_img;
+  float lsum = 0.f;
+#pragma unroll
+  for (int j = 0; j < L::CPL; ++j) {
+    const int c = l + j * LPR;
+    if (c >= K) continue;
+    const float s_ = clamp_nan(0.f, 1e-6f, 1.0f - 1e-6f);
+    const float y = p.gt_onehot[img * K + c];
+    lsum += -(y * fmax_nan(logf(s_), -100.f) + (1.f - y) * fmax_nan(logf(1.f - s_), -100.f));
+    if (ph == 0) p.img_scores[img * K + c] = s_;
+  }
+  lsum = L::gsum(lsum);
+  if (threadIdx.x == 0) p.loss_part[img] = lsum * norm;
+}
+
 // Every stage is a handful of DEPENDENT memory round trips, not arithmetic: a thread's WS_ROWS / RPP rows are fetched
 // together, ahead of the cross-block combine, and kept in registers (stage 0 used to read its det logits twice, stages 1 / 2
 // took one round trip per row pass).  Same operations on the same values in the same order as the row-by-row form.
@@ -495,6 +517,7 @@ __device__ __forceinline__ void wsddn_stage_body(const WsddnParams& p, const Log
   const int img = blockIdx.y, blk = blockIdx.x;
   const int r0 = p.img_off[img], r1 = p.img_off[img + 1];
   const int nb = (r1 - r0 + WS_ROWS - 1) / WS_ROWS;
+  if (STAGE == 2 && nb == 0 && blk == 0) ws_empty_image<LPR>(p, img);  // uniform per block, off the row loops
   if (blk >= nb) return;
   const int rb0 = r0 + blk * WS_ROWS, rb1 = min(rb0 + WS_ROWS, r1);
   const int K = p.K;
@@ -1444,7 +1467,9 @@ int drn_colsum_reduce(const float* colpart, int nparts, int N, float* colsum, in
   return DRN_OK;
 }
 
-// scratch: n_img * ceil(max_rows/128) * 3 * 128 floats (max_rows = largest proposal count of one image)
+// scratch: n_img * ceil(max_rows/32) * 384 floats (32-row blocks, three rows of 128 column partials each); max_rows >=
+// the proposal count of every image: rows beyond it are not processed.  An image without proposals gets
+// img_scores = 1e-6 and the BCE of that row, and no gradient.
 int drn_wsddn_fwd_bwd(const float* logits, long ld, int c_cls, int c_det, int K, const int* img_off, int n_img,
                       const float* gt_onehot, float* scores, float* row_softmax, float* img_scores, float* loss_part,
                       float* dlogits, long ld_d, float* scratch, int max_rows, int mean_loss, float loss_scale,

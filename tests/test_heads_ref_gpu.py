@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 import golden_util as G
 from __graft_entry__ import load_package
+from mil_ref_util import softmax_rel_bound as _softmax_rel_bound  # (C + 2 R + 16) u: shared with the MIL loss tests
 
 pytestmark = pytest.mark.gpu
 O = G.O
@@ -316,16 +317,6 @@ def test_sum_small(drn, cabi, n):
 
 
 # ------------------------------------------------------------------------------------------- mean_softmax
-def _softmax_rel_bound(x64, C):
-    """relative error bound of an fp32 softmax row computed as exp(x - max) / sum, per row: the subtraction's rounding
-    scaled by |x - max| (R, over the entries whose exp is a normal number; the others are below 2^-126 and enter only the
-    absolute 2^-120 of the callers), exp <= 2 ulp, the sum gamma_C, the division; first order: (C + 2 R + 16) u"""
-    mx = x64.max(-1, keepdim=True).values
-    d = (x64 - mx).abs()
-    R = torch.where(d <= 88, d, torch.zeros(())).max(-1).values
-    return (C + 2 * R + 16) * U
-
-
 def _msm_logits(rs, M, C, H, gap):
     """head windows of C columns, `gap` NaN columns between and around them, NaN in row M: rows of N(0, 3) logits, rows
     spread over +-1e4 (exp overflows unless the maximum is subtracted) and rows of equal logits"""

@@ -1225,11 +1225,25 @@ def test_oicr_refine_chain_equals_per_head_sequence(drn, K, M_per, nh):
 
 
 @pytest.mark.parametrize("K,M_per,nh,splits", [(20, [2000], 3, 8), (6, [90, 77], 2, 3), (80, [1500, 500], 4, 1),
-                                               (20, [37, 2000, 5], 3, 4)])
+                                               (20, [37, 2000, 5], 3, 4),
+                                               # more than eight partials: the any-number-of-splits loader
+                                               (20, [2049, 31], 3, 16), (80, [300], 2, 9), (33, [4097, 5], 2, 16),
+                                               # an image without proposals: defined outputs, the same in both forms
+                                               (20, [40, 0, 33], 2, 9), (65, [0, 40, 33], 3, 3)])
 def test_mil_oicr_losses_equals_separate_calls(drn, K, M_per, nh, splits):
     """drn_mil_oicr_losses (six launches) == drn_bias_act_fwd (fp32 logits) + drn_wsddn_fwd_bwd + drn_oicr_refine_chain
     (nine), bit for bit: logits, scores, image scores, losses, targets, probabilities, the gradient of the logits and
     the dropout counter; run twice"""
+    _mil_equals_separate(drn, K, M_per, nh, splits, True)
+
+
+@pytest.mark.parametrize("K,M_per,nh,splits", [(20, [300, 41], 2, 9), (80, [77], 1, 2)])
+def test_mil_oicr_losses_without_bias(drn, K, M_per, nh, splits):
+    """the same with bias = NULL (the logits are the plain sum of the partials)"""
+    _mil_equals_separate(drn, K, M_per, nh, splits, False)
+
+
+def _mil_equals_separate(drn, K, M_per, nh, splits, with_bias):
     M, n_img = sum(M_per), len(M_per)
     rs = np.random.RandomState(91)
     C_ = K + 1
@@ -1238,6 +1252,8 @@ def test_mil_oicr_losses_equals_separate_calls(drn, K, M_per, nh, splits):
     col0s = [2 * K + k * C_ for k in range(nh)]
     part = torch.from_numpy(rs.standard_normal((splits, M, ldp)).astype(np.float32)).to(DEV)
     bias = torch.from_numpy(rs.standard_normal(NH).astype(np.float32)).to(DEV)
+    if not with_bias:
+        bias = None
     props = _boxes(M, 35).to(DEV)
     gmax = 4
     gcl = torch.zeros((n_img, gmax), dtype=torch.int32)
