@@ -21,6 +21,7 @@ _SIGS = {
     "drn_augment_u8": "piii" + "iiii" + "pii" + "ppi" + "ppi" + "i" + "if" + "idf" + "p",
     "drn_conv2d_nhwc": "pppppp" + "iiiiiiiiii" + "lll" + "iip",
     "drn_conv2d_nhwc_q": "pppppp" + "iiiiiiiiii" + "lll" + "iiiifp",
+    "drn_conv2d_plan": "pppppp" + "iiiiiiiiii" + "lll" + "iiiifi",
     "drn_conv3x3_pw_nhwc": "pppp" + "i" + "pppp" + "p" + "iii" + "ll" + "f" + "ii" + "p",
     "drn_maxpool2x2_nhwc": "ppiiiiiip",
     "drn_maxpool3x3s2_nhwc": "ppiiiiip",

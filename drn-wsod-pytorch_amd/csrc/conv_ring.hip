@@ -26,6 +26,7 @@
 #include "drn_common.h"
 #include "tune.h"
 #include "conv_params.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -242,27 +243,9 @@ int launch_ring(const ConvParams& p, hipStream_t st) {
 
 }  // namespace
 
-// (hidden: called by drn_conv2d_nhwc_q in gemm_conv.hip)
-// Runs the convolution on the register-ring kernels when it is in their class; DRN_ERR_UNSUPPORTED otherwise (the caller
-// then takes the kernels of gemm_conv.hip).  `cus` = compute units of the device; `tiles64_one` = 64x64 tiles of ONE image of
-// this layer: the class is decided on one image's geometry, so a layer takes the same kernel family - the same fp32 summation
-// order - whether its image runs alone or in a batch (graphed trunk groups vs eager steps, 2 ranks vs 1).
-__attribute__((visibility("hidden"))) int drn_conv_ring_try(const ConvParams& p, int dtype, int cus, long tiles64_one, hipStream_t st) {
-  if (!g_tune.conv_ring || dtype != DRN_BF16 || p.out_dt != DRN_BF16 || (p.residual && p.res_dt != DRN_BF16)) return DRN_ERR_UNSUPPORTED;
-  if ((p.Cin & 63) || (p.Cout & 7) || p.KH * p.KW > 32 || (p.ldy & 7) || (p.residual && (p.ldres & 7))) return DRN_ERR_UNSUPPORTED;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (!al16(p.X) || !al16(p.Wt) || !al16(p.Y) || (p.residual && !al16(p.residual)) || (p.ldw * 2) % 16 != 0) return DRN_ERR_UNSUPPORTED;
-  if ((long)p.Cout * p.ldw * 2 >= 0xFFFFFFF0L) return DRN_ERR_UNSUPPORTED;
-  const int nslab = p.KH * p.KW * (p.Cin >> 6);
-  // Where the ring kernel wins (tools/conv_bench.py at 800x1216, profiles/r5_04_*, r5_12_*): layers of >= 4 K slabs on more
-  // than CUs / 4 and up to ~4 rounds of 64x64 tiles per image - the res3 / res4 1x1 and 3x3 layers of a real-size image.
-  // Single-slab 1x1s and the huge res2 maps are bound by their output traffic (the 128-wide tiles of gemm_conv.hip move fewer
-  // operand bytes there); maps of fewer than 1024 pixels (the 224x224 benchmark image) stay in the small-map kernels' class.
-  int pick = g_tune.conv_ring;
-  if (pick == 1) {
-    if (nslab < 4 || tiles64_one <= cus / 4 || tiles64_one > 4L * cus || (long)p.Ho * p.Wo < 1024) return DRN_ERR_UNSUPPORTED;
-    pick = 64;
-  }
-  if (pick == 128) return launch_ring<128, 128, 3>(p, st);
+// (hidden: called by conv_fwd_launch in gemm_conv.hip.  conv_fwd_plan there has decided that the layer is in the kernels' class -
+// bf16, Cin % 64 == 0, 16-byte rows and pointers - and which tile runs it: 64 = 64x64, 128 = 128x128)
+__attribute__((visibility("hidden"))) int drn_conv_ring_launch(const ConvParams& p, int tile, hipStream_t st) {
+  if (tile == 128) return launch_ring<128, 128, 3>(p, st);
   return launch_ring<64, 64, 4>(p, st);
 }

@@ -18,6 +18,8 @@
 #include "drn_common.h"
 #include "tune.h"
 #include "conv_params.h"
+#include "conv_launch.h"
+#include "../../include/drn_wsod.h"
 
 #include <limits.h>
 
@@ -2191,10 +2193,168 @@ static long tail_split_main_cols(int M, int N, int splits, int nwg) {
   return N;
 }
 
-// conv_ring.hip: the register-ring kernels (bf16, Cin % 64 == 0); DRN_ERR_UNSUPPORTED outside their class
-__attribute__((visibility("hidden"))) int drn_conv_ring_try(const ConvParams& p, int dtype, int cus, long tiles64_one, hipStream_t st);
-// pp8.hip: the eight-wave 128x128 kernel (bf16, Cin % 64 == 0); DRN_ERR_UNSUPPORTED outside its class
-__attribute__((visibility("hidden"))) int drn_pp8_conv_try(const ConvParams& p, int dtype, int cus, hipStream_t st);
+namespace {
+// ---- the forward's host side: which kernel a layer runs on (conv_fwd_plan) and its launch (conv_fwd_launch) ----------------
+
+// (dtype, fp8_k64) -> the <DT, K64> template arguments of the tiled / k2 / ks kernels: f(integral_constant<int, DT>,
+// bool_constant<K64>).  K64 only distinguishes the fp8 kernels.
+template <class F>
+int with_conv_dtype(int dtype, bool k64, F&& f) {
+  if (dtype == DRN_BF16) return f(std::integral_constant<int, DRN_BF16>{}, std::true_type{});
+  if (dtype == DRN_FP8)
+    return k64 ? f(std::integral_constant<int, DRN_FP8>{}, std::true_type{})
+               : f(std::integral_constant<int, DRN_FP8>{}, std::false_type{});
+  return f(std::integral_constant<int, DRN_F32>{}, std::true_type{});
+}
+
+bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+
+// What conv3x3_c64_kernel asks of every caller (drn_conv2d_nhwc_q's plan and drn_conv3x3_pw_nhwc): the knob, a map of at least
+// conv_patch_min pixels (117 KB of LDS, so only where the trunk is not meant to share CUs with the heads' GEMMs: maps of
+// >= 32k pixels), 16-byte weight rows, aligned weights / output / shortcut.
+bool patch_c64_ok(const DrnTune& t, long pixels, const void* w, long ldw, const void* y, const void* residual) {
+  return t.conv_patch && pixels >= t.conv_patch_min && (ldw * 2) % 16 == 0 && al16(w) && al16(y) && (!residual || al16(residual));
+}
+
+struct ConvPlan {
+  int kind;   // DRN_CONV_KIND_* (include/drn_wsod.h)
+  int dtype;  // element type of x / w
+  bool k64;   // fp8 operands: the K = 64 scaled MFMA (false: the K = 16 form, DRN_CONV_KIND_FP8_K16 in drn_conv2d_plan)
+};
+
+// Which kernel runs the layer `p` (operands of `dtype`) under the knobs `t` on a device of `cus` compute units.  Pure: no device
+// call, no read of g_tune.  The ONE place that holds a class condition of the forward; the order of the rules is part of it.
+// Every family gives the same bits except the two small-map kernels (k2, ks), which add their K partials in another order.
+ConvPlan conv_fwd_plan(const ConvParams& p, int dtype, const DrnTune& t, int cus) {
+  ConvPlan pl{DRN_CONV_KIND_TILED_128, dtype, dtype != DRN_FP8 || t.fp8_k64 != 0};
+  auto is = [&](int kind) { pl.kind = kind; return pl; };
+  const int es = drn_esize(dtype);
+  const bool res = p.residual != nullptr;
+  const bool bf16_io = dtype == DRN_BF16 && p.out_dt == DRN_BF16 && (!res || p.res_dt == DRN_BF16);
+  const long HoWo = (long)p.Ho * p.Wo, Mtot = (long)p.Nb * HoWo;
+  const int nslab = (p.Ktot * es + 127) / 128;
+  // (decided on ONE image's geometry: the k2 / ks kernels add the K partials in another order than the tiled ones, and a layer
+  // must round the same way whether its image runs alone or in a batch - graphed trunk pairs vs eager, 2 ranks vs 1)
+  const long tiles64 = ((HoWo + 63) / 64) * ((p.Cout + 63) / 64);
+
+  // LDS-resident patch + weights for the 64-channel 3x3 layers of large maps (conv3x3_c64_kernel)
+  if (bf16_io && p.Cin == 64 && p.Cout == 64 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.dil == 1 && p.pad == 1 &&
+      patch_c64_ok(t, HoWo, p.Wt, p.ldw, p.Y, p.residual) && (p.ldy & 7) == 0 && (!res || (p.ldres & 7) == 0))
+    return is(DRN_CONV_KIND_PATCH_C64);
+
+  // What the register-ring kernels (conv_ring.hip) and the eight-wave kernel (pp8.hip) both ask: bf16, whole 64-channel K slabs
+  // (so nslab == KH * KW * (Cin >> 6)), 16-byte rows and pointers, 32-bit byte offsets into the weights
+  const bool slab64 = bf16_io && (p.Cin & 63) == 0 && (p.Cout & 7) == 0 && p.KH * p.KW <= 32 && (p.ldy & 7) == 0 &&
+                      (!res || (p.ldres & 7) == 0) && al16(p.X) && al16(p.Wt) && al16(p.Y) && (!res || al16(p.residual)) &&
+                      (p.ldw * 2) % 16 == 0 && (long)p.Cout * p.ldw * 2 < 0xFFFFFFF0L;
+  // (pp8 reads scale / bias as vectors; the input's 32-bit range is an argument check of the entry points)
+  const bool pp8_ok = t.pp8 && slab64 && (!p.scale || al16(p.scale)) && (!p.bias || al16(p.bias));
+  // the 256x128 form where one image's layer gives it at least ~5/8 of the CUs' worth of tiles (drn_pp8_wide_ok)
+  auto pp8 = [&] { return is(drn_pp8_wide_ok(HoWo, p.Cout, t, cus) ? DRN_CONV_KIND_PP8_WIDE : DRN_CONV_KIND_PP8); };
+  if (t.pp8 == 2 && pp8_ok) return pp8();  // (A/B pin: every layer in the eight-wave kernel's class takes it)
+
+  // 1x1 / stride 1 convs to >= 256 channels of a large map: the GEMM ping-pong mainloop with the conv epilogue
+  // (conv1x1_pp_kernel; the dilated-C5 trunk's 1x1s to 512 / 1024 / 2048 channels and the res2 1x1s to 256 channels at a real
+  // image size).  Class measured (profiles/r5_17_conv1x1_pp_threshold_*.txt, r5_19_conv_800.txt): from ~3/4 of the CUs' worth
+  // of 256x256 tiles per image on it wins at any K; at 100-191 tiles - half the chip holds a tile - only with a long K loop
+  // (>= 16 slabs: 2048 -> 512 at 118 tiles 47 -> 44 us, but 128 -> 512 at 120 tiles 12 -> 15 us); at 59-60 tiles (res4 of the
+  // C4 trunk, the DC5 trunk's 1x1s to 256 channels) the small tiles win; a 64-channel output wastes three quarters of the
+  // tile.  Decided on ONE image's geometry; same bits as the tiled kernels either way.
+  const bool pp_ok = t.conv_pp && bf16_io && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && (p.Cin & 63) == 0 &&
+                     (p.Cout & 7) == 0 && (p.ldy & 3) == 0 && (!res || (p.ldres & 3) == 0) &&
+                     (((uintptr_t)p.X | (uintptr_t)p.Wt | (uintptr_t)p.Y | (uintptr_t)p.residual) & 15) == 0 &&
+                     (p.ldw * 2) % 16 == 0 && (long)p.Cout * p.ldw * 2 < 0xFFFFFFF0L;
+  const long t256 = ((HoWo + 255) / 256) * ((p.Cout + 255) / 256);
+  // (1) >= 3/4 of the CUs' worth of 256x256 tiles: the ping-pong GEMM mainloop, whatever K
+  if (pp_ok && (t.conv_pp > 1 ? t256 >= t.conv_pp : (p.Cout >= 256 && t256 >= 192))) return is(DRN_CONV_KIND_PP256);
+  // (2) the eight-wave 128x128 / 256x128 kernel (pp8.hip; round 6): layers with too few 256x256 tiles for (1) - the 3x3s of
+  // res4 / res5, the 1x1s to 256 / 512 channels of the dilated-C5 trunk, the C4 trunk's 1x1s to 1024 channels.  Measured class
+  // (tools/conv_bench.py / tools/pp8_probe.py at 800x1216, profiles/r6_*): one image's layer offers at least 5/8 of the CUs a
+  // 128x128 tile and the K loop is long enough to amortise the ring's prologue.
+  const long t128 = ((HoWo + 127) / 128) * ((p.Cout + 127) / 128);
+  if (pp8_ok && (t.pp8 != 1 || (nslab >= 4 && t128 * 8 >= 5L * cus && p.Cout >= 128))) return pp8();
+  // (3) 100-191 tiles of 256x256 with a long K loop (round 5's class; reached when (2) is switched off)
+  if (pp_ok && t.conv_pp == 1 && p.Cout >= 256 && t256 >= 100 && (p.Cin >> 6) >= 16) return is(DRN_CONV_KIND_PP256);
+
+  // everything beyond the latency-bound small maps: the register-ring kernels.  Where they win (tools/conv_bench.py at
+  // 800x1216, profiles/r5_04_*, r5_12_*): layers of >= 4 K slabs on more than CUs / 4 and up to ~4 rounds of 64x64 tiles per
+  // image - the res3 / res4 1x1 and 3x3 layers of a real-size image.  Single-slab 1x1s and the huge res2 maps are bound by
+  // their output traffic (the 128-wide tiled kernels move fewer operand bytes there); maps of fewer than 1024 pixels (the
+  // 224x224 benchmark image) stay in the small-map kernels' class.  Decided on ONE image's geometry, as above.
+  if (t.conv_ring && slab64) {
+    if (t.conv_ring == 128) return is(DRN_CONV_KIND_RING_128);
+    if (t.conv_ring != 1 || (nslab >= 4 && tiles64 > cus / 4 && tiles64 <= 4L * cus && HoWo >= 1024))
+      return is(DRN_CONV_KIND_RING_64);
+  }
+
+  // two K-groups per 64x64 tile (conv_nhwc_k2_kernel): mid-size layers - more 64x64 tiles than the wave-K-split kernel
+  // takes, at most one per CU (the kernel keeps one 512-thread workgroup per CU) - with an even slab count >= 8
+  const long k2_max = t.conv_k2_tiles >= 0 ? t.conv_k2_tiles : cus;
+  if ((nslab & 1) == 0 && nslab >= 8 && tiles64 > cus / 4 && tiles64 <= k2_max && p.Nb <= 64) return is(DRN_CONV_KIND_K2);
+  // few 64x64 tiles and a long K loop: latency-bound, see conv_nhwc_ks_kernel
+  // (round 2, tools/conv_bench.py at 800x1216: up to one 64x64 tile per CU the 36-slab res4 3x3 still gains, 23.1 ->
+  // 20.5 us, while layers with few slabs lose - the 9-slab stem 3x3 8.6 -> 9.7 us at 224x224: deep K only)
+  const long ks_max = t.conv_ks_tiles > 0 ? t.conv_ks_tiles : (nslab >= 32 ? cus : cus / 4);
+  if (t.conv_ksplit && tiles64 <= ks_max && nslab >= 8 && p.Nb <= 64) return is(DRN_CONV_KIND_KS);
+
+  // the tiled kernels, on the BATCH's geometry (they give the same bits at every tile)
+  if (((Mtot + 127) / 128) * ((p.Cout + 127) / 128) < 128) return is(DRN_CONV_KIND_TILED_64);
+  // narrow outputs (the 64-channel stem / res2 layers at real image sizes): a 128x128 tile would run half empty
+  return is(p.Cout <= 64 ? DRN_CONV_KIND_TILED_128X64 : DRN_CONV_KIND_TILED_128);
+}
+
+// Issues what the plan says.  A refused launch is DRN_ERR_LAUNCH: no other kernel is tried.
+int conv_fwd_launch(const ConvPlan& pl, const ConvParams& p, hipStream_t st) {
+  auto tiled = [&](auto bm, auto bn) {
+    return with_conv_dtype(pl.dtype, pl.k64, [&](auto dt, auto k64) {
+      return launch_conv<decltype(dt)::value, decltype(bm)::value, decltype(bn)::value, decltype(k64)::value>(p, st);
+    });
+  };
+  using i64 = std::integral_constant<int, 64>;
+  using i128 = std::integral_constant<int, 128>;
+  switch (pl.kind) {
+    case DRN_CONV_KIND_PATCH_C64: return launch_conv3x3_c64(p, st);
+    case DRN_CONV_KIND_PP256: return launch_conv1x1_pp(p, st);
+    case DRN_CONV_KIND_PP8: return drn_pp8_conv_launch(p, false, st);
+    case DRN_CONV_KIND_PP8_WIDE: return drn_pp8_conv_launch(p, true, st);
+    case DRN_CONV_KIND_RING_64: return drn_conv_ring_launch(p, 64, st);
+    case DRN_CONV_KIND_RING_128: return drn_conv_ring_launch(p, 128, st);
+    case DRN_CONV_KIND_K2:
+      return with_conv_dtype(pl.dtype, pl.k64, [&](auto dt, auto k64) {
+        return launch_conv_k2<decltype(dt)::value, decltype(k64)::value>(p, st);
+      });
+    case DRN_CONV_KIND_KS:
+      return with_conv_dtype(pl.dtype, pl.k64, [&](auto dt, auto k64) {
+        return launch_conv_ks<decltype(dt)::value, decltype(k64)::value>(p, st);
+      });
+    case DRN_CONV_KIND_TILED_64: return tiled(i64{}, i64{});
+    case DRN_CONV_KIND_TILED_128X64: return tiled(i128{}, i64{});
+    default: return tiled(i128{}, i128{});
+  }
+}
+
+// The argument checks of drn_conv2d_nhwc_q and drn_conv2d_plan, and the parameter block.  Pointers are inspected, never
+// dereferenced.
+int conv_params(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* residual, int Nb, int H,
+                int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil, long ldw, long ldy, long ldres, int relu,
+                int dtype, int out_dtype, int res_dtype, float res_mult, const DrnTune& t, ConvParams& p) {
+  if (!x || !w || !y) return DRN_ERR_ARG;
+  auto known = [](int d) { return d == DRN_F32 || d == DRN_BF16 || d == DRN_FP8; };
+  if (!known(dtype) || !known(out_dtype) || (residual && !known(res_dtype))) return DRN_ERR_ARG;
+  const int es = drn_esize(dtype);
+  if ((Cin * es) % 16 != 0 || (ldw * es) % 16 != 0) return DRN_ERR_ARG;  // 16-B chunks never straddle taps
+  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+  const int Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  if (Ho <= 0 || Wo <= 0 || Nb <= 0) return DRN_ERR_ARG;
+  if ((long)Nb * H * W * Cin * es >= 0xFFFFFFF0L) return DRN_ERR_ARG;  // one buffer descriptor spans the input
+  const int Ktot = KH * KW * Cin;
+  if (ldw * es < ((Ktot * es + 127) / 128) * 128) return DRN_ERR_ARG;  // weight rows zero-padded to 128-B slabs
+  p = ConvParams{(const char*)x, (const char*)w, (char*)y, scale, bias, (const char*)residual, Nb, H, W, Cin, Ho, Wo,
+                 Cout, KH, KW, stride, pad, dil, relu, Ktot, ldw, ldy, ldres, out_dtype, res_dtype, res_mult, t.fp8_k64};
+  return DRN_OK;
+}
+
+}  // namespace
 
 DrnTune g_tune;  // (tune.h)
 
@@ -2501,8 +2661,6 @@ int drn_gemm_tn_acc_sgd_guard(const void* A, const void* Bt, const float* grad_a
                            ld_w, seg_dev, momentum, first_step, grad_scale, guard, stream);
 }
 
-// NHWC conv + per-channel affine (folded FrozenBN or bias) + optional residual + optional ReLU; `dtype` is the element
-// type of x / w (fp32, bf16 or fp8 e4m3fn), y and the residual may be stored in another one (see include/drn_wsod.h).
 // The tail of a 64-channel bottleneck on a large map as ONE launch (conv3x3_c64_kernel<.., PW, POOL>): the 3x3's output never
 // goes to memory; w3 == NULL: no 1x1 stage (y has 64 channels, the residual - if any - too); pool: MaxPool2d(2, 2) in the
 // epilogue (needs the last ReLU).  Same shape class as the LDS-resident-patch kernel takes on its own; anything else:
@@ -2511,10 +2669,8 @@ int drn_conv3x3_pw_nhwc(const void* x, const void* w2, const float* scale2, cons
                         const float* scale3, const float* bias3, const void* residual, void* y, int Nb, int H, int W,
                         long ldw2, long ldw3, float res_mult, int relu3, int pool, void* stream) {
   if (!x || !w2 || !y || Nb <= 0 || H <= 0 || W <= 0) return DRN_ERR_ARG;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (!g_tune.conv_patch || (long)H * W < g_tune.conv_patch_min || (long)Nb * H * W * 128 >= 0xFFFFFFF0L ||
-      ldw2 < 9 * 64 || (w3 && ldw3 < 64) || (ldw2 * 2) % 16 != 0 || (w3 && (ldw3 * 2) % 16 != 0) || !al16(x) || !al16(w2) ||
-      (w3 && !al16(w3)) || !al16(y) || (residual && !al16(residual)) || (!w3 && !pool) ||
+  if (!patch_c64_ok(g_tune, (long)H * W, w2, ldw2, y, residual) || (long)Nb * H * W * 128 >= 0xFFFFFFF0L || ldw2 < 9 * 64 ||
+      (w3 && ldw3 < 64) || (w3 && (ldw3 * 2) % 16 != 0) || !al16(x) || (w3 && !al16(w3)) || (!w3 && !pool) ||
       (pool && (!(w3 ? relu3 : relu2) || H < 2 || W < 2)))
     return DRN_ERR_UNSUPPORTED;
   const int cy = w3 ? 256 : 64;
@@ -2524,98 +2680,30 @@ int drn_conv3x3_pw_nhwc(const void* x, const void* w2, const float* scale2, cons
   return launch_conv3x3_c64_pw(p, (hipStream_t)stream);
 }
 
+// NHWC conv + per-channel affine (folded FrozenBN or bias) + optional residual + optional ReLU; `dtype` is the element
+// type of x / w (fp32, bf16 or fp8 e4m3fn), y and the residual may be stored in another one (see include/drn_wsod.h).
 int drn_conv2d_nhwc_q(const void* x, const void* w, void* y, const float* scale, const float* bias,
                       const void* residual, int Nb, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                       int pad, int dil, long ldw, long ldy, long ldres, int relu, int dtype, int out_dtype,
                       int res_dtype, float res_mult, void* stream) {
-  if (!x || !w || !y) return DRN_ERR_ARG;
-  auto known = [](int d) { return d == DRN_F32 || d == DRN_BF16 || d == DRN_FP8; };
-  if (!known(dtype) || !known(out_dtype) || (residual && !known(res_dtype))) return DRN_ERR_ARG;
-  const int es = drn_esize(dtype);
-  if ((Cin * es) % 16 != 0 || (ldw * es) % 16 != 0) return DRN_ERR_ARG;  // 16-B chunks never straddle taps
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  if (Ho <= 0 || Wo <= 0 || Nb <= 0) return DRN_ERR_ARG;
-  if ((long)Nb * H * W * Cin * es >= 0xFFFFFFF0L) return DRN_ERR_ARG;  // one buffer descriptor spans the input
-  const int Ktot = KH * KW * Cin;
-  if (ldw * es < ((Ktot * es + 127) / 128) * 128) return DRN_ERR_ARG;  // weight rows zero-padded to 128-B slabs
-  ConvParams p{(const char*)x, (const char*)w, (char*)y, scale, bias, (const char*)residual, Nb, H, W, Cin, Ho, Wo,
-               Cout, KH, KW, stride, pad, dil, relu, Ktot, ldw, ldy, ldres, out_dtype, res_dtype, res_mult, g_tune.fp8_k64};
-  hipStream_t st = (hipStream_t)stream;
-  const long Mtot = (long)Nb * Ho * Wo;
-  const bool small = ((Mtot + 127) / 128) * ((Cout + 127) / 128) < 128;
-  // narrow outputs (the 64-channel stem / res2 layers at real image sizes): a 128x128 tile would run half empty
-  const bool narrow = !small && Cout <= 64;
-  // few 64x64 tiles and a long K loop: latency-bound, see conv_nhwc_ks_kernel
-  const int nslab = (Ktot * es + 127) / 128;
-  // (decided on ONE image's geometry: this kernel adds the K partials in another order than the tiled ones, and a layer
-  // must round the same way whether its image runs alone or in a batch - graphed trunk pairs vs eager, 2 ranks vs 1)
-  const long tiles64 = (((long)Ho * Wo + 63) / 64) * ((Cout + 63) / 64);
-  // (round 2, tools/conv_bench.py at 800x1216: up to one 64x64 tile per CU the 36-slab res4 3x3 still gains, 23.1 ->
-  // 20.5 us, while layers with few slabs lose - the 9-slab stem 3x3 8.6 -> 9.7 us at 224x224: deep K only)
-  const long ks_max = g_tune.conv_ks_tiles > 0 ? g_tune.conv_ks_tiles : (nslab >= 32 ? cu_count() : cu_count() / 4);
-  // LDS-resident patch + weights for the 64-channel 3x3 layers of large maps (conv3x3_c64_kernel; 117 KB of LDS, so only
-  // where the trunk is not meant to share CUs with the heads' GEMMs: maps of >= 32k pixels)
-  if (g_tune.conv_patch && dtype == DRN_BF16 && out_dtype == DRN_BF16 && (!residual || res_dtype == DRN_BF16) && Cin == 64 &&
-      Cout == 64 && KH == 3 && KW == 3 && stride == 1 && dil == 1 && pad == 1 && (long)Ho * Wo >= g_tune.conv_patch_min &&
-      (ldy & 7) == 0 && (((uintptr_t)y) & 15) == 0 && (!residual || ((ldres & 7) == 0 && (((uintptr_t)residual) & 15) == 0)) &&
-      (ldw * 2) % 16 == 0 && (((uintptr_t)w) & 15) == 0)
-    return launch_conv3x3_c64(p, st);
-  // everything beyond the latency-bound small maps: the register-ring kernels (conv_ring.hip; bf16, Cin % 64 == 0).  Decided on
-  // ONE image's geometry: the small-map kernels below add their K partials in another order
-  // 1x1 / stride 1 convs to >= 256 channels of a large map: the GEMM ping-pong mainloop with the conv epilogue
-  // (conv1x1_pp_kernel; the dilated-C5 trunk's 1x1s to 512 / 1024 / 2048 channels and the res2 1x1s to 256 channels at a real
-  // image size).  Class measured (profiles/r5_17_conv1x1_pp_threshold_*.txt, r5_19_conv_800.txt): from ~3/4 of the CUs' worth
-  // of 256x256 tiles per image on it wins at any K; at 100-191 tiles - half the chip holds a tile - only with a long K loop
-  // (>= 16 slabs: 2048 -> 512 at 118 tiles 47 -> 44 us, but 128 -> 512 at 120 tiles 12 -> 15 us); at 59-60 tiles (res4 of the
-  // C4 trunk, the DC5 trunk's 1x1s to 256 channels) the small tiles win; a 64-channel output wastes three quarters of the
-  // tile.  Decided on ONE image's geometry; same bits as the tiled kernels either way.
-  if (g_tune.pp8 == 2) {  // (A/B pin: every layer in the eight-wave kernel's class takes it)
-    const int rc = drn_pp8_conv_try(p, dtype, cu_count(), st);
-    if (rc != DRN_ERR_UNSUPPORTED) return rc;
-  }
-  const bool pp_ok = g_tune.conv_pp && dtype == DRN_BF16 && out_dtype == DRN_BF16 && (!residual || res_dtype == DRN_BF16) && KH == 1 &&
-                     KW == 1 && stride == 1 && pad == 0 && (Cin & 63) == 0 && (Cout & 7) == 0 && (ldy & 3) == 0 &&
-                     (!residual || (ldres & 3) == 0) &&
-                     (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)residual) & 15) == 0 && (ldw * 2) % 16 == 0 &&
-                     (long)Cout * ldw * 2 < 0xFFFFFFF0L;
-  const long t256 = (((long)Ho * Wo + 255) / 256) * ((Cout + 255) / 256);
-  // (1) >= 3/4 of the CUs' worth of 256x256 tiles: the ping-pong GEMM mainloop, whatever K
-  if (pp_ok && (g_tune.conv_pp > 1 ? t256 >= g_tune.conv_pp : (Cout >= 256 && t256 >= 192))) return launch_conv1x1_pp(p, st);
-  // (2) the eight-wave 128x128 / 256x128 kernel (pp8.hip; round 6): layers with too few 256x256 tiles for (1) - the 3x3s of
-  // res4 / res5, the 1x1s to 256 / 512 channels of the dilated-C5 trunk, the C4 trunk's 1x1s to 1024 channels
-  {
-    const int rc = drn_pp8_conv_try(p, dtype, cu_count(), st);
-    if (rc != DRN_ERR_UNSUPPORTED) return rc;
-  }
-  // (3) 100-191 tiles of 256x256 with a long K loop (round 5's class; reached when (2) is switched off)
-  if (pp_ok && g_tune.conv_pp == 1 && Cout >= 256 && t256 >= 100 && (Cin >> 6) >= 16) return launch_conv1x1_pp(p, st);
-  {
-    const int rc = drn_conv_ring_try(p, dtype, cu_count(), tiles64, st);
-    if (rc != DRN_ERR_UNSUPPORTED) return rc;
-  }
-  // two K-groups per 64x64 tile (conv_nhwc_k2_kernel): mid-size layers - more 64x64 tiles than the wave-K-split kernel
-  // takes, at most one per CU (the kernel keeps one 512-thread workgroup per CU) - with an even slab count >= 8
-  const long k2_max = g_tune.conv_k2_tiles >= 0 ? g_tune.conv_k2_tiles : cu_count();
-  if ((nslab & 1) == 0 && nslab >= 8 && tiles64 > cu_count() / 4 && tiles64 <= k2_max && Nb <= 64)
-    return dtype == DRN_BF16 ? launch_conv_k2<DRN_BF16>(p, st)
-           : dtype == DRN_FP8 ? (p.fp8_k64 ? launch_conv_k2<DRN_FP8>(p, st) : launch_conv_k2<DRN_FP8, false>(p, st))
-                              : launch_conv_k2<DRN_F32>(p, st);
-  if (g_tune.conv_ksplit && tiles64 <= ks_max && nslab >= 8 && Nb <= 64)
-    return dtype == DRN_BF16 ? launch_conv_ks<DRN_BF16>(p, st)
-           : dtype == DRN_FP8 ? (p.fp8_k64 ? launch_conv_ks<DRN_FP8>(p, st) : launch_conv_ks<DRN_FP8, false>(p, st))
-                              : launch_conv_ks<DRN_F32>(p, st);
-  if (dtype == DRN_BF16)
-    return small ? launch_conv<DRN_BF16, 64, 64>(p, st)
-                 : narrow ? launch_conv<DRN_BF16, 128, 64>(p, st) : launch_conv<DRN_BF16, 128, 128>(p, st);
-  if (dtype == DRN_FP8 && p.fp8_k64)
-    return small ? launch_conv<DRN_FP8, 64, 64>(p, st)
-                 : narrow ? launch_conv<DRN_FP8, 128, 64>(p, st) : launch_conv<DRN_FP8, 128, 128>(p, st);
-  if (dtype == DRN_FP8)
-    return small ? launch_conv<DRN_FP8, 64, 64, false>(p, st)
-                 : narrow ? launch_conv<DRN_FP8, 128, 64, false>(p, st) : launch_conv<DRN_FP8, 128, 128, false>(p, st);
-  return small ? launch_conv<DRN_F32, 64, 64>(p, st)
-               : narrow ? launch_conv<DRN_F32, 128, 64>(p, st) : launch_conv<DRN_F32, 128, 128>(p, st);
+  ConvParams p;
+  const int rc = conv_params(x, w, y, scale, bias, residual, Nb, H, W, Cin, Cout, KH, KW, stride, pad, dil, ldw, ldy, ldres, relu,
+                             dtype, out_dtype, res_dtype, res_mult, g_tune, p);
+  if (rc != DRN_OK) return rc;
+  return conv_fwd_launch(conv_fwd_plan(p, dtype, g_tune, cu_count()), p, (hipStream_t)stream);
+}
+
+// Host-only: the kernel drn_conv2d_nhwc_q would run these arguments on, under the knobs as they stand, on a device of `cus`
+// compute units (<= 0: this device's).  No launch, no device memory touched.  See include/drn_wsod.h.
+int drn_conv2d_plan(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* residual, int Nb,
+                    int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil, long ldw, long ldy, long ldres,
+                    int relu, int dtype, int out_dtype, int res_dtype, float res_mult, int cus) {
+  ConvParams p;
+  const int rc = conv_params(x, w, y, scale, bias, residual, Nb, H, W, Cin, Cout, KH, KW, stride, pad, dil, ldw, ldy, ldres, relu,
+                             dtype, out_dtype, res_dtype, res_mult, g_tune, p);
+  if (rc != DRN_OK) return rc;
+  const ConvPlan pl = conv_fwd_plan(p, dtype, g_tune, cus > 0 ? cus : cu_count());
+  return pl.kind | (pl.k64 ? 0 : DRN_CONV_KIND_FP8_K16);
 }
 
 int drn_conv2d_nhwc(const void* x, const void* w, void* y, const float* scale, const float* bias,

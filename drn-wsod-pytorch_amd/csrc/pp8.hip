@@ -31,6 +31,7 @@
 #include "drn_common.h"
 #include "tune.h"
 #include "conv_params.h"
+#include "conv_launch.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -543,14 +544,6 @@ int launch_pp8_any(const Pp8Params& p, bool wide, hipStream_t st) {
   return launch_pp8<128, 5, EPI, 1>(p, st);
 }
 
-// the 256x128 form where one image's layer gives it at least ~5/8 of the CUs' worth of tiles (its tiles are twice the work)
-static bool pp8_wide_ok(long rows_one, int N, int cus) {
-  if (g_tune.pp8_wide == 0) return false;
-  if (g_tune.pp8_wide == 2) return true;
-  const long t256 = ((rows_one + 255) / 256) * ((N + 127) / 128);
-  return t256 * 8 >= 5L * cus;
-}
-
 }  // namespace
 
 // DRN_TUNE_PP8_PROFILE: print and clear the shader-clock split the profile variants (VAR & 8) accumulated
@@ -568,25 +561,17 @@ __attribute__((visibility("hidden"))) int drn_tune_pp8_profile_dump() {
   return 0;
 }
 
-// Runs the convolution on the eight-wave kernel when it is in its class; DRN_ERR_UNSUPPORTED otherwise (drn_conv2d_nhwc_q then
-// goes on to the other kernel families).  The class is decided on ONE image's geometry (`HoWo`), so a layer takes the same
-// kernel whether its image runs alone or in a batch; every family gives the same bits anyway.
-__attribute__((visibility("hidden"))) int drn_pp8_conv_try(const ConvParams& c, int dtype, int cus, hipStream_t st) {
-  if (!g_tune.pp8 || dtype != DRN_BF16 || c.out_dt != DRN_BF16 || (c.residual && c.res_dt != DRN_BF16)) return DRN_ERR_UNSUPPORTED;
-  if ((c.Cin & 63) || (c.Cout & 7) || c.KH * c.KW > 32 || (c.ldy & 7) || (c.residual && (c.ldres & 7))) return DRN_ERR_UNSUPPORTED;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (!al16(c.X) || !al16(c.Wt) || !al16(c.Y) || (c.residual && !al16(c.residual)) || (c.ldw * 2) % 16 != 0 ||
-      (c.scale && !al16(c.scale)) || (c.bias && !al16(c.bias)))
-    return DRN_ERR_UNSUPPORTED;
-  if ((long)c.Cout * c.ldw * 2 >= 0xFFFFFFF0L || (long)c.Nb * c.H * c.W * c.Cin * 2 >= 0xFFFFFFF0L) return DRN_ERR_UNSUPPORTED;
-  const int nslab = c.KH * c.KW * (c.Cin >> 6);
-  const long t128 = (((long)c.Ho * c.Wo + 127) / 128) * ((c.Cout + 127) / 128);
-  if (g_tune.pp8 == 1) {
-    // measured class (tools/conv_bench.py / tools/pp8_probe.py at 800x1216, profiles/r6_*): one image's layer offers at least
-    // 5/8 of the CUs a 128x128 tile and the K loop is long enough to amortise the ring's prologue.  (1x1 layers with >= 192 tiles
-    // of 256x256 never get here: drn_conv2d_nhwc_q sends them to conv1x1_pp_kernel first - its tile moves half the bytes per MFMA.)
-    if (nslab < 4 || t128 * 8 < 5L * cus || c.Cout < 128) return DRN_ERR_UNSUPPORTED;
-  }
+// the 256x128 form where one image's layer gives it at least ~5/8 of the CUs' worth of tiles (its tiles are twice the work)
+__attribute__((visibility("hidden"))) bool drn_pp8_wide_ok(long rows_one, int N, const DrnTune& t, int cus) {
+  if (t.pp8_wide == 0) return false;
+  if (t.pp8_wide == 2) return true;
+  const long t256 = ((rows_one + 255) / 256) * ((N + 127) / 128);
+  return t256 * 8 >= 5L * cus;
+}
+
+// (hidden: called by conv_fwd_launch in gemm_conv.hip.  conv_fwd_plan there has decided that the layer is in the kernel's class - bf16,
+// Cin % 64 == 0, 16-byte rows and pointers, 32-bit byte offsets - and which form runs it: wide = the 256x128 tile)
+__attribute__((visibility("hidden"))) int drn_pp8_conv_launch(const ConvParams& c, bool wide, hipStream_t st) {
   Pp8Params p{};
   p.A = c.X; p.a_bytes = (unsigned)((long)c.Nb * c.H * c.W * c.Cin * 2); p.pix_b = (unsigned)(c.Cin * 2);
   p.B = c.Wt; p.ldb_b = (unsigned)(c.ldw * 2);
@@ -595,7 +580,7 @@ __attribute__((visibility("hidden"))) int drn_pp8_conv_try(const ConvParams& c, 
   p.spt = c.Cin >> 6;
   p.scale = c.scale; p.bias = c.bias; p.residual = c.residual; p.ldres = c.ldres; p.res_mult = c.res_mult; p.relu = c.relu;
   p.Y = c.Y; p.ldy = c.ldy;
-  return launch_pp8_any<PP8_CONV>(p, pp8_wide_ok((long)c.Ho * c.Wo, c.Cout, cus), st);
+  return launch_pp8_any<PP8_CONV>(p, wide, st);
 }
 
 extern "C" {
@@ -621,7 +606,7 @@ int drn_linear_act_fwd(const void* A, const void* W, const float* bias, const fl
   p.bias = bias; p.relu = relu;
   p.Y = (char*)out; p.ldy = ld_out; p.YT = (char*)outT; p.ldyt = ld_outT;
   p.mask = mask; p.seed = seed; p.seed_dev = seed_dev; p.drop_p = drop_p;
-  return launch_pp8_any<PP8_FC>(p, pp8_wide_ok(M, N, drn_launch::cu_count()), (hipStream_t)stream);
+  return launch_pp8_any<PP8_FC>(p, drn_pp8_wide_ok(M, N, g_tune, drn_launch::cu_count()), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -266,6 +266,39 @@ def conv2d_nhwc_q(x, w_packed, cout, kh, kw, stride, pad, dil, scale, bias, out_
     return y
 
 
+# the kernel codes of drn_conv2d_plan (#define DRN_CONV_KIND_* of include/drn_wsod.h; tests/test_conv_plan_cpu.py holds them equal)
+CONV_KIND_PATCH_C64 = 1
+CONV_KIND_PP256 = 2
+CONV_KIND_PP8 = 3
+CONV_KIND_PP8_WIDE = 4
+CONV_KIND_RING_64 = 5
+CONV_KIND_RING_128 = 6
+CONV_KIND_K2 = 7
+CONV_KIND_KS = 8
+CONV_KIND_TILED_64 = 9
+CONV_KIND_TILED_128X64 = 10
+CONV_KIND_TILED_128 = 11
+CONV_KIND_FP8_K16 = 0x100
+CONV_KINDS_TILED = (CONV_KIND_TILED_64, CONV_KIND_TILED_128X64, CONV_KIND_TILED_128)
+
+
+def conv2d_plan(x, w_packed, cout, kh, kw, stride, pad, dil, scale, bias, out_dtype, residual=None, res_mult=1.0,
+                relu=False, cus=0):
+    """drn_conv2d_plan: the kernel (CONV_KIND_*, CONV_KIND_FP8_K16 or-ed in for the K = 16 fp8 form) that conv2d_nhwc_q runs
+    these arguments on under the knobs as they stand, on a device of `cus` compute units (0: this device's).  Host-only:
+    nothing is launched, allocated or dereferenced, so the tensors may live anywhere."""
+    assert x.is_contiguous() and x.dim() == 4 and x.dtype == w_packed.dtype
+    n, h, w, cin = x.shape
+    at = lambda t: None if t is None else t.data_ptr()
+    y = 4096  # (the output conv2d_nhwc_q allocates: a fresh, aligned tensor)
+    rc = C.lib().drn_conv2d_plan(at(x), at(w_packed), y, at(scale), at(bias), at(residual), n, h, w, cin, cout, kh, kw, stride, pad,
+                                 dil, _2d(w_packed), cout, cout, int(relu), C.dt(x.dtype), C.dt(out_dtype),
+                                 C.dt(residual.dtype) if residual is not None else 0, float(res_mult), int(cus))
+    if rc < 0:
+        raise C.DrnError("drn_conv2d_plan failed: %s (%d)" % (C._ERR.get(rc, "error"), rc))
+    return rc
+
+
 def conv3x3_pw_nhwc(x, w2_packed, scale2, bias2, relu2, w3_packed=None, scale3=None, bias3=None, residual=None, res_mult=1.0,
                     relu3=True, pool=False, out=None):
     """drn_conv3x3_pw_nhwc: 3x3 (64 -> 64, pad 1) -> act [-> 1x1 (64 -> 256) + residual -> act] [-> 2x2 / stride-2 max pool] as

@@ -92,6 +92,27 @@ int drn_conv2d_nhwc_q(const void* x, const void* w, void* y, const float* scale,
                       int pad, int dil, long ldw, long ldy, long ldres, int relu, int dtype, int out_dtype,
                       int res_dtype, float res_mult, void* stream);
 
+/* Host-side query, no launch: the kernel drn_conv2d_nhwc_q runs these arguments on, with the knobs (drn_tune) as they stand,
+ * on a device of `cus` compute units (cus <= 0: the current device's; 256 when there is none).  The arguments are those of
+ * drn_conv2d_nhwc_q without the stream; pointers are inspected for NULL and alignment, never dereferenced.  Returns a
+ * DRN_CONV_KIND_* code, with DRN_CONV_KIND_FP8_K16 or-ed in when fp8 operands run the K = 16 MFMA form (DRN_TUNE_FP8_K64 = 0),
+ * or DRN_ERR_ARG for exactly the arguments drn_conv2d_nhwc_q refuses.  Tests and tools read the kernel choice off it. */
+#define DRN_CONV_KIND_PATCH_C64 1    /* conv3x3_c64_kernel: LDS-resident patch, 3x3 / 64 -> 64 channels of a large map */
+#define DRN_CONV_KIND_PP256 2        /* conv1x1_pp_kernel: 1x1 on the 256x256 ping-pong GEMM mainloop */
+#define DRN_CONV_KIND_PP8 3          /* pp8_kernel, the 128x128 form */
+#define DRN_CONV_KIND_PP8_WIDE 4     /* pp8_kernel, the 256x128 form */
+#define DRN_CONV_KIND_RING_64 5      /* conv_ring_kernel, 64x64 tile */
+#define DRN_CONV_KIND_RING_128 6     /* conv_ring_kernel, 128x128 tile */
+#define DRN_CONV_KIND_K2 7           /* conv_nhwc_k2_kernel: two K-groups per 64x64 tile */
+#define DRN_CONV_KIND_KS 8           /* conv_nhwc_ks_kernel: 32x32 tile, wave-K-split */
+#define DRN_CONV_KIND_TILED_64 9     /* conv_nhwc_kernel, 64x64 tile */
+#define DRN_CONV_KIND_TILED_128X64 10 /* conv_nhwc_kernel, 128x64 tile */
+#define DRN_CONV_KIND_TILED_128 11   /* conv_nhwc_kernel, 128x128 tile */
+#define DRN_CONV_KIND_FP8_K16 0x100  /* flag: fp8 operands on the K = 16 non-scaled MFMA */
+int drn_conv2d_plan(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* residual, int Nb,
+                    int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil, long ldw, long ldy, long ldres,
+                    int relu, int dtype, int out_dtype, int res_dtype, float res_mult, int cus);
+
 /* The tail of a 64-channel bottleneck block on a large map as ONE launch (BottleneckBlock.forward,
  * projects/WSL/wsl/modeling/backbone/resnet_ws.py:217-237: conv2 -> relu -> conv3 -> + shortcut -> relu [-> max pool]):
  * y = pool(act3((conv1x1(act2(conv3x3(x) * scale2 + bias2)) * scale3 + bias3) + residual * res_mult)), bf16;
@@ -335,7 +356,7 @@ int drn_gemm_set_tile(int tile);
 #define DRN_TUNE_ROI_LANE_REPS 22 /* lane-per-bin ROIPool on maps that leave one block per CU: groups of 64 ROIs a block walks with one staged map slice (0 = default: 4, halved while fewer than two rounds of blocks would remain; 1 = a block per group) */
 #define DRN_TUNE_CONV_RING 23 /* register-ring conv kernels (conv_ring.hip; bf16, Cin % 64 == 0, layers beyond the latency-bound small maps): 0 = off (the tiles of gemm_conv.hip), 1 = default (64x64 tile, class by measurement), 64 / 128 = pin the 64x64 / 128x128 tile (any other value is ignored: drn_tune returns the unchanged setting); every tile gives the same bits as the 64x64 / 128x128 tiled kernel */
 #define DRN_TUNE_CONV_PP 24 /* 1x1 / stride-1 bf16 convs of large maps on the 256x256 ping-pong GEMM mainloop with the conv epilogue (conv1x1_pp_kernel): 0 = off, 1 = default (Cout >= 256 and >= 192 tiles of 256x256 per image, or >= 100 tiles with K >= 1024), n > 1 = at least n tiles, any Cout; same bits as the tiled kernels */
-#define DRN_TUNE_PP8 25 /* eight-wave ping-pong kernel (pp8.hip: 128x128 or 256x128 tile, two waves per SIMD half a phase apart; bf16 convs with Cin % 64 == 0 and drn_linear_act_fwd): 0 = off, 1 = default class (measured per layer shape, see drn_pp8_conv_try), 2 = every layer in the kernel's class; same bits as the tiled kernels */
+#define DRN_TUNE_PP8 25 /* eight-wave ping-pong kernel (pp8.hip: 128x128 or 256x128 tile, two waves per SIMD half a phase apart; bf16 convs with Cin % 64 == 0 and drn_linear_act_fwd): 0 = off, 1 = default class (measured per layer shape, see conv_fwd_plan), 2 = every layer in the kernel's class; same bits as the tiled kernels */
 #define DRN_TUNE_PP8_STAGES 26 /* 3 / 4 / 5 (default 5): 32-KB LDS stages of the 128x128 form's ring = 1 / 2 / 3 K slabs in flight (A/B knob; bit-identical) */
 #define DRN_TUNE_PP8_VARIANT 27 /* schedule variant of that kernel (A/B knob; bit-identical): 0 = a slab's four DMA pieces in the fragment-read phase, 1 (default) = two there and two between the MFMAs, 2 = all between the MFMAs, + 4 = no s_setprio around the MFMAs, + 8 = profile build (shader-clock split of the mainloop) */
 #define DRN_TUNE_PP8_PROFILE 28 /* any value: print (stderr) and clear the per-phase shader-clock sums the profile builds (DRN_TUNE_PP8_VARIANT + 8) accumulated for workgroup 0; returns 0 */

@@ -55,10 +55,10 @@ def test_conv_fp8(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, k64):
     bf_res = out == "fp8bf16res"
     out = "fp8" if bf_res else out
     with drn.tuned({drn.TUNE_FP8_K64: k64}):
-        _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res)
+        _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res, k64)
 
 
-def _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res):
+def _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res, k64):
     rs = np.random.RandomState(3)
     x = torch.from_numpy(np.abs(rs.standard_normal((N, H, W, cin))).astype(np.float32))
     w = torch.from_numpy((rs.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32))
@@ -85,9 +85,10 @@ def _conv_fp8_case(drn, N, H, W, cin, cout, k, pad, dil, res, relu, out, bf_res)
     wp[:, : k * k * cin] = wq.float().permute(0, 2, 3, 1).reshape(cout, -1)
     alpha = (bn_scale * s_y / (s_x * s_w)).float().contiguous().to(DEV)
     beta = (bn_bias * s_y).float().contiguous().to(DEV)
-    y = drn.conv2d_nhwc_q(xq.to(DEV), wp.to(FP8).to(DEV), cout, k, k, 1, pad, dil, alpha, beta,
-                          FP8 if out == "fp8" else torch.bfloat16, r_q.to(DEV) if res else None,
-                          s_y / s_r if res else 1.0, relu)
+    args = (xq.to(DEV), wp.to(FP8).to(DEV), cout, k, k, 1, pad, dil, alpha, beta, FP8 if out == "fp8" else torch.bfloat16,
+            r_q.to(DEV) if res else None, s_y / s_r if res else 1.0, relu)
+    y = drn.conv2d_nhwc_q(*args)
+    assert bool(drn.conv2d_plan(*args) & drn.CONV_KIND_FP8_K16) == (not k64)  # the MFMA form the test says it runs
     torch.cuda.synchronize()
     # the kernel's pre-rounding value equals `ref` up to fp32 summation order (the products are exact): eps below; the
     # stored value must then be a correct rounding of SOME value within eps of ref: |stored - ref| <= ulp(ref)/2 + eps

@@ -403,10 +403,13 @@ def test_conv3x3_c64_patch_kernel(drn, case):
     if relu:
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, 64)
+    plan = lambda: drn.conv2d_plan(xd, wp, 64, 3, 3, 1, 1, 1, scale, bias, dtype, res, 1.0, relu)
     with drn.tuned({drn.TUNE_CONV_PATCH: 1}):
         y1 = drn.conv2d_nhwc(xd, wp, 64, 3, 3, 1, 1, 1, scale, bias, res, relu)
+        assert plan() == drn.CONV_KIND_PATCH_C64
         drn.tune(drn.TUNE_CONV_PATCH, 0)
         y0 = drn.conv2d_nhwc(xd, wp, 64, 3, 3, 1, 1, 1, scale, bias, res, relu)
+        assert plan() == drn.CONV_KIND_RING_64  # (with the patch kernel off these maps run on the ring kernel, itself bit-identical to the tiled one)
     torch.cuda.synchronize()
     assert torch.equal(y1, y0)
     got = y1.float().cpu().permute(0, 3, 1, 2)
@@ -438,10 +441,13 @@ def test_conv2d_wave_k_split(drn, dtype, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, k, k, stride, pad, dil, scale, bias, res, relu)
+    plan = lambda: drn.conv2d_plan(xd, wp, cout, k, k, stride, pad, dil, scale, bias, dtype, res, 1.0, relu)
     with drn.tuned({drn.TUNE_CONV_KSPLIT: 0}) as prev:
         assert prev[drn.TUNE_CONV_KSPLIT] == 1
         tiled = run()
+        assert plan() in drn.CONV_KINDS_TILED
     ys = [run() for _ in range(3)]
+    assert plan() == drn.CONV_KIND_KS
     for y in ys[1:]:
         assert torch.equal(y, ys[0])
     got = ys[0].float().cpu().permute(0, 3, 1, 2)
@@ -487,13 +493,16 @@ def test_conv_ring_kernels(drn, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, k, k, stride, pad, dil, scale, bias, res, relu)
+    plan = lambda: drn.conv2d_plan(xd, wp, cout, k, k, stride, pad, dil, scale, bias, dtype, res, 1.0, relu)
     with drn.tuned({drn.TUNE_CONV_RING: 0, drn.TUNE_CONV_K2_TILES: 0, drn.TUNE_CONV_KSPLIT: 0, drn.TUNE_PP8: 0}) as prev:
         assert prev[drn.TUNE_CONV_RING] == 1
         tiled = run()  # conv_nhwc_kernel<64x64 | 128x128>
+        assert plan() in drn.CONV_KINDS_TILED
         ys = {}
         for pin in (64, 128, 1):
             drn.tune(drn.TUNE_CONV_RING, pin)
             ys[pin] = run()
+            assert pin == 1 or plan() == {64: drn.CONV_KIND_RING_64, 128: drn.CONV_KIND_RING_128}[pin]
         drn.tune(drn.TUNE_CONV_RING, 64)
         again = run()
     torch.cuda.synchronize()
@@ -538,9 +547,11 @@ def test_pp8_conv_kernel(drn, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, k, k, stride, pad, dil, scale, bias, res, relu)
+    plan = lambda: drn.conv2d_plan(xd, wp, cout, k, k, stride, pad, dil, scale, bias, dtype, res, 1.0, relu)
     with drn.tuned({drn.TUNE_PP8: 0, drn.TUNE_CONV_RING: 0, drn.TUNE_CONV_K2_TILES: 0, drn.TUNE_CONV_KSPLIT: 0, drn.TUNE_CONV_PP: 0}) as prev:
         assert prev[drn.TUNE_PP8] == 1
         tiled = run()  # conv_nhwc_kernel<64x64 | 128x128>
+        assert plan() in drn.CONV_KINDS_TILED
         drn.tune(drn.TUNE_PP8, 2)
         ys = {}
         for stages, variant, wide in ((3, 0, 0), (4, 0, 0), (4, 1, 0), (5, 0, 0), (5, 2, 0), (5, 5, 0), (5, 1, 0), (5, 1, 2), (5, 0, 2),
@@ -549,6 +560,7 @@ def test_pp8_conv_kernel(drn, case):
                             drn.TUNE_PP8_WIDE: wide,  # 2: the 256x128 form (three 48-KB stages) whatever the tile count
                             drn.TUNE_PP8_WIDE_VARIANT: 5 if variant else 0}):  # (its two DMA placements)
                 ys[(stages, variant, wide)] = [run() for _ in range(3)]
+                assert wide == 1 or plan() == (drn.CONV_KIND_PP8_WIDE if wide else drn.CONV_KIND_PP8)
     torch.cuda.synchronize()
     for stages, lst in ys.items():
         for y in lst:
@@ -660,11 +672,14 @@ def test_conv1x1_pp_kernel(drn, case):
         ref = F.relu(ref)
     wp = _pack_w(wt, dtype, drn, cin)
     run = lambda: drn.conv2d_nhwc(xd, wp, cout, 1, 1, 1, 0, 1, scale, bias, res, relu)
+    plan = lambda: drn.conv2d_plan(xd, wp, cout, 1, 1, 1, 0, 1, scale, bias, dtype, res, 1.0, relu)
     with drn.tuned({drn.TUNE_CONV_PP: 0, drn.TUNE_CONV_RING: 0, drn.TUNE_CONV_K2_TILES: 0, drn.TUNE_CONV_KSPLIT: 0, drn.TUNE_PP8: 0}) as prev:
         assert prev[drn.TUNE_CONV_PP] == 1
         tiled = run()  # conv_nhwc_kernel<128x128>
+        assert plan() in drn.CONV_KINDS_TILED
         drn.tune(drn.TUNE_CONV_PP, 2)  # (any layer of >= 2 tiles)
         y = run()
+        assert plan() == drn.CONV_KIND_PP256
         again = run()
     torch.cuda.synchronize()
     assert torch.equal(y, tiled), float((y.float() - tiled.float()).abs().max())

@@ -63,7 +63,8 @@ else:
 if os.environ.get("CONV_BENCH_EXTRA"):  # the +res layers without their residual: what the epilogue's reads cost
     LAYERS += [("res2 conv3 1x1 64>256 (no res)", h4, w4, 64, 256, 1, 1, False, 0), ("res3 conv3 1x1 128>512 (no res)", h8, w8, 128, 512, 1, 1, False, 0)]
 tot_us = tot_gf = 0.0
-print("%-30s %9s %8s %8s %9s %8s" % ("%s @ %dx%d" % (WORKLOAD, H, W), "pixels", "us", "TFLOP/s", "GB/s", "x count"))
+print("%-30s %9s %8s %8s %9s %8s  %s" % ("%s @ %dx%d" % (WORKLOAD, H, W), "pixels", "us", "TFLOP/s", "GB/s", "x count", "kernel"))
+KIND = {v: n[len("CONV_KIND_"):].lower() for n, v in vars(ops).items() if n.startswith("CONV_KIND_") and isinstance(v, int)}
 ONLY = os.environ.get("CONV_ONLY")  # substring filter on the layer names
 for name, h, w, cin, cout, k, dil, res, cnt in LAYERS:
     if ONLY and ONLY not in name:
@@ -95,7 +96,9 @@ for name, h, w, cin, cout, k, dil, res, cnt in LAYERS:
     us = a.elapsed_time(b) / 100 * 1e3
     gf = 2.0 * h * w * k * k * cin * cout / 1e9
     mb = (h * w * (cin + cout * (2 if res else 1)) + k * k * cin * cout) * es / 1e6
-    print("%-30s %9d %8.1f %8.1f %9.0f %8d" % (name, h * w, us, gf / us * 1e3, mb / us * 1e3, cnt))
+    kind = ops.conv2d_plan(x, wt, cout, k, k, 1, pad, dil, scale, bias, dt, r, 1.0, True)  # what drn_conv2d_nhwc_q ran it on
+    print("%-30s %9d %8.1f %8.1f %9.0f %8d  %s%s" % (name, h * w, us, gf / us * 1e3, mb / us * 1e3, cnt, KIND[kind & 0xff],
+                                                    " (fp8 K = 16)" if kind & ops.CONV_KIND_FP8_K16 else ""))
     tot_us += us * cnt
     tot_gf += gf * cnt
 print("sum over the trunk's convs (stem.conv1 excluded): %.0f us, %.1f GF -> %.0f TFLOP/s = %.3f of the dense %s MFMA peak" % (
