@@ -203,8 +203,8 @@ def test_unfrozen_backbone_train_step_fp32(name, freeze_at):
     # and lands on different sides of the ReLU in the two fp32 summation orders (measured: the only mask mismatch in
     # the whole trunk).  That moves one pixel's contribution in plain2.0.conv1 and everything below it, which a
     # max-norm comparison sees at the 1e-2 level; those tensors get the relaxed bound, all others the tight one.
-    # Every conv / pool backward call inside this very backward was checked against CPU autograd on its own inputs
-    # (<= 2e-6 relative).
+    # That every conv / pool / block backward is right on its own inputs - per element, at the device's saved masks - is
+    # what tests/test_trunk_bwd_gpu.py checks (test_conv_backward_layer, test_maxpool2x2_bwd, test_block_backward).
     def loose(n):
         return (name, freeze_at) == ("model_vgg16_small", 0) and (".plain1." in n or ".plain2.0.conv1." in n)
 
