@@ -71,6 +71,8 @@ _SIGS = {
     "drn_sgd_step_clip": "pppilpipifif" + "ifp" + "p",
     "drn_sgd_step_block_clip": "pppilpip" + "iiiil" + "fif" + "ifp" + "p",
     "drn_loss_guard": "piiipp",
+    "drn_head_metrics": "plpiipipp",
+    "drn_metrics_record": "pipiipipp",
     "drn_sgd_step_guard": "pppilpipifif" + "ifp" + "pp",
     "drn_sgd_step_block_guard": "pppilpip" + "iiiil" + "fif" + "ifp" + "pp",
     "drn_gemm_tn_sgd_guard": "ppp" + "iiii" + "lll" + "ppplp" + "fif" + "pp",

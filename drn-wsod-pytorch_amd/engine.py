@@ -1150,7 +1150,13 @@ class DataParallel:
 class Trainer:
     """projects/WSL/tools/train_net.py:41-117 (run_step) over detectron2/engine/train_loop.py:170-289."""
 
-    def __init__(self, cfg, model, data_loader_iter, optimizer=None, scheduler=None, parallel=None, start_iter=0):
+    def __init__(self, cfg, model, data_loader_iter, optimizer=None, scheduler=None, parallel=None, start_iter=0,
+                 metrics_period=0, metrics_slots=256):
+        """metrics_period N > 0: every step's losses and the OICR branches' label statistics are recorded on the device
+        (ROIHeads.enable_metrics, metrics.MetricsRing); every N iterations the ring is drained - a stream-ordered copy, no sync -
+        and the PREVIOUS drain, long complete by then, is decoded into self.storage at the records' own iterations, with `lr`
+        from the host when a scheduler is present.  flush_metrics() collects what is still under way.  0 (default): off, every
+        launch as before.  More than one rank: each rank logs its own records (no cross-rank average)."""
         self.cfg, self.model = cfg, model
         self._it = data_loader_iter
         self.optimizer = optimizer or build_optimizer(cfg, model)
@@ -1170,6 +1176,33 @@ class Trainer:
             if getattr(self.dp, "exchange", False):
                 self.optimizer._refuse_guard_multi_rank("a gradient exchange")
             self._anchor_guard()
+        self.metrics_period = int(metrics_period)
+        self.metrics, self._lr_log = None, {}
+        if self.metrics_period > 0:
+            if self.metrics_period > metrics_slots:
+                raise DrnError("metrics_period %d exceeds the ring's %d slots: records would be lost between drains"
+                               % (self.metrics_period, metrics_slots))
+            self.metrics = model.roi_heads.enable_metrics(metrics_slots)
+            self.metrics.iter0 = self.iter
+
+    def _feed_metrics(self, wait):
+        """decode the last drain into the storage (wait: synchronise its event - and nothing else - first)"""
+        recs, lost = self.metrics.collect(wait=wait)
+        for it, scalars in recs:
+            if it in self._lr_log:
+                scalars = dict(scalars, lr=self._lr_log.pop(it))
+            for k, v in scalars.items():
+                self.storage.put_scalar_at(k, v, it, smoothing_hint=k != "lr")
+        return lost
+
+    def flush_metrics(self):
+        """drain now and wait for that one copy: everything recorded so far is in self.storage afterwards.  Returns the
+        number of records lost (overwritten in the ring before a drain reached them)."""
+        if self.metrics is None:
+            return 0
+        lost = self._feed_metrics(True)
+        self.metrics.drain()
+        return lost + self._feed_metrics(True)
 
     def _anchor_guard(self):
         """the guard counts checks; the next one is iteration self.iter"""
@@ -1185,6 +1218,8 @@ class Trainer:
             self.storage = EventStorage(self.start_iter)
             if self._guard is not None:
                 self._anchor_guard()
+            if self.metrics is not None:
+                self.metrics.iter0 = self.iter - int(self.metrics.state[0])
         return extra
 
     def run_step(self):
@@ -1220,6 +1255,13 @@ class Trainer:
             self.dp.finish()
             self.optimizer.step(self.dp.grad_scale)
             self.optimizer.zero_grad()
+        if self.metrics is not None:
+            if self.scheduler is not None:  # hooks.LRScheduler.after_step (hooks.py:228-231): the lr this iteration ran with, of
+                # the largest parameter group
+                self._lr_log[self.iter] = max(self.optimizer.param_groups, key=lambda g: g["cnt"])["lr"]
+            if (self.iter - self.start_iter + 1) % self.metrics_period == 0:
+                self._feed_metrics(True)  # the previous drain: metrics_period steps old
+                self.metrics.drain()
         if self.scheduler is not None:
             # hooks.LRScheduler.after_step (detectron2/engine/hooks.py:232-235) runs after EVERY iteration: SOLVER.STEPS,
             # WARMUP_ITERS and MAX_ITER count micro-iterations also when WSL.ITER_SIZE > 1

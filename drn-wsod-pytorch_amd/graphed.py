@@ -87,6 +87,22 @@ class _StaticInputs:
         self.losses = None
         self.engine.pool_sets_pinned = None  # a new step captures anew: the previous owner's pin (if any) is void
         self.engine.pool_sets_pin_owner = None
+        self.engine.captured_by = None  # weakref to the step whose captured graphs hold the engine's launch sequence
+
+    @property
+    def metrics(self):
+        """the head engine's MetricsRing (ROIHeads.enable_metrics(), BEFORE this step is primed: the two launches are captured
+        with the heads like any other), or None"""
+        return getattr(self.engine, "metrics", None)
+
+    def _anchor_metrics(self, start_iter):
+        """the ring counts records; the next one is iteration start_iter (one small D2H read, at construction)"""
+        if self.metrics is not None:
+            self.metrics.iter0 = int(start_iter) - int(self.metrics.state[0])
+
+    def _mark_captured(self):
+        self.engine.captured_by = weakref.ref(self)
+        self._metrics_keep = self.metrics  # the captured launches write into its buffers: they live as long as the graphs
 
     def _new_rois(self):
         """[M, 5] rows (image index, box): the index column is written once, here"""
@@ -246,6 +262,7 @@ class GraphedTrainStep(_StaticInputs):
         if self._guard is not None:
             self._guard.window_first = self.iter_size == 1
             self._guard.iter0 = self._start_iter - self._guard.read()["calls"]
+        self._anchor_metrics(self._start_iter)
 
     def release(self):
         """give the fc6 operand sets back (they may grow again); the captured graphs of this object must not be replayed
@@ -254,6 +271,9 @@ class GraphedTrainStep(_StaticInputs):
         if own is not None and own() is self:
             self.engine.pool_sets_pinned = None
             self.engine.pool_sets_pin_owner = None
+        own = getattr(self.engine, "captured_by", None)
+        if own is not None and own() is self:
+            self.engine.captured_by = None
         self._primed = False
 
     # ---- host side of one step: stage inputs into the static buffers (tiny async copies) -----------------------
@@ -467,6 +487,7 @@ class GraphedTrainStep(_StaticInputs):
         self.g_pbb = [_captured(self._bb_body, slot)[0] for slot in range(P)]
         self.g_main, self.losses = _captured(self._main_body)
         self._primed = True
+        self._mark_captured()
         return first
 
     # ---- lookahead = 1 ------------------------------------------------------------------------------------------------------------
@@ -518,6 +539,7 @@ class GraphedTrainStep(_StaticInputs):
         self.g_main, self.losses = _captured(self._main_body)
         self.g_pool = _captured(self._pool_body)[0]
         self._primed = True
+        self._mark_captured()
         return first
 
     def step(self, batch, next_batch, *upcoming):
@@ -569,7 +591,7 @@ class GraphedFullStep(_StaticInputs):
     only pay when the optimizer can update one while the next is still being produced, which the plain optimizer step of a
     trainable trunk does not do."""
 
-    def __init__(self, model, optimizer, example_batch, parallel=None):
+    def __init__(self, model, optimizer, example_batch, parallel=None, start_iter=0):
         if getattr(optimizer, "_pipelined", False):
             raise DrnError("GraphedFullStep uses the plain optimizer step (the pipelined mode assumes a frozen trunk)")
         super().__init__(model, optimizer, example_batch)
@@ -590,6 +612,7 @@ class GraphedFullStep(_StaticInputs):
             if self.dp is not None:
                 optimizer._refuse_guard_multi_rank("a gradient exchange")
             self._guard.window_first = True
+        self._anchor_metrics(start_iter)  # (start_iter: the training iteration of the first step, for the metrics ring alone)
 
     def _stage(self, batch):
         self._stage_labels(batch)
@@ -687,6 +710,7 @@ class GraphedFullStep(_StaticInputs):
                 self.g_step, self.losses = _captured(self._fwd_bwd)
                 self.g_trunk = _captured(self._trunk_bwd)[0]
                 self.g_opt = _captured(self._opt_body)[0]
+            self._mark_captured()
             return first
         self.opt.refresh_tables()
         self.g_step.replay()

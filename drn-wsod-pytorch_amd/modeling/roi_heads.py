@@ -995,6 +995,7 @@ class _HeadEngine:
                                argmax=pooled.get("argmax"))
         self._last_state = state
         self._guard_check(state["loss_list"])
+        self._metrics_record(loss_names, state, n_img, [] if pcl else [col["r%d" % k] for k in range(h.refine_K)])
         outs = _TrainFn.apply(self.anchor, self, state)
         return dict(zip(loss_names, outs)), state
 
@@ -1004,6 +1005,16 @@ class _HeadEngine:
         g = getattr(self, "loss_guard", None)
         if g is not None:
             g.check(loss_list)
+
+    def _metrics_record(self, loss_names, state, n_img, col0s):
+        """per-step metrics (ROIHeads.enable_metrics; drn_head_metrics + drn_metrics_record) right behind the guard's check, on
+        the stream that computed the losses: the label statistics of the OICR branches in `col0s` against the labels their
+        losses used, then the step's record.  WSDDN / CSC / PCL heads pass no branch (the reference logs no label accuracy for
+        them: PCLOutputs.losses never calls _log_accuracy).  Off = the attribute is None and no launch changes."""
+        m = getattr(self, "metrics", None)
+        if m is not None:
+            m.record(loss_names, state["loss_list"], n_img, state["M"], state["w"]["logits"], col0s, self.h.num_classes,
+                     [t["labels"] for t in state["aux"]["targets"]] if col0s else ())
 
     # ---- CSCROIHeads -----------------------------------------------------------------------------------
     def _forward_csc(self, w, col, M, dtype, rois, objectness, feat_nhwc, pooled, gt, img_off, n_img, masks, drop_p,
@@ -1029,6 +1040,7 @@ class _HeadEngine:
             state["fg"] = dict(fg, hook=fg_hook)
         self._last_state = state
         self._guard_check(state["loss_list"])
+        self._metrics_record(["loss_cls_pos", "loss_cls_neg"], state, 1, [])
         outs = _TrainFn.apply(self.anchor, self, state)
         return dict(zip(["loss_cls_pos", "loss_cls_neg"], outs)), state
 
@@ -1460,6 +1472,25 @@ class OICRROIHeads(ROIHeads):
         if z is None or z.shape != (n_img, K) or z.device != dev:
             z = self._zero_oh = torch.zeros((n_img, K), dtype=torch.float32, device=dev)
         return z
+
+    def enable_metrics(self, slots=256):
+        """Record every training step's losses and, for OICR branches, label statistics into a device-side ring of `slots`
+        records (metrics.MetricsRing, returned): two small launches behind the loss tail, no host sync.  A graphed step freezes
+        its launch sequence when it is primed, so this has to come first: enable_metrics() -> build / prime the graphed step."""
+        from ..metrics import MetricsRing
+
+        eng = self._engine
+        owner = getattr(eng, "captured_by", None)
+        if owner is not None and owner() is not None:
+            raise DrnError("enable_metrics() after a graphed step was primed: its captured launches would never record.  Order: "
+                           "enable_metrics(), then create and prime the GraphedTrainStep / GraphedFullStep")
+        eng.ensure(next(self.parameters()).device)
+        eng.metrics = MetricsRing(slots, eng.arena_w.device)
+        return eng.metrics
+
+    def disable_metrics(self):
+        """back to the launch sequence without metrics (eager steps at once; a primed graphed step keeps what it captured)"""
+        self._engine.metrics = None
 
     def prefetch_pooled(self, features, proposals):
         """pool a FUTURE batch's proposals (on whatever stream is current) into the engine's spare buffer set"""

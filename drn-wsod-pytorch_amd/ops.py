@@ -907,6 +907,68 @@ def loss_guard(losses, mode, window_first, state):
            C.stream())
 
 
+# include/drn_wsod.h: DRN_METRICS_*
+METRICS_MAX_HEADS, METRICS_MAX_LOSSES, METRICS_COUNTERS, METRICS_COUNT_STRIDE = 8, 16, 6, 8
+METRICS_ROWS_PER_BLOCK, METRICS_RECORD_WORDS = 64, 72
+
+
+def head_metrics_rows(K):
+    """(rows one wave of drn_head_metrics holds at a time, rows of one workgroup) for K foreground classes"""
+    lanes = 2
+    while lanes < 64 and lanes < (K + 7) // 4:
+        lanes *= 2
+    return 64 // lanes, METRICS_ROWS_PER_BLOCK
+
+
+def metrics_ring(slots, device):
+    """Device side of the per-step metrics: ONE int32 allocation [4 + slots * METRICS_RECORD_WORDS] (so a drain is one copy), its
+    views `state` (int32[4], [0] = records written) and `ring` ([slots, METRICS_RECORD_WORDS]), and the zeroed counts scratch
+    of head_metrics() (int32[METRICS_MAX_HEADS, METRICS_COUNT_STRIDE])."""
+    slots = int(slots)
+    if slots < 1:
+        raise C.DrnError("metrics_ring(): %d slots" % slots)
+    buf = torch.zeros((4 + slots * METRICS_RECORD_WORDS,), dtype=torch.int32, device=device)
+    return dict(buf=buf, state=buf[:4], ring=buf[4:].view(slots, METRICS_RECORD_WORDS),
+                counts=torch.zeros((METRICS_MAX_HEADS, METRICS_COUNT_STRIDE), dtype=torch.int32, device=device))
+
+
+def head_metrics(logits, col0s, K, labels, M, counts):
+    """drn_head_metrics: per refinement branch k, the six label counters of rows 0 .. M-1 - n_ig, n_bg, n_fg, n_acc, n_fg_acc,
+    n_fneg with p = first arg-max of logits[r, col0s[k] : col0s[k] + K + 1] and g = labels[k][r] - ADDED into counts[k, 0:6]
+    (zero on entry; metrics_record() clears it again).  labels: an int32 [nh, M] tensor or a list of nh int32 [M] tensors."""
+    nh = len(col0s)
+    if nh > METRICS_MAX_HEADS or K + 1 > 1024:
+        raise C.DrnError("head_metrics(): %d branches of %d columns (at most %d of at most 1024 are built)"
+                         % (nh, K + 1, METRICS_MAX_HEADS))
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] >= M
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == METRICS_MAX_HEADS * METRICS_COUNT_STRIDE
+    rows = [labels[k] for k in range(nh)]
+    assert len(labels) == nh
+    for t in rows:
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= M
+    ptrs = (ctypes.c_void_p * max(nh, 1))(*[t.data_ptr() for t in rows])
+    c0 = C.host_ints(list(col0s) or [0])
+    C.call("drn_head_metrics", C.ptr(logits), _2d(logits), ctypes.cast(c0, ctypes.c_void_p), nh, int(K),
+           ctypes.cast(ptrs, ctypes.c_void_p), int(M), C.ptr(counts), C.stream())
+
+
+def metrics_record(losses, counts, nh, M, ring, state):
+    """drn_metrics_record: one wave writes the step's record - index, n, nh, M, the loss bit patterns, counts[:nh, 0:6], index again -
+    into slot state[0] % slots of `ring`, advances state[0] and stores zeros back into `counts`.  No synchronisation; capturable."""
+    n = len(losses)
+    if not 1 <= n <= METRICS_MAX_LOSSES or nh > METRICS_MAX_HEADS:
+        raise C.DrnError("metrics_record(): %d loss scalars, %d branches (1 .. %d and 0 .. %d are built)"
+                         % (n, nh, METRICS_MAX_LOSSES, METRICS_MAX_HEADS))
+    for t in losses:
+        assert t.dtype == torch.float32 and t.numel() == 1 and t.is_cuda
+    assert ring.dtype == torch.int32 and ring.dim() == 2 and ring.shape[1] == METRICS_RECORD_WORDS and ring.is_contiguous()
+    assert state.dtype == torch.int32 and state.numel() == 4 and state.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == METRICS_MAX_HEADS * METRICS_COUNT_STRIDE
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in losses])
+    C.call("drn_metrics_record", ctypes.cast(ptrs, ctypes.c_void_p), n, C.ptr(counts), int(nh), int(M), C.ptr(ring),
+           ring.shape[0], C.ptr(state), C.stream())
+
+
 CLIP_NONE, CLIP_VALUE, CLIP_NORM = 0, 1, 2  # clip_mode of drn_sgd_step_clip / drn_sgd_step_block_clip
 _NORM_TYPES = {1.0: 1, 2.0: 2, float("inf"): 0}  # NORM_TYPE -> norm_type of drn_grad_norms
 

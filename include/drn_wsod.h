@@ -599,6 +599,50 @@ int drn_gemm_tn_acc_sgd_guard(const void* A, const void* Bt, const float* grad_a
                               void* shadow, long ld_w, const void* seg_dev, float momentum, int first_step, float grad_scale,
                               const int* guard, void* stream);
 
+/* ---- per-step metrics from a device-side ring ---------------------------------------------------------------------------------
+ * The reference floats every logged scalar on the host each iteration: the losses and their sum (detectron2/engine/train_loop.py:260-289,
+ * _write_metrics), per refinement branch fast_rcnn/cls_accuracy_r{k}, fg_cls_accuracy_r{k}, false_negative_r{k}
+ * (projects/WSL/wsl/modeling/roi_heads/fast_rcnn.py:1098-1126, _log_accuracy) and roi_head/num_{fg,bg,ig}_samples_r{k}
+ * (roi_heads.py:338-349, roi_heads_oicr.py:366-374).  Here the device writes ONE record per step into a ring and the host copies the
+ * ring every N steps; nothing on the step waits for it.  Two launches, both capturable, no argument that changes from step to step.
+ *
+ * drn_head_metrics: label statistics of nh refinement branches in one launch.  logits = the heads' fp32 logits [rows >= M, ldl]
+ * (4-byte aligned; 16-byte loads are used wherever a row's columns allow); col0s = HOST array of nh first-column indices, labels = HOST
+ * array of nh device pointers to int32 labels[M] (-1 ignore, K background) - both copied into the launch's arguments.  For row r of
+ * branch k: p = the FIRST maximal index of logits[r, col0_k .. col0_k + K] (torch.argmax's tie rule; +0 and -0 tie), g = labels_k[r].
+ * counts = int32[nh][DRN_METRICS_COUNT_STRIDE] in device memory, ZERO on entry; the kernel adds, as exact integers,
+ *   [0] n_ig = #{g == -1}   [1] n_bg = #{g == K}   [2] n_fg = #{0 <= g < K}
+ *   [3] n_acc = #{p == g}   [4] n_fg_acc = #{0 <= g < K, p == g}   [5] n_fneg = #{0 <= g < K, p == K}      ([6], [7] stay zero)
+ * with one atomicAdd(int*) per non-zero counter and workgroup: the result does not depend on arrival order.  A workgroup of sixteen
+ * waves owns DRN_METRICS_ROWS_PER_BLOCK consecutive rows of one branch; a row is read by L lanes of one wave, L = the smallest power of two
+ * >= max(2, (K + 7) / 4) and <= 64, so a wave holds 64 / L rows at a time.  No column outside the branches' K + 1 columns and no row
+ * >= M is read.  NaN logits: unspecified (the anomaly guard is the tool for such runs).
+ * Shape class: 0 <= nh <= 8, 1 <= K, K + 1 <= 1024, col0_k + K + 1 <= ldl, any M >= 0 (nh == 0 or M == 0: nothing is launched).
+ * Errors: DRN_ERR_UNSUPPORTED (nh > 8, K + 1 > 1024), DRN_ERR_ARG (null pointer, negative size, columns outside ldl).
+ *
+ * drn_metrics_record: one wave publishes the step's record.  losses = HOST array of n (1 .. 16) device pointers to the step's fp32
+ * loss scalars (the list drn_loss_guard gets), copied into the launch's arguments.  ring = uint32[slots][DRN_METRICS_RECORD_WORDS],
+ * state = int32[4], both device memory; state[0] = records written so far (0 before the first call; [1..3] reserved).  The record of
+ * call i goes to slot i % slots:
+ *   word 0        i (the record index)                 word 1   n          word 2   nh          word 3   M
+ *   words 4..19   bit patterns of the n losses, then zeros
+ *   words 20..67  counts[k][0..5] of branch k at 20 + 6 k, zeros for k >= nh
+ *   words 68..70  zero                                 word 71  i again (a reader accepts a record only if both index words agree)
+ * then state[0] = i + 1, and all 64 words of `counts` are stored back as ZERO: the next step's drn_head_metrics finds its scratch
+ * cleared without a memset node.  The slot comes from device memory, so a replayed graph advances through the ring; the kernel
+ * boundary between the two launches is their only hand-off (no flag, no spinning).  Ordinary vector stores only.
+ * Errors: DRN_ERR_UNSUPPORTED (n > 16, nh > 8), DRN_ERR_ARG (null pointer, n < 1, nh < 0, M < 0, slots < 1). */
+#define DRN_METRICS_MAX_HEADS 8
+#define DRN_METRICS_MAX_LOSSES 16
+#define DRN_METRICS_COUNTERS 6
+#define DRN_METRICS_COUNT_STRIDE 8
+#define DRN_METRICS_ROWS_PER_BLOCK 64
+#define DRN_METRICS_RECORD_WORDS 72
+int drn_head_metrics(const float* logits, long ldl, const int* col0s, int nh, int K, const void* const* labels, int M, int* counts,
+                     void* stream);
+int drn_metrics_record(const void* const* losses, int n, int* counts, int nh, int M, unsigned* ring, int slots, int* state,
+                       void* stream);
+
 /* ---- inference tail -------------------------------------------------------------------------- */
 
 /* fast_rcnn_inference_single_image, fast_rcnn.py:88-141 + batched_nms, detectron2/layers/nms.py:10-29. */
