@@ -1,4 +1,4 @@
-// What the convolution forward's plan and launch (conv_fwd_plan / conv_fwd_launch, gemm_conv.hip) use of the other two conv
+// What the convolution forward's plan and launch (conv_fwd_plan / conv_fwd_launch, conv.hip) use of the other two conv
 // translation units.  The class conditions are in conv_fwd_plan; these launch the decided form.  Library-internal.
 #pragma once
 #include "drn_common.h"

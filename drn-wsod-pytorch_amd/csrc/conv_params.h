@@ -1,4 +1,4 @@
-// Parameter block of the NHWC convolution kernels (gemm_conv.hip: register-staged tiles, LDS-resident 3x3 / 64-channel
+// Parameter block of the NHWC convolution kernels (conv.hip: register-staged tiles, LDS-resident 3x3 / 64-channel
 // kernel; conv_ring.hip: the register-ring kernels; pp8.hip: the eight-wave 128x128 kernel).  Host-built, passed by value.
 #pragma once
 

@@ -5,7 +5,7 @@
 // projects/WSL/wsl/modeling/backbone/vgg.py:104-122; detectron2/layers/wrappers.py:94-99, batch_norm.py:45-65).
 //
 // Why another kernel family.  At 800x1216 the res3 / res4 / res5 layers are GEMMs of 3800-15200 rows x 128-2048 columns with
-// K = 128 .. 4608: far too few 256x256 tiles for the GEMM kernels of gemm_conv.hip (15 tiles for the res4 3x3), and the
+// K = 128 .. 4608: far too few 256x256 tiles for the GEMM kernels of gemm.hip (15 tiles for the res4 3x3), and the
 // register-staged 64x64 / 128x128 conv tiles there ran at 0.5-0.9 us per 128-byte K slab (259 TFLOP/s on the res4 3x3,
 // profiles/r4_62_conv_800.txt).  Two measurements of this round say why and what to build instead:
 //   * `__syncthreads()` is `s_waitcnt vmcnt(0) lgkmcnt(0)` + `s_barrier`: the old mainloop's barrier per slab drained its whole
@@ -243,7 +243,7 @@ int launch_ring(const ConvParams& p, hipStream_t st) {
 
 }  // namespace
 
-// (hidden: called by conv_fwd_launch in gemm_conv.hip.  conv_fwd_plan there has decided that the layer is in the kernels' class -
+// (hidden: called by conv_fwd_launch in conv.hip.  conv_fwd_plan there has decided that the layer is in the kernels' class -
 // bf16, Cin % 64 == 0, 16-byte rows and pointers - and which tile runs it: 64 = 64x64, 128 = 128x128)
 __attribute__((visibility("hidden"))) int drn_conv_ring_launch(const ConvParams& p, int tile, hipStream_t st) {
   if (tile == 128) return launch_ring<128, 128, 3>(p, st);

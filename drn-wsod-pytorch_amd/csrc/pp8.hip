@@ -15,7 +15,7 @@
 //     [12 fragment reads + 4 LDS-DMA pieces + the wait that retires the next slab]  barrier  [8 MFMAs, s_setprio 1]  barrier
 // The two waves of a SIMD (wave w and w + 4 = the two rows of the wave layout) run one barrier interval apart: while one
 // multiplies, its partner reads fragments and issues the DMA of a later slab - the 256x256 kernel's schedule
-// (gemm_conv.hip pp_mainloop) at a quarter of its tile.
+// (mfma_mainloop.h pp_mainloop) at a quarter of its tile.
 // Staging: `buffer_load_dwordx4 ... lds` into a ring of NSTG stages of 32 KB (A rows [128][128 B] then B rows [128][128 B],
 // 16-byte k-slots XOR-swizzled with (row >> 1) & 7 on the SOURCE side, same involution on the fragment reads).  The im2col
 // gather is the per-lane source offset: row = output pixel, a K slab = 64 input channels of one tap; taps in the zero padding,
@@ -569,7 +569,7 @@ __attribute__((visibility("hidden"))) bool drn_pp8_wide_ok(long rows_one, int N,
   return t256 * 8 >= 5L * cus;
 }
 
-// (hidden: called by conv_fwd_launch in gemm_conv.hip.  conv_fwd_plan there has decided that the layer is in the kernel's class - bf16,
+// (hidden: called by conv_fwd_launch in conv.hip.  conv_fwd_plan there has decided that the layer is in the kernel's class - bf16,
 // Cin % 64 == 0, 16-byte rows and pointers, 32-bit byte offsets - and which form runs it: wide = the 256x128 tile)
 __attribute__((visibility("hidden"))) int drn_pp8_conv_launch(const ConvParams& c, bool wide, hipStream_t st) {
   Pp8Params p{};

@@ -7,12 +7,12 @@
 // tap per pixel) against ALL weights (64 x 49 taps, resident for the workgroup's life: the launch is persistent), rounded
 // to bf16 into LDS exactly as drn_conv2d_nhwc would store them, and pooled from there.  The conv map never leaves the chip.
 //
-// Same arithmetic as the two launches, bit for bit: the tiled conv kernels (gemm_conv.hip, mainloop + mma_step) give an
+// Same arithmetic as the two launches, bit for bit: the tiled conv kernels (conv.hip on mfma_mainloop.h: mainloop + mma_step) give an
 // output element ONE fp32 accumulator that takes v_mfma_f32_32x32x16_bf16 steps over k = (kh, kw, ci) ascending, 16 k-values
 // = two taps per step (lanes 0-31 the even tap, lanes 32-63 the odd one); this kernel issues the same steps in the same
 // order (the all-zero padding steps of the 448-value rows add +0 and are skipped), the same `acc * scale + bias`, ReLU and
 // bf16 rounding, and the pool takes its maxima in drn_maxpool3x3s2_nhwc's order (rows, then columns, padding skipped).
-// Built WITHOUT -ffp-contract=off, like gemm_conv.hip: the affine contracts to the same fma there and here.
+// Built WITHOUT -ffp-contract=off, like conv.hip: the affine contracts to the same fma there and here.
 #include "drn_common.h"
 #include "../../include/drn_wsod.h"
 
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void stem7x7_pool_kernel(StemParams p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[i]),
                                                               __builtin_bit_cast(bf16x8_t, fb[j]), acc[i][j], 0, 0, 0);
     }
-    // affine + ReLU + bf16 rounding (conv_epilogue of gemm_conv.hip), into the conv tile [pixel][64 channels]
+    // affine + ReLU + bf16 rounding (conv_epilogue of conv.hip), into the conv tile [pixel][64 channels]
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int nl = j * 32 + l31;

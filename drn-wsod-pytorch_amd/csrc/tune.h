@@ -1,6 +1,6 @@
 // The tuning state of the library: every knob of drn_tune (include/drn_wsod.h documents them, by id) and the tile pin of
-// drn_gemm_set_tile, each with its default.  ONE instance, g_tune, defined in gemm_conv.hip next to drn_tune's table of
-// {id, field, accept rule}; the other translation units only read it.  Defaults are the measured best.
+// drn_gemm_set_tile, each with its default.  ONE instance, g_tune, defined in tune.hip - the knobs' one home - next to
+// drn_tune's table of {id, field, accept rule}; the other translation units only read it.  Defaults are the measured best.
 #pragma once
 
 struct DrnTune {

@@ -333,7 +333,7 @@ int drn_gemm_set_tile(int tile);
 
 /* tuning knobs for A/B measurements and tests (defaults = the measured best); returns the previous value, -1 for an
  * unknown knob.  A value a knob does not take is ignored (the setting stays, and is what drn_tune returns).  The knobs, by id
- * (the library keeps them in one table: csrc/tune.h holds the state and the defaults, drn_tune in csrc/gemm_conv.hip the rule
+ * (the library keeps them in one table: csrc/tune.h holds the state and the defaults, drn_tune in csrc/tune.hip the rule
  * of every knob): */
 #define DRN_TUNE_GEMM_PERSISTENT 1 /* 0/1 - 256x256 GEMM launches with more (tile, K-split) work items than CUs run as ONE resident workgroup per CU that loops over its share (default 1; same arithmetic, bit-identical results) */
 #define DRN_TUNE_SGD_GRID 2 /* workgroups (x) of the optimizer kernel (8..65535, default 512) */
@@ -354,7 +354,7 @@ int drn_gemm_set_tile(int tile);
 #define DRN_TUNE_ROI_LANE 19 /* 0/1 (default 1): the bf16 training operand A from the lane-per-bin ROIPool kernel (a wave per ROI, lane = bin: every channel leaves as one 98-byte run per store instruction); 0 = the 64-ROI kernel writes A; 2 = the lane kernel but never its walking form; 3 (tests) = 1 with one sub-group of 64 ROIs per block of the walking form instead of two - drn_tune then reports 1, and any other value brings the two sub-groups back */
 #define DRN_TUNE_SGDP_EPILOGUE 20 /* 0/1 (default 1): the tile epilogue of drn_gemm_tn_sgd moves the bf16 gradient tile LDS -> global four 16-byte pieces per trip instead of one (A/B knob; bit-identical) */
 #define DRN_TUNE_ROI_LANE_REPS 22 /* lane-per-bin ROIPool on maps that leave one block per CU: groups of 64 ROIs a block walks with one staged map slice (0 = default: 4, halved while fewer than two rounds of blocks would remain; 1 = a block per group) */
-#define DRN_TUNE_CONV_RING 23 /* register-ring conv kernels (conv_ring.hip; bf16, Cin % 64 == 0, layers beyond the latency-bound small maps): 0 = off (the tiles of gemm_conv.hip), 1 = default (64x64 tile, class by measurement), 64 / 128 = pin the 64x64 / 128x128 tile (any other value is ignored: drn_tune returns the unchanged setting); every tile gives the same bits as the 64x64 / 128x128 tiled kernel */
+#define DRN_TUNE_CONV_RING 23 /* register-ring conv kernels (conv_ring.hip; bf16, Cin % 64 == 0, layers beyond the latency-bound small maps): 0 = off (the tiles of conv.hip), 1 = default (64x64 tile, class by measurement), 64 / 128 = pin the 64x64 / 128x128 tile (any other value is ignored: drn_tune returns the unchanged setting); every tile gives the same bits as the 64x64 / 128x128 tiled kernel */
 #define DRN_TUNE_CONV_PP 24 /* 1x1 / stride-1 bf16 convs of large maps on the 256x256 ping-pong GEMM mainloop with the conv epilogue (conv1x1_pp_kernel): 0 = off, 1 = default (Cout >= 256 and >= 192 tiles of 256x256 per image, or >= 100 tiles with K >= 1024), n > 1 = at least n tiles, any Cout; same bits as the tiled kernels */
 #define DRN_TUNE_PP8 25 /* eight-wave ping-pong kernel (pp8.hip: 128x128 or 256x128 tile, two waves per SIMD half a phase apart; bf16 convs with Cin % 64 == 0 and drn_linear_act_fwd): 0 = off, 1 = default class (measured per layer shape, see conv_fwd_plan), 2 = every layer in the kernel's class; same bits as the tiled kernels */
 #define DRN_TUNE_PP8_STAGES 26 /* 3 / 4 / 5 (default 5): 32-KB LDS stages of the 128x128 form's ring = 1 / 2 / 3 K slabs in flight (A/B knob; bit-identical) */

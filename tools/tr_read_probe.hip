@@ -1,6 +1,6 @@
 // What ds_read_b64_tr_b16 returns on this GPU: every lane reads 8 bytes at lds + lane * 8 of an LDS image holding
 // element index = position; prints, per lane, the four source positions it received.  (The fragment-major LDS image of
-// the TN GEMM operand - gemm_conv.hip, pp_offsets<true> - is built on: lane l, element j <- position
+// the TN GEMM operand - mfma_mainloop.h, pp_offsets<true> - is built on: lane l, element j <- position
 // (l & 15) + 16 * j + 64 * (l >> 4).)   build: hipcc --offload-arch=gfx950 tools/tr_read_probe.hip -o tools/build/tr_read_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
