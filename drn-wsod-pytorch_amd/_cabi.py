@@ -73,6 +73,9 @@ _SIGS = {
     "drn_loss_guard": "piiipp",
     "drn_head_metrics": "plpiipipp",
     "drn_metrics_record": "pipiipipp",
+    "drn_label_proposals": "ppiii" + "pppi" + "ppi" + "i" + "ppp" + "p",
+    "drn_mil_metrics": "pliipipp",
+    "drn_metrics_record_annot": "pipiiipipp",
     "drn_sgd_step_guard": "pppilpipifif" + "ifp" + "pp",
     "drn_sgd_step_block_guard": "pppilpip" + "iiiil" + "fif" + "ifp" + "pp",
     "drn_gemm_tn_sgd_guard": "ppp" + "iiii" + "lll" + "ppplp" + "fif" + "pp",

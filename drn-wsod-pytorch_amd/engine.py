@@ -1151,12 +1151,13 @@ class Trainer:
     """projects/WSL/tools/train_net.py:41-117 (run_step) over detectron2/engine/train_loop.py:170-289."""
 
     def __init__(self, cfg, model, data_loader_iter, optimizer=None, scheduler=None, parallel=None, start_iter=0,
-                 metrics_period=0, metrics_slots=256):
+                 metrics_period=0, metrics_slots=256, metrics_annotated=False, metrics_max_gt=64):
         """metrics_period N > 0: every step's losses and the OICR branches' label statistics are recorded on the device
         (ROIHeads.enable_metrics, metrics.MetricsRing); every N iterations the ring is drained - a stream-ordered copy, no sync -
         and the PREVIOUS drain, long complete by then, is decoded into self.storage at the records' own iterations, with `lr`
         from the host when a scheduler is present.  flush_metrics() collects what is still under way.  0 (default): off, every
-        launch as before.  More than one rank: each rank logs its own records (no cross-rank average)."""
+        launch as before.  More than one rank: each rank logs its own records (no cross-rank average).
+        metrics_annotated: also the six un-suffixed scalars against the annotated boxes (enable_metrics(annotated=True))."""
         self.cfg, self.model = cfg, model
         self._it = data_loader_iter
         self.optimizer = optimizer or build_optimizer(cfg, model)
@@ -1182,7 +1183,10 @@ class Trainer:
             if self.metrics_period > metrics_slots:
                 raise DrnError("metrics_period %d exceeds the ring's %d slots: records would be lost between drains"
                                % (self.metrics_period, metrics_slots))
-            self.metrics = model.roi_heads.enable_metrics(metrics_slots)
+            if metrics_annotated:
+                self.metrics = model.roi_heads.enable_metrics(metrics_slots, annotated=True, max_gt=metrics_max_gt)
+            else:
+                self.metrics = model.roi_heads.enable_metrics(metrics_slots)
             self.metrics.iter0 = self.iter
 
     def _feed_metrics(self, wait):

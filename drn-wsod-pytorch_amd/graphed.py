@@ -77,17 +77,47 @@ class _StaticInputs:
         self.rois = self._new_rois()
         self.obj = torch.zeros((M,), dtype=torch.float32, device=dev)
         self.props = torch.zeros((M, 4), dtype=torch.float32, device=dev)
-        # image-level labels live in ONE device block (one H2D copy per step): [onehot f32 | classes i32 | count i32]
-        self._gt_block = torch.zeros((2 * n_img * K + n_img,), dtype=torch.int32, device=dev)
-        nk = n_img * K
-        self.gt = dict(onehot=self._gt_block[:nk].view(torch.float32).view(n_img, K),
-                       classes=self._gt_block[nk: 2 * nk].view(n_img, K), count=self._gt_block[2 * nk:],
-                       props=self.props, max_rows=max(self.nper))
+        self._layout_labels()
         self.img_off = torch.tensor(self._off, dtype=torch.int32, device=dev)
         self.losses = None
         self.engine.pool_sets_pinned = None  # a new step captures anew: the previous owner's pin (if any) is void
         self.engine.pool_sets_pin_owner = None
         self.engine.captured_by = None  # weakref to the step whose captured graphs hold the engine's launch sequence
+
+    def _annot_max_gt(self):
+        """max_gt of the metrics ring's annotated-box block, 0 without one"""
+        m = getattr(self.engine, "metrics", None)
+        return m.max_gt if m is not None and m.annotated else 0
+
+    def _layout_labels(self):
+        """image-level labels live in ONE device block (one H2D copy per step): [onehot f32 | classes i32 | count i32], and - only
+        with the metrics ring's annotated-box block (ROIHeads.enable_metrics(annotated=True)) - behind them the annotated boxes
+        [boxes f32 | classes i32 | count i32] (roi_heads.pack_annotated).  Settled before the step is primed."""
+        from .modeling.roi_heads import annotated_views, annotated_words
+
+        n_img, K = self.n_img, self.K
+        self._ann_gt = self._annot_max_gt()
+        nk = n_img * K
+        self._gt_words = 2 * nk + n_img
+        extra = annotated_words(n_img, self._ann_gt) if self._ann_gt else 0
+        self._gt_block = torch.zeros((self._gt_words + extra,), dtype=torch.int32, device=self.model.device)
+        self.gt = dict(onehot=self._gt_block[:nk].view(torch.float32).view(n_img, K),
+                       classes=self._gt_block[nk: 2 * nk].view(n_img, K), count=self._gt_block[2 * nk: self._gt_words],
+                       props=self.props, max_rows=max(self.nper))
+        if self._ann_gt:
+            self.gt.update(annotated_views(self._gt_block[self._gt_words:], n_img, self._ann_gt))
+        if hasattr(self, "_gt_nb"):
+            self._gt_nb = [torch.zeros_like(self._gt_block) for _ in self._gt_nb]
+        if hasattr(self, "_ring"):
+            del self._ring
+
+    def _check_label_layout(self):
+        """the annotated-box option may be switched until the step is primed (enable_metrics() is refused afterwards): the block is
+        laid out anew while nothing was captured; a captured step keeps the layout its graphs read"""
+        if self._annot_max_gt() != self._ann_gt:
+            own = getattr(self.engine, "captured_by", None)
+            if own is None or own() is not self:
+                self._layout_labels()
 
     @property
     def metrics(self):
@@ -115,6 +145,7 @@ class _StaticInputs:
         """Image-level labels of the CURRENT batch.  They are built on the host and go through a ring of PINNED
         staging buffers so the H2D copies are truly asynchronous - a pageable source would block the host until the
         previous replay has drained and leave the GPU idle between replays."""
+        self._check_label_layout()
         ints = [torch.unique(x["instances"].gt_classes.cpu(), sorted=True) for x in batch]
         nk = self.n_img * self.K
         if not hasattr(self, "_ring"):
@@ -132,6 +163,10 @@ class _StaticInputs:
             oh[i, g] = 1
             cl[i, : len(g)] = g.to(torch.int32)
             buf[2 * nk + i] = len(g)
+        if self._ann_gt:  # the annotated boxes ride in the same pinned buffer and the same copy
+            from .modeling.roi_heads import pack_annotated
+
+            buf[self._gt_words:].copy_(pack_annotated([x["instances"] for x in batch], self._ann_gt))
         (self._gt_block if dst is None else dst).copy_(buf, non_blocking=True)
         slot["ev"] = torch.cuda.Event()
         slot["ev"].record()
@@ -548,6 +583,8 @@ class GraphedTrainStep(_StaticInputs):
         the ahead_arity(G, A) batches after that, of which only the images are read: lookahead=L, batches t+2 .. t+L (the backbone
         of the last one runs now); trunk_pairs=G, batches t+2 .. t+2G-1 (when t % G == 0 the chain of the last G starts now)."""
         self._replayed = self._primed
+        if not self._primed:
+            self._check_label_layout()  # (in front of the first staging: the staging sets follow the block)
         if self._primed:
             # the captured (or eagerly issued) SGD launches read lr / weight decay from device tables: follow the schedule
             self.opt.refresh_tables()

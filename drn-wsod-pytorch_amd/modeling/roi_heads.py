@@ -995,7 +995,7 @@ class _HeadEngine:
                                argmax=pooled.get("argmax"))
         self._last_state = state
         self._guard_check(state["loss_list"])
-        self._metrics_record(loss_names, state, n_img, [] if pcl else [col["r%d" % k] for k in range(h.refine_K)])
+        self._metrics_record(loss_names, state, n_img, [] if pcl else [col["r%d" % k] for k in range(h.refine_K)], gt, img_off)
         outs = _TrainFn.apply(self.anchor, self, state)
         return dict(zip(loss_names, outs)), state
 
@@ -1006,15 +1006,26 @@ class _HeadEngine:
         if g is not None:
             g.check(loss_list)
 
-    def _metrics_record(self, loss_names, state, n_img, col0s):
+    def _metrics_record(self, loss_names, state, n_img, col0s, gt=None, img_off=None):
         """per-step metrics (ROIHeads.enable_metrics; drn_head_metrics + drn_metrics_record) right behind the guard's check, on
         the stream that computed the losses: the label statistics of the OICR branches in `col0s` against the labels their
         losses used, then the step's record.  WSDDN / CSC / PCL heads pass no branch (the reference logs no label accuracy for
-        them: PCLOutputs.losses never calls _log_accuracy).  Off = the attribute is None and no launch changes."""
+        them: PCLOutputs.losses never calls _log_accuracy).  Off = the attribute is None and no launch changes.
+        A ring with the annotated-box block (enable_metrics(annotated=True)) gets, for every head class alike, the proposals, the
+        annotated boxes of the step's label upload and the MIL scores: two more launches in front of the record."""
         m = getattr(self, "metrics", None)
         if m is not None:
+            annot = None
+            if m.annotated:
+                if gt is None or "ann_boxes" not in gt:
+                    raise DrnError("metrics with the annotated-box block: this step's labels carry no annotated boxes "
+                                   "(enable_metrics(annotated=True) comes before the graphed step is primed)")
+                pm = self.h.proposal_matcher
+                annot = dict(props=gt["props"], img_off=img_off, boxes=gt["ann_boxes"], classes=gt["ann_classes"],
+                             count=gt["ann_count"], thresholds=pm.thresholds[1:-1], labels=pm.labels,
+                             scores=state["aux"]["scores"], max_rows=gt.get("max_rows"))
             m.record(loss_names, state["loss_list"], n_img, state["M"], state["w"]["logits"], col0s, self.h.num_classes,
-                     [t["labels"] for t in state["aux"]["targets"]] if col0s else ())
+                     [t["labels"] for t in state["aux"]["targets"]] if col0s else (), annot=annot)
 
     # ---- CSCROIHeads -----------------------------------------------------------------------------------
     def _forward_csc(self, w, col, M, dtype, rois, objectness, feat_nhwc, pooled, gt, img_off, n_img, masks, drop_p,
@@ -1040,7 +1051,7 @@ class _HeadEngine:
             state["fg"] = dict(fg, hook=fg_hook)
         self._last_state = state
         self._guard_check(state["loss_list"])
-        self._metrics_record(["loss_cls_pos", "loss_cls_neg"], state, 1, [])
+        self._metrics_record(["loss_cls_pos", "loss_cls_neg"], state, 1, [], gt, img_off)
         outs = _TrainFn.apply(self.anchor, self, state)
         return dict(zip(["loss_cls_pos", "loss_cls_neg"], outs)), state
 
@@ -1370,6 +1381,38 @@ class ROIHeads(nn.Module):
         }
 
 
+def pack_annotated(targets, max_gt):
+    """the annotated boxes of a step, packed on the host for the label upload: int32 words [boxes fp32 n_img * max_gt * 4 |
+    classes n_img * max_gt | counts n_img] (views: annotated_views).  Feeds the un-suffixed logging scalars of the metrics ring
+    and no loss (roi_heads.py:256-353).  More than max_gt boxes in an image: DrnError - the length is known here, without a sync."""
+    n_img = len(targets)
+    words = torch.zeros((annotated_words(n_img, max_gt),), dtype=torch.int32)
+    v = annotated_views(words, n_img, max_gt)
+    for i, t in enumerate(targets):
+        b = t.gt_boxes.tensor.detach().cpu().to(torch.float32).reshape(-1, 4)
+        c = t.gt_classes.detach().cpu().reshape(-1)
+        if b.shape[0] != c.shape[0]:
+            raise DrnError("image %d: %d annotated boxes, %d classes" % (i, b.shape[0], c.shape[0]))
+        if b.shape[0] > max_gt:
+            raise DrnError("image %d has %d annotated boxes, enable_metrics(max_gt=%d) holds at most %d: enable with a larger "
+                           "max_gt" % (i, b.shape[0], max_gt, max_gt))
+        v["ann_boxes"][i, : b.shape[0]] = b
+        v["ann_classes"][i, : c.shape[0]] = c.to(torch.int32)
+        v["ann_count"][i] = b.shape[0]
+    return words
+
+
+def annotated_words(n_img, max_gt):
+    return n_img * max_gt * 5 + n_img
+
+
+def annotated_views(words, n_img, max_gt):
+    """the three tensors of pack_annotated's word block, as views (host or device)"""
+    nb = n_img * max_gt * 4
+    return dict(ann_boxes=words[:nb].view(torch.float32).view(n_img, max_gt, 4),
+                ann_classes=words[nb: nb + n_img * max_gt].view(n_img, max_gt), ann_count=words[nb + n_img * max_gt:])
+
+
 def get_image_level_gt(targets, num_classes):
     """roi_heads.py:137-153.  `unique(sorted=True)` of a handful of ints: done on the host copy of the labels
     (they arrive from the data loader on the host), so no device sync is introduced."""
@@ -1473,11 +1516,25 @@ class OICRROIHeads(ROIHeads):
             z = self._zero_oh = torch.zeros((n_img, K), dtype=torch.float32, device=dev)
         return z
 
-    def enable_metrics(self, slots=256):
+    def enable_metrics(self, slots=256, annotated=False, max_gt=64):
         """Record every training step's losses and, for OICR branches, label statistics into a device-side ring of `slots`
         records (metrics.MetricsRing, returned): two small launches behind the loss tail, no host sync.  A graphed step freezes
-        its launch sequence when it is primed, so this has to come first: enable_metrics() -> build / prime the graphed step."""
+        its launch sequence when it is primed, so this has to come first: enable_metrics() -> build / prime the graphed step.
+        annotated=True (any head class): two more launches label the proposals against the ANNOTATED boxes of targets[i].gt_boxes /
+        gt_classes (at most max_gt per image) and record the reference's six un-suffixed scalars, roi_head/num_{fg,bg,ig}_samples
+        and fast_rcnn/{cls_accuracy,fg_cls_accuracy,false_negative}; the boxes travel in the step's label upload."""
+        from .. import ops
         from ..metrics import MetricsRing
+
+        if annotated:
+            if self.proposal_append_gt:
+                raise DrnError("enable_metrics(annotated=True) with MODEL.ROI_HEADS.PROPOSAL_APPEND_GT = True: appending the "
+                               "annotated boxes to the proposals is not built (every shipped recipe sets it False)")
+            if not 1 <= int(max_gt) <= ops.LABEL_MAX_GT:
+                raise DrnError("enable_metrics(max_gt=%d): 1 .. %d annotated boxes per image are built" % (max_gt, ops.LABEL_MAX_GT))
+            if getattr(self, "refine_mode", "oicr") != "pcl" and self.refine_K > ops.METRICS_ANNOT_ROW:
+                raise DrnError("enable_metrics(annotated=True) with %d OICR branches: the block takes the record's last head slot, "
+                               "at most %d branches leave room" % (self.refine_K, ops.METRICS_ANNOT_ROW))
 
         eng = self._engine
         owner = getattr(eng, "captured_by", None)
@@ -1485,7 +1542,7 @@ class OICRROIHeads(ROIHeads):
             raise DrnError("enable_metrics() after a graphed step was primed: its captured launches would never record.  Order: "
                            "enable_metrics(), then create and prime the GraphedTrainStep / GraphedFullStep")
         eng.ensure(next(self.parameters()).device)
-        eng.metrics = MetricsRing(slots, eng.arena_w.device)
+        eng.metrics = MetricsRing(slots, eng.arena_w.device, annotated, max_gt)
         return eng.metrics
 
     def disable_metrics(self):
@@ -1541,6 +1598,10 @@ class OICRROIHeads(ROIHeads):
             gt = dict(onehot=oh.to(dev, non_blocking=True), classes=gcl.to(dev, non_blocking=True),
                       count=torch.tensor([len(g) for g in ints], dtype=torch.int32).to(dev, non_blocking=True),
                       props=self._take_props(rois), max_rows=max(nper))
+            ring = getattr(self._engine, "metrics", None)
+            if ring is not None and ring.annotated:  # the annotated boxes, packed on the host: one more small upload
+                words = pack_annotated(targets, ring.max_gt).to(dev, non_blocking=True)
+                gt.update(annotated_views(words, n_img, ring.max_gt))
             losses, state = self._engine.forward(nhwc, rois, obj, True, off.to(dev, non_blocking=True), n_img, gt,
                                                  pooled=pooled)
             self.pred_class_img_logits = state["aux"]["img_scores"]

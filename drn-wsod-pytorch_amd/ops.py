@@ -952,21 +952,80 @@ def head_metrics(logits, col0s, K, labels, M, counts):
            ctypes.cast(ptrs, ctypes.c_void_p), int(M), C.ptr(counts), C.stream())
 
 
-def metrics_record(losses, counts, nh, M, ring, state):
+def metrics_record(losses, counts, nh, M, ring, state, annot=False):
     """drn_metrics_record: one wave writes the step's record - index, n, nh, M, the loss bit patterns, counts[:nh, 0:6], index again -
-    into slot state[0] % slots of `ring`, advances state[0] and stores zeros back into `counts`.  No synchronisation; capturable."""
+    into slot state[0] % slots of `ring`, advances state[0] and stores zeros back into `counts`.  No synchronisation; capturable.
+    annot (drn_metrics_record_annot): counts[METRICS_ANNOT_ROW] - what label_proposals() and mil_metrics() added - is published too,
+    in the last head slot, word 68 and the flag word 70; nh may then be at most 7."""
     n = len(losses)
-    if not 1 <= n <= METRICS_MAX_LOSSES or nh > METRICS_MAX_HEADS:
+    if not 1 <= n <= METRICS_MAX_LOSSES or nh > (METRICS_ANNOT_ROW if annot else METRICS_MAX_HEADS):
         raise C.DrnError("metrics_record(): %d loss scalars, %d branches (1 .. %d and 0 .. %d are built)"
-                         % (n, nh, METRICS_MAX_LOSSES, METRICS_MAX_HEADS))
+                         % (n, nh, METRICS_MAX_LOSSES, METRICS_ANNOT_ROW if annot else METRICS_MAX_HEADS))
     for t in losses:
         assert t.dtype == torch.float32 and t.numel() == 1 and t.is_cuda
     assert ring.dtype == torch.int32 and ring.dim() == 2 and ring.shape[1] == METRICS_RECORD_WORDS and ring.is_contiguous()
     assert state.dtype == torch.int32 and state.numel() == 4 and state.is_contiguous()
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == METRICS_MAX_HEADS * METRICS_COUNT_STRIDE
     ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in losses])
+    if annot:
+        C.call("drn_metrics_record_annot", ctypes.cast(ptrs, ctypes.c_void_p), n, C.ptr(counts), int(nh), int(M), 1, C.ptr(ring),
+               ring.shape[0], C.ptr(state), C.stream())
+        return
     C.call("drn_metrics_record", ctypes.cast(ptrs, ctypes.c_void_p), n, C.ptr(counts), int(nh), int(M), C.ptr(ring),
            ring.shape[0], C.ptr(state), C.stream())
+
+
+# include/drn_wsod.h: the annotated-box block
+LABEL_MAX_GT, METRICS_ANNOT_ROW, METRICS_ANNOT_WORD_FG, METRICS_ANNOT_WORD_FLAG, METRICS_ANNOT_FLAG = 256, 7, 68, 70, 1
+
+
+def label_proposals(props, img_off, n_img, gt_boxes, gt_classes, gt_count, K, thresholds=(0.5,), labels=(0, 1), counts=None,
+                    max_rows=None, out=None):
+    """drn_label_proposals: every proposal row against the ANNOTATED boxes of its image (pairwise_iou + Matcher without low-quality
+    matches + the matched box's class; roi_heads.py:256-353).  props fp32 [M, 4], img_off int32 [n_img + 1], gt_boxes fp32
+    [n_img, max_gt, 4], gt_classes int32 [n_img, max_gt], gt_count int32 [n_img].  -> dict(labels int32 [M]: class, K background,
+    -1 ignore; matched int32 [M]: the best box, lowest index on equal IoU; counts: n_ig, n_bg, n_fg ADDED into counts[0:3]).
+    counts: an int32 block of >= 3 words (a zeroed one of METRICS_COUNT_STRIDE is made when None); out: (labels, matched) to write
+    into.  No synchronisation; capturable."""
+    M, dev = props.shape[0], props.device
+    max_gt = gt_classes.shape[1]
+    nthr = len(thresholds)
+    if max_gt > LABEL_MAX_GT or not 1 <= nthr <= 3 or len(labels) != nthr + 1:
+        raise C.DrnError("label_proposals(): max_gt %d, %d thresholds, %d labels (at most %d boxes per image, 1 .. 3 thresholds "
+                         "and one label more are built)" % (max_gt, nthr, len(labels), LABEL_MAX_GT))
+    assert props.dtype == torch.float32 and props.dim() == 2 and props.shape[1] == 4 and props.is_contiguous()
+    assert img_off.dtype == torch.int32 and img_off.numel() == n_img + 1 and img_off.is_contiguous()
+    assert gt_boxes.dtype == torch.float32 and gt_boxes.shape == (n_img, max_gt, 4) and gt_boxes.is_contiguous()
+    assert gt_classes.dtype == torch.int32 and gt_classes.shape == (n_img, max_gt) and gt_classes.is_contiguous()
+    assert gt_count.dtype == torch.int32 and gt_count.numel() == n_img and gt_count.is_contiguous()
+    if counts is None:
+        counts = torch.zeros((METRICS_COUNT_STRIDE,), dtype=torch.int32, device=dev)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 3
+    lab, mat = out if out is not None else (torch.empty((M,), dtype=torch.int32, device=dev),
+                                            torch.empty((M,), dtype=torch.int32, device=dev))
+    for t in (lab, mat):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= M
+    th, lb = C.host_floats(thresholds), C.host_ints(labels)
+    C.call("drn_label_proposals", C.ptr(props), C.ptr(img_off), int(n_img), M, int(max_rows or M), C.ptr(gt_boxes),
+           C.ptr(gt_classes), C.ptr(gt_count), max_gt, ctypes.cast(th, ctypes.c_void_p), ctypes.cast(lb, ctypes.c_void_p), nthr,
+           int(K), C.ptr(lab), C.ptr(mat), C.ptr(counts), C.stream())
+    return dict(labels=lab, matched=mat, counts=counts)
+
+
+def mil_metrics(scores, labels, M, counts, ncol=None, bg_ind=None):
+    """drn_mil_metrics: WSDDNOutputs._log_accuracy (fast_rcnn.py:213-235) of the MIL scores [>= M, ncol] against label_proposals()'
+    labels, with that code's background index ncol - 1: n_acc, n_fg_acc, n_fneg and the foreground count #{0 <= g < ncol - 1} ADDED
+    into counts[3:7].  First arg-max, like head_metrics().  No synchronisation; capturable."""
+    ncol = scores.shape[1] if ncol is None else int(ncol)
+    bg_ind = ncol - 1 if bg_ind is None else int(bg_ind)
+    if ncol > 1024 or bg_ind != ncol - 1:
+        raise C.DrnError("mil_metrics(): %d columns, background index %d (at most 1024 columns, background = the last, are built)"
+                         % (ncol, bg_ind))
+    assert scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1 and scores.shape[0] >= M
+    assert scores.shape[1] >= ncol >= 1
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() >= M
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 7
+    C.call("drn_mil_metrics", C.ptr(scores), _2d(scores), ncol, bg_ind, C.ptr(labels), int(M), C.ptr(counts), C.stream())
 
 
 CLIP_NONE, CLIP_VALUE, CLIP_NORM = 0, 1, 2  # clip_mode of drn_sgd_step_clip / drn_sgd_step_block_clip

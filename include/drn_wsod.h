@@ -631,7 +631,44 @@ int drn_gemm_tn_acc_sgd_guard(const void* A, const void* Bt, const float* grad_a
  * then state[0] = i + 1, and all 64 words of `counts` are stored back as ZERO: the next step's drn_head_metrics finds its scratch
  * cleared without a memset node.  The slot comes from device memory, so a replayed graph advances through the ring; the kernel
  * boundary between the two launches is their only hand-off (no flag, no spinning).  Ordinary vector stores only.
- * Errors: DRN_ERR_UNSUPPORTED (n > 16, nh > 8), DRN_ERR_ARG (null pointer, n < 1, nh < 0, M < 0, slots < 1). */
+ * Errors: DRN_ERR_UNSUPPORTED (n > 16, nh > 8), DRN_ERR_ARG (null pointer, n < 1, nh < 0, M < 0, slots < 1).
+ *
+ * The annotated-box block (opt-in; ROIHeads.enable_metrics(annotated=True)).  Every head class of the reference first labels its
+ * proposals against the ANNOTATED boxes (label_and_sample_proposals, roi_heads.py:256-353, called from roi_heads_oicr.py:266,
+ * roi_heads_wsddn.py:218, roi_heads_pcl.py:235, roi_heads_csc.py:252) and logs roi_head/num_{fg,bg,ig}_samples; its MIL predictor
+ * then logs fast_rcnn/{cls_accuracy,fg_cls_accuracy,false_negative} of the MIL scores against those labels
+ * (WSDDNOutputs._log_accuracy, fast_rcnn.py:213-235).  The boxes feed these six scalars and no loss.
+ *
+ * drn_label_proposals: proposals = fp32 [M, 4] (16-byte aligned), img_off = int32[n_img + 1] row offsets, gt_boxes = fp32
+ * [n_img, max_gt, 4], gt_classes = int32 [n_img, max_gt], gt_count = int32[n_img] (all device memory; a count is clamped to
+ * 0 .. max_gt), thresholds / match_labels = HOST arrays of nthr (1 .. 3) IoU thresholds and nthr + 1 Matcher labels in {-1, 0, 1},
+ * max_rows = an upper bound of the rows of one image (sizes the grid).  For row r of image i and annotated box j of that image, in
+ * fp32, this operation order, no contraction (detectron2/structures/boxes.py:329-361):
+ *   a1 = (X2 - X1) * (Y2 - Y1) of the annotated box, a2 = (x2 - x1) * (y2 - y1) of the proposal,
+ *   inter = max(min(X2, x2) - max(X1, x1), 0) * max(min(Y2, y2) - max(Y1, y1), 0),   iou = inter > 0 ? inter / (a1 + a2 - inter) : 0
+ * which equals torch's pairwise_iou bit for bit.  v = the maximum over j, matched[r] = its j; DEFINITION: on equal IoU the LOWEST
+ * box index wins (so a row that overlaps nothing is matched to box 0).  Matcher (detectron2/modeling/matcher.py,
+ * allow_low_quality_matches = False): with t_0 = -inf, t_1 .. t_nthr = thresholds, t_nthr+1 = +inf, the Matcher label is
+ * match_labels[q] for the q with t_q <= v < t_q+1; labels[r] = K for 0, -1 for -1, the class of box matched[r] for 1.  An image with
+ * no annotated box: labels K, matched 0 (roi_heads.py:234-246).  counts = int32[>= 3], device memory: [0] += #{label == -1},
+ * [1] += #{label == K}, [2] += the rest, over all images, as exact integers (one atomicAdd(int*) per non-zero counter and workgroup;
+ * no float atomic, no host sync, capturable).  One thread per row, 256 rows of ONE image per workgroup, the image's boxes in LDS.
+ * NaN coordinates: unspecified.
+ * Shape class: n_img >= 0, M >= 0, 1 <= max_gt <= DRN_LABEL_MAX_GT, 1 <= nthr <= 3, K >= 1 (n_img, M or max_rows == 0: no launch).
+ * Errors: DRN_ERR_UNSUPPORTED (max_gt > DRN_LABEL_MAX_GT, nthr > 3), DRN_ERR_ARG (null / misaligned pointer, sizes, a label outside
+ * {-1, 0, 1}).
+ *
+ * drn_mil_metrics: drn_head_metrics' statistics of ONE fp32 matrix scores[rows >= M, lds] with an explicit column count and
+ * background index - what fast_rcnn.py:213-235 computes of the MIL scores [M, K]: bg_ind = shape[1] - 1 = ncol - 1 (the LAST CLASS
+ * column stands in for the background there; restated as it is).  p = the FIRST maximal index of scores[r, 0 .. ncol), g = labels[r]:
+ *   counts[3] += #{p == g}   [4] += #{0 <= g < bg_ind, p == g}   [5] += #{0 <= g < bg_ind, p == bg_ind}   [6] += #{0 <= g < bg_ind}
+ * ([0..2] are drn_label_proposals').  Shape class: 1 <= ncol <= 1024, bg_ind == ncol - 1, lds >= ncol, any M >= 0.
+ * Errors: DRN_ERR_UNSUPPORTED (ncol > 1024, another bg_ind), DRN_ERR_ARG.
+ *
+ * drn_metrics_record_annot: drn_metrics_record with one more argument; annot == 0 is drn_metrics_record.  annot != 0: row
+ * DRN_METRICS_ANNOT_ROW of `counts` is the annotated-box block and is published in the record's unused space,
+ *   words 62..67  counts[7][0..5] (the last head slot)     word 68  counts[7][6]     word 70  DRN_METRICS_ANNOT_FLAG
+ * so nh may be at most 7 (DRN_ERR_UNSUPPORTED otherwise).  A record without the block has zeros there, as before. */
 #define DRN_METRICS_MAX_HEADS 8
 #define DRN_METRICS_MAX_LOSSES 16
 #define DRN_METRICS_COUNTERS 6
@@ -642,6 +679,17 @@ int drn_head_metrics(const float* logits, long ldl, const int* col0s, int nh, in
                      void* stream);
 int drn_metrics_record(const void* const* losses, int n, int* counts, int nh, int M, unsigned* ring, int slots, int* state,
                        void* stream);
+#define DRN_LABEL_MAX_GT 256
+#define DRN_METRICS_ANNOT_ROW 7
+#define DRN_METRICS_ANNOT_WORD_FG 68
+#define DRN_METRICS_ANNOT_WORD_FLAG 70
+#define DRN_METRICS_ANNOT_FLAG 1u
+int drn_label_proposals(const float* proposals, const int* img_off, int n_img, int M, int max_rows, const float* gt_boxes,
+                        const int* gt_classes, const int* gt_count, int max_gt, const float* thresholds, const int* match_labels,
+                        int nthr, int K, int* labels, int* matched, int* counts, void* stream);
+int drn_mil_metrics(const float* scores, long lds, int ncol, int bg_ind, const int* labels, int M, int* counts, void* stream);
+int drn_metrics_record_annot(const void* const* losses, int n, int* counts, int nh, int M, int annot, unsigned* ring, int slots,
+                             int* state, void* stream);
 
 /* ---- inference tail -------------------------------------------------------------------------- */
 
