@@ -32,6 +32,8 @@ _SIGS = {
     "drn_tta_accumulate": "ppppllfffiip",
     "drn_pcl_adjacency": "pifpp",
     "drn_pcl_refine": "pipiipipppip" + "ppppppppppi" + "ppp",
+    "drn_pcl_adjacency_batch": "ppiiifpp",
+    "drn_pcl_refine_batch": "pipiipippp" + "piii" + "pppp" + "ppppppp" + "i" + "pppp",
     "drn_im2col_t": "pp" + "iiiiiiiiii" + "lip",
     "drn_maxpool2x2_bwd_nhwc": "pppiiiiiip",
     "drn_add": "ppplip",

@@ -25,6 +25,7 @@ constexpr int PCL_MAXR = 4096;          // proposals per image (BASELINE configs
 constexpr int PCL_W = PCL_MAXR / 32;    // words of a row mask
 constexpr int PCL_T = 1024;             // threads of the one workgroup that walks one refinement branch
 constexpr int PCL_CHUNK = 64;           // blocked prefix sum (oracle/pcl_oracle.py SCAN_CHUNK)
+constexpr int PCL_MAXIMG = 16;          // images of one batched launch (grid.y of pcl_refine_batch_kernel)
 constexpr int PCL_MAXP = 640;           // centres kept in LDS for the assignment phase (5 per labelled class)
 constexpr int PCL_NINV = 3584;          // reciprocals kept in LDS for the k-means search (larger distances divide)
 constexpr int PCL_ROWBUF_WORDS = (16384 + 32768 + 8192) / 4;  // adjacency rows of the top cluster staged in LDS
@@ -60,6 +61,32 @@ __global__ __launch_bounds__(256) void pcl_adjacency_kernel(PclAdjParams p) {
   p.adj[(long)r * p.W32 + w] = bits;
 }
 
+// image batch: blockIdx.z = image, rows [img_off[z], img_off[z+1]) of boxes / adj; bit columns are LOCAL to the image.
+// adj [M][W32] with W32 = ceil(max_rows / 32): every word of an image's rows is written (bits at and beyond R_i are 0),
+// rows that belong to no image are not.  An image whose row count is outside 1 .. max_rows writes nothing.
+struct PclAdjBatchParams { const float* boxes; uint32_t* adj; const int* img_off; int M; int max_rows; int W32; float thr; };
+
+__global__ __launch_bounds__(256) void pcl_adjacency_batch_kernel(PclAdjBatchParams p) {
+  __shared__ float cb[32][4];
+  const int off = p.img_off[blockIdx.z];
+  const int R = p.img_off[blockIdx.z + 1] - off;
+  if (R <= 0 || R > p.max_rows || off < 0 || off + R > p.M) return;  // uniform over the block
+  const int w = blockIdx.x;
+  if (threadIdx.x < 128) {
+    const int c = w * 32 + (threadIdx.x >> 2);
+    cb[threadIdx.x >> 2][threadIdx.x & 3] = c < R ? p.boxes[4 * (long)(off + c) + (threadIdx.x & 3)] : 0.f;
+  }
+  __syncthreads();
+  const int r = blockIdx.y * 256 + threadIdx.x;
+  if (r >= R) return;
+  float rb[4];
+  for (int e = 0; e < 4; ++e) rb[e] = p.boxes[4 * (long)(off + r) + e];
+  uint32_t bits = 0;
+  for (int j = 0; j < 32; ++j)
+    if (w * 32 + j < R && iou_xyxy(rb, cb[j]) > p.thr) bits |= 1u << j;
+  p.adj[(long)(off + r) * p.W32 + w] = bits;
+}
+
 // ------------------------------------------------------------------------------------------- row softmax, all branches
 struct PclSoftmaxParams { const float* logits; int ld; int cols[8]; int NB; int K1; int R; float* probs; };
 
@@ -79,13 +106,15 @@ __global__ __launch_bounds__(256) void pcl_softmax_kernel(PclSoftmaxParams p) {
 // ------------------------------------------------------------------------------------------- one branch, one workgroup
 struct PclRefineParams {
   const float* boxes;       // [R,4]
-  const uint32_t* adj;      // [R,W32]
+  const uint32_t* adj;      // [R,ld_adj] (ld_adj = W32 for one image; the batch's common word count for an image view)
   const float* wsddn;       // [R,ld_ws]: the MIL head's scores (last_score of branch 0; class c in column c)
   int ld_ws;
-  const float* probs;       // [NB][R][K1]: softmax of every branch, column 0 = background
+  const float* probs;       // [NB][RS][K1]: softmax of every branch, column 0 = background
   const float* onehot;      // [K] image-level labels
   int R, K, K1, W32, NB, PMAX;
-  int* labels; float* cls_w; int* assign;                                   // [NB][R]
+  int ld_adj;               // words between two rows of adj
+  int RS;                   // rows between two branches of probs / labels / cls_w / assign (R for one image, M for a view)
+  int* labels; float* cls_w; int* assign;                                   // [NB][RS]
   int* pc_labels; float* pc_probs; int* pc_count; float* img_w; int* pc_rows; float* pc_scores;  // [NB][PMAX]
   int* n_pc;                // [NB]
   float* losses;            // [NB]
@@ -153,8 +182,12 @@ __device__ __forceinline__ double recip(const double* inv, int d) { return d <= 
 #define PCL_TICK(k)
 #endif
 
-__global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
+// One refinement branch `b` of one image on one workgroup.  The image is rows [off, off + R) of every matrix and slice `im`
+// of the per-cluster outputs (one image: off = 0, im = 0, R = p.R).  BATCH: every dlogits entry is multiplied once more
+// by gscale = 1 / images.
+template <bool BATCH>
+__device__ __forceinline__ void pcl_refine_body(const PclRefineParams& p, const int b, const int im, const long off,
+                                                const int R, const float gscale, unsigned char* lds_raw) {
   PclShared& S = *reinterpret_cast<PclShared*>(lds_raw);
   unsigned char* big = lds_raw + ((sizeof(PclShared) + 15) & ~size_t(15));
   // k-means phase                                   | graph phase            | assignment phase
@@ -175,20 +208,28 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
                                                        // upper half of T2 + B2 + CP = 56 KB
   unsigned short* mlist = OPT;                         // members, ascending rows [4096]
 
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int R = p.R, K = p.K, K1 = p.K1, W32 = p.W32;
-  const float* last = b == 0 ? p.wsddn : p.probs + (long)(b - 1) * R * K1 + 1;  // class c of row r: last[r*ldl + c]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = p.K, K1 = p.K1, W32 = (R + 31) / 32;
+  // the image's view (one image: off = 0, im = 0): its rows of every matrix, its slice of the per-cluster outputs
+  const float* v_boxes = p.boxes + 4 * off;
+  const uint32_t* v_adj = p.adj + off * p.ld_adj;
+  const float* v_wsddn = p.wsddn + off * p.ld_ws;
+  const float* v_probs = p.probs + off * K1;
+  const float* v_onehot = p.onehot + (long)im * K;
+  float* v_dlogits = p.dlogits + off * p.ld;
+  const long pco = ((long)im * p.NB + b) * p.PMAX;
+  const float* last = b == 0 ? v_wsddn : v_probs + (long)(b - 1) * p.RS * K1 + 1;  // class c of row r: last[r*ldl + c]
   const int ldl = b == 0 ? p.ld_ws : K1;
-  const float* pnew = p.probs + (long)b * R * K1;
-  int* o_labels = p.labels + (long)b * R;
-  float* o_w = p.cls_w + (long)b * R;
-  int* o_assign = p.assign + (long)b * R;
-  int* o_pcl = p.pc_labels + (long)b * p.PMAX;
-  float* o_pcp = p.pc_probs + (long)b * p.PMAX;
-  int* o_pcc = p.pc_count + (long)b * p.PMAX;
-  float* o_iw = p.img_w + (long)b * p.PMAX;
-  int* o_rows = p.pc_rows + (long)b * p.PMAX;
-  float* o_sc = p.pc_scores + (long)b * p.PMAX;
+  const float* pnew = v_probs + (long)b * p.RS * K1;
+  int* o_labels = p.labels + (long)b * p.RS + off;
+  float* o_w = p.cls_w + (long)b * p.RS + off;
+  int* o_assign = p.assign + (long)b * p.RS + off;
+  int* o_pcl = p.pc_labels + pco;
+  float* o_pcp = p.pc_probs + pco;
+  int* o_pcc = p.pc_count + pco;
+  float* o_iw = p.img_w + pco;
+  int* o_rows = p.pc_rows + pco;
+  float* o_sc = p.pc_scores + pco;
   const float EPS9 = 1e-9f;  // pcl.py:33-37 (the upper clip 1 - 1e-9 rounds to 1.0f and never fires)
 
   if (tid < PCL_W) S.alive[tid] = tid < W32 ? (tid == W32 - 1 && (R & 31) ? (1u << (R & 31)) - 1u : 0xFFFFFFFFu) : 0u;
@@ -201,7 +242,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
   __syncthreads();
   int P = 0;  // centres so far (uniform)
   for (int c = 0; c < K; ++c) {
-    if (p.onehot[c] != 1.f) continue;
+    if (v_onehot[c] != 1.f) continue;
     // ---- pool = rows still alive; their clipped scores, compacted (order is irrelevant: they get sorted)
     int n = 0;
     for (int w = 0; w < W32; ++w) n += __popc(S.alive[w]);
@@ -419,7 +460,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
     // one (member, word) pair per thread and step: independent coalesced loads; integer LDS adds are order-free
     for (int idx = tid; idx < nmem * W32; idx += PCL_T) {
       const int x = idx / W32, w = idx - x * W32;
-      const uint32_t v = p.adj[(long)mlist[x] * W32 + w];
+      const uint32_t v = v_adj[(long)mlist[x] * p.ld_adj + w];
       if (staged) rowbuf[idx] = v;
       const int d = __popc(v & S.member[w]);
       if (d) atomicAdd(&deg[x], d);
@@ -442,7 +483,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
         const int tslot = (int)((key - 1u) & 4095u);
         const int t = mlist[tslot];
         const bool tlive = bit(S.live, t);
-        const uint32_t* trow = staged ? rowbuf + tslot * W32 : p.adj + (long)t * W32;
+        const uint32_t* trow = staged ? rowbuf + tslot * W32 : v_adj + (long)t * p.ld_adj;
         int cnt = 0;
         uint32_t iw[PCL_W / 64], lv[PCL_W / 64];
         uint32_t sk = 0;
@@ -496,7 +537,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
 #pragma unroll
               for (int u = 0; u < 8; ++u) {
                 const int j = S.nz[min(g0 + u, nlist - 1)];
-                const uint32_t* jrow = staged ? rowbuf + (int)rslot[j] * W32 : p.adj + (long)j * W32;
+                const uint32_t* jrow = staged ? rowbuf + (int)rslot[j] * W32 : v_adj + (long)j * p.ld_adj;
 #pragma unroll
                 for (int g = 0; g < PCL_W / 64; ++g) {
                   const int w = g * 64 + lane;
@@ -572,7 +613,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
   float* rowp = reinterpret_cast<float*>(B2);       // [4096] clipped probability of the assigned centre's class
   for (int i = tid; i < P; i += PCL_T) {
     const int row = o_rows[i];
-    for (int e = 0; e < 4; ++e) cb[4 * i + e] = p.boxes[4 * (long)row + e];
+    for (int e = 0; e < 4; ++e) cb[4 * i + e] = v_boxes[4 * (long)row + e];
     cs[i] = o_sc[i];
     cl[i] = o_pcl[i];
   }
@@ -583,7 +624,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
     const int r = q * PCL_T + tid;
     if (r >= R) continue;
     float rb[4];
-    for (int e = 0; e < 4; ++e) rb[e] = p.boxes[4 * (long)r + e];
+    for (int e = 0; e < 4; ++e) rb[e] = v_boxes[4 * (long)r + e];
     float best = -1.f;
     int a = 0;
     for (int i = 0; i < P; ++i) {
@@ -617,7 +658,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
       cb[4 * i + 1] = (float)n;            // reuse: pc_count
     }
   }
-  if (tid == 0) p.n_pc[b] = P;
+  if (tid == 0) p.n_pc[im * p.NB + b] = P;
   __syncthreads();
   PCL_TICK(6)
   // ---- loss (pcl_loss_cpu.cpp:8-58) and d loss / d logits through the softmax (pcl_loss_cpu.cpp:60-115)
@@ -635,7 +676,7 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
       lsum -= (double)roww[r] * (double)logf(fmaxf(pl, 1e-6f));
       g = -roww[r] / fmaxf(pl, 1e-5f);
     } else {
-      g = p.onehot[lab - 1] != 0.f ? -cs[as] / fmaxf(cb[4 * as + 1] * cb[4 * as], 1e-5f) : 0.f;
+      g = v_onehot[lab - 1] != 0.f ? -cs[as] / fmaxf(cb[4 * as + 1] * cb[4 * as], 1e-5f) : 0.f;
     }
     g = g * invR;
     rowg[r] = g;
@@ -657,20 +698,59 @@ __global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
       const int idx = base + u * PCL_T;
       if (idx < total) {
         const int r = idx / K1, j = idx - r * K1;
-        p.dlogits[(long)r * p.ld + col0 + j] = v[u] * ((j == (int)rowa[r] ? rowg[r] : 0.f) - rowgp[r]);
+        const float dv = v[u] * ((j == (int)rowa[r] ? rowg[r] : 0.f) - rowgp[r]);
+        v_dlogits[(long)r * p.ld + col0 + j] = BATCH ? dv * gscale : dv;
       }
     }
   }
   for (int i = tid; i < P; i += PCL_T)
-    if (p.onehot[cl[i] - 1] != 0.f) lsum -= (double)cs[i] * (double)logf(fmaxf(cb[4 * i], 1e-6f));
+    if (v_onehot[cl[i] - 1] != 0.f) lsum -= (double)cs[i] * (double)logf(fmaxf(cb[4 * i], 1e-6f));
   const double tot = block_sum_f64(lsum, S);
-  if (tid == 0) p.losses[b] = (float)(tot / (double)R);
+  if (tid == 0) p.losses[im * p.NB + b] = (float)(tot / (double)R);
   PCL_TICK(7)
 #ifdef PCL_PROFILE
   if (tid == 0 && b == p.NB - 1)
     for (int k = 0; k < 10; ++k) o_sc[p.PMAX - 10 + k] = (float)prof_[k];
 #endif
 }
+
+__global__ __launch_bounds__(PCL_T) void pcl_refine_kernel(PclRefineParams p) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  pcl_refine_body<false>(p, blockIdx.x, 0, 0, p.R, 1.f, lds_raw);
+}
+
+// image batch: workgroup (branch, image).  `p` describes the whole batch: boxes / wsddn / probs / dlogits / labels / cls_w /
+// assign by global row (RS = M), adj [M][ld_adj], onehot [n][K], per-cluster outputs [n][NB][PMAX], n_pc / losses [n][NB].
+// The row range, and with it R, W32 and 1 / R, comes from img_off on the device.
+struct PclBatchParams { PclRefineParams p; const int* img_off; int n_img; int M; int max_rows; };
+
+__global__ __launch_bounds__(PCL_T) void pcl_refine_batch_kernel(PclBatchParams q) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const int b = blockIdx.x, im = blockIdx.y;
+  const int off = q.img_off[im];
+  const int R = q.img_off[im + 1] - off;
+  if (R <= 0 || R > q.max_rows || off < 0 || off + R > q.M) {
+    // not an image this launch can walk (the host bound max_rows is too small, or img_off is not ascending): nothing of
+    // it is touched, and its loss is NaN so that the batch loss cannot pass for a number
+    if (threadIdx.x == 0) { q.p.n_pc[im * q.p.NB + b] = 0; q.p.losses[im * q.p.NB + b] = __int_as_float(0x7fc00000); }
+    return;
+  }
+  pcl_refine_body<true>(q.p, b, im, off, R, 1.f / (float)q.n_img, lds_raw);
+}
+
+// loss[b] = (float)((sum over images i, ascending, of (double)loss_img[i][b]) / n): one thread per branch, fixed order
+struct PclMeanParams { const float* loss_img; float* loss; int n_img; int NB; };
+
+__global__ __launch_bounds__(64) void pcl_batch_mean_kernel(PclMeanParams p) {
+  const int b = threadIdx.x;
+  if (b >= p.NB) return;
+  double acc = 0.0;
+  for (int i = 0; i < p.n_img; ++i) acc += (double)p.loss_img[i * p.NB + b];
+  p.loss[b] = (float)(acc / (double)p.n_img);
+}
+
+constexpr size_t PCL_REFINE_LDS =
+    ((sizeof(PclShared) + 15) & ~size_t(15)) + 16384 + 32776 + 32768 + 32768 + 8192 + 8192 + PCL_NINV * 8;
 
 }  // namespace
 
@@ -700,15 +780,63 @@ int drn_pcl_refine(const float* logits, int ld, const int* cols, int n_branch, i
   PclRefineParams rp{};
   rp.boxes = boxes; rp.adj = adj; rp.wsddn = wsddn_scores; rp.ld_ws = ld_ws; rp.probs = probs; rp.onehot = onehot;
   rp.R = R; rp.K = K; rp.K1 = K + 1; rp.W32 = (R + 31) / 32; rp.NB = n_branch; rp.PMAX = pmax;
+  rp.ld_adj = rp.W32; rp.RS = R;
   rp.labels = labels; rp.cls_w = cls_w; rp.assign = assign; rp.pc_labels = pc_labels; rp.pc_probs = pc_probs;
   rp.pc_count = pc_count; rp.img_w = img_w; rp.pc_rows = pc_rows; rp.pc_scores = pc_scores; rp.n_pc = n_pc;
   rp.losses = losses; rp.dlogits = dlogits; rp.ld = ld;
   for (int b = 0; b < n_branch; ++b) { sp.cols[b] = cols[b]; rp.cols[b] = cols[b]; }
   pcl_softmax_kernel<<<dim3((R + 255) / 256, n_branch), 256, 0, stream>>>(sp);
   DRN_CHECK_LAUNCH();
-  const size_t lds = ((sizeof(PclShared) + 15) & ~size_t(15)) + 16384 + 32776 + 32768 + 32768 + 8192 + 8192 + PCL_NINV * 8;
+  const size_t lds = PCL_REFINE_LDS;
   if (!drn_launch::allow_lds(reinterpret_cast<const void*>(pcl_refine_kernel), (int)lds)) return DRN_ERR_LAUNCH;
   pcl_refine_kernel<<<n_branch, PCL_T, lds, stream>>>(rp);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+int drn_pcl_adjacency_batch(const float* boxes, const int* img_off, int n_img, int M, int max_rows, float iou_thr,
+                            uint32_t* adj, hipStream_t stream) {
+  if (!boxes || !img_off || !adj || n_img <= 0 || M <= 0 || max_rows <= 0) return DRN_ERR_ARG;
+  if (max_rows > PCL_MAXR || n_img > PCL_MAXIMG) return DRN_ERR_UNSUPPORTED;
+  if ((long)M > (long)n_img * max_rows) return DRN_ERR_ARG;  // some image has more than max_rows rows
+  PclAdjBatchParams p{boxes, adj, img_off, M, max_rows, (max_rows + 31) / 32, iou_thr};
+  pcl_adjacency_batch_kernel<<<dim3(p.W32, (max_rows + 255) / 256, n_img), 256, 0, stream>>>(p);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+int drn_pcl_refine_batch(const float* logits, int ld, const int* cols, int n_branch, int K, const float* wsddn_scores,
+                         int ld_ws, const float* boxes, const uint32_t* adj, const float* onehot, const int* img_off,
+                         int n_img, int M, int max_rows, float* probs, int* labels, float* cls_w, int* assign,
+                         int* pc_labels, float* pc_probs, int* pc_count, float* img_w, int* pc_rows, float* pc_scores,
+                         int* n_pc, int pmax, float* loss_img, float* losses, float* dlogits, hipStream_t stream) {
+  if (!logits || !cols || !wsddn_scores || !boxes || !adj || !onehot || !img_off || !probs || !labels || !cls_w ||
+      !assign || !pc_labels || !pc_probs || !pc_count || !img_w || !pc_rows || !pc_scores || !n_pc || !loss_img ||
+      !losses || !dlogits)
+    return DRN_ERR_ARG;
+  if (M <= 0 || max_rows <= 0 || n_img <= 0 || K <= 0 || n_branch <= 0 || n_branch > 8 || pmax < 5) return DRN_ERR_ARG;
+  if (max_rows > PCL_MAXR || n_img > PCL_MAXIMG || K > 128 || pmax > PCL_MAXP) return DRN_ERR_UNSUPPORTED;
+  if ((long)M > (long)n_img * max_rows) return DRN_ERR_ARG;
+  PclSoftmaxParams sp{};
+  sp.logits = logits; sp.ld = ld; sp.NB = n_branch; sp.K1 = K + 1; sp.R = M; sp.probs = probs;
+  PclBatchParams bp{};
+  PclRefineParams& rp = bp.p;
+  rp.boxes = boxes; rp.adj = adj; rp.wsddn = wsddn_scores; rp.ld_ws = ld_ws; rp.probs = probs; rp.onehot = onehot;
+  rp.R = 0; rp.K = K; rp.K1 = K + 1; rp.W32 = 0; rp.NB = n_branch; rp.PMAX = pmax;
+  rp.ld_adj = (max_rows + 31) / 32; rp.RS = M;
+  rp.labels = labels; rp.cls_w = cls_w; rp.assign = assign; rp.pc_labels = pc_labels; rp.pc_probs = pc_probs;
+  rp.pc_count = pc_count; rp.img_w = img_w; rp.pc_rows = pc_rows; rp.pc_scores = pc_scores; rp.n_pc = n_pc;
+  rp.losses = loss_img; rp.dlogits = dlogits; rp.ld = ld;
+  bp.img_off = img_off; bp.n_img = n_img; bp.M = M; bp.max_rows = max_rows;
+  for (int b = 0; b < n_branch; ++b) { sp.cols[b] = cols[b]; rp.cols[b] = cols[b]; }
+  pcl_softmax_kernel<<<dim3((M + 255) / 256, n_branch), 256, 0, stream>>>(sp);
+  DRN_CHECK_LAUNCH();
+  if (!drn_launch::allow_lds(reinterpret_cast<const void*>(pcl_refine_batch_kernel), (int)PCL_REFINE_LDS))
+    return DRN_ERR_LAUNCH;
+  pcl_refine_batch_kernel<<<dim3(n_branch, n_img), PCL_T, PCL_REFINE_LDS, stream>>>(bp);
+  DRN_CHECK_LAUNCH();
+  PclMeanParams mp{loss_img, losses, n_img, n_branch};
+  pcl_batch_mean_kernel<<<1, 64, 0, stream>>>(mp);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

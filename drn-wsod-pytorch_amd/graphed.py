@@ -103,7 +103,7 @@ class _StaticInputs:
         self._gt_block = torch.zeros((self._gt_words + extra,), dtype=torch.int32, device=self.model.device)
         self.gt = dict(onehot=self._gt_block[:nk].view(torch.float32).view(n_img, K),
                        classes=self._gt_block[nk: 2 * nk].view(n_img, K), count=self._gt_block[2 * nk: self._gt_words],
-                       props=self.props, max_rows=max(self.nper))
+                       props=self.props, max_rows=max(self.nper), rows=list(self.nper))
         if self._ann_gt:
             self.gt.update(annotated_views(self._gt_block[self._gt_words:], n_img, self._ann_gt))
         if hasattr(self, "_gt_nb"):

@@ -946,18 +946,31 @@ class _HeadEngine:
         if pcl and h.refine_K > 0:
             # PCLROIHeads (roi_heads_pcl.py:311-334): every branch's targets come from the previous branch's
             # probabilities through proposal clustering; targets, loss and dlogits of all branches in three launches
-            if n_img != 1:
+            batches = getattr(self, "pcl_image_batches", False)
+            if n_img != 1 and not batches:
                 raise DrnError("PCL clusters the proposals of ONE image per step (third_party/pcl.py:94 asserts it)")
             if any(h.refine_reg[: h.refine_K]):
                 raise DrnError("PCL with box regression branches is not on the built path (no reference config uses it)")
-            adj = ops.pcl_adjacency(gt["props"], 0.4)
-            res = ops.pcl_refine(w["logits"], [col["r%d" % k] for k in range(h.refine_K)], K, scores, gt["props"], adj,
-                                 gt["onehot"].view(-1), dl)
+            rcols = [col["r%d" % k] for k in range(h.refine_K)]
+            if batches:
+                # PCLROIHeads.enable_image_batches(): one (branch, image) grid clusters every image; loss_cls_r{k} is the mean
+                # over the images of the single-image loss and dlogits carries the 1 / n_img (include/drn_wsod.h)
+                max_rows = gt.get("max_rows") or M
+                adj = ops.pcl_adjacency_batch(gt["props"], img_off, n_img, max_rows, 0.4)
+                per_image, loss_img, loss_b = ops.pcl_refine_batch(w["logits"], rcols, K, scores, gt["props"], adj,
+                                                                   gt["onehot"], img_off, n_img, max_rows, dl,
+                                                                   rows=gt.get("rows"))
+                aux["targets"], aux["pcl_loss_img"] = per_image, loss_img
+                branch_loss = [loss_b[k: k + 1] for k in range(h.refine_K)]
+            else:
+                adj = ops.pcl_adjacency(gt["props"], 0.4)
+                res = ops.pcl_refine(w["logits"], rcols, K, scores, gt["props"], adj, gt["onehot"].view(-1), dl)
+                aux["targets"] = list(res)
+                branch_loss = [r["loss"] for r in res]
             for k in range(h.refine_K):
                 loss_names.append("loss_cls_r%d" % k)
-                loss_list.append(res[k]["loss"].view(()))
+                loss_list.append(branch_loss[k].view(()))
                 head_cols.append(("r%d" % k, len(loss_list) - 1))
-                aux["targets"].append(res[k])
         elif chain is None and h.refine_K > 0 and not any(h.refine_reg[: h.refine_K]):
             # no branch regresses boxes: every branch's targets depend only on the previous branch's softmax of logits
             # that already exist, so the whole cascade is four launches (drn_oicr_refine_chain)
@@ -1597,7 +1610,7 @@ class OICRROIHeads(ROIHeads):
             off = torch.tensor([0] + list(torch.tensor(nper).cumsum(0).tolist()), dtype=torch.int32)
             gt = dict(onehot=oh.to(dev, non_blocking=True), classes=gcl.to(dev, non_blocking=True),
                       count=torch.tensor([len(g) for g in ints], dtype=torch.int32).to(dev, non_blocking=True),
-                      props=self._take_props(rois), max_rows=max(nper))
+                      props=self._take_props(rois), max_rows=max(nper), rows=nper)
             ring = getattr(self._engine, "metrics", None)
             if ring is not None and ring.annotated:  # the annotated boxes, packed on the host: one more small upload
                 words = pack_annotated(targets, ring.max_gt).to(dev, non_blocking=True)
@@ -1663,6 +1676,25 @@ class PCLROIHeads(OICRROIHeads):
     (csrc/pcl.hip)."""
 
     refine_mode = "pcl"
+
+    @property
+    def image_batches(self):
+        return bool(getattr(self._engine, "pcl_image_batches", False))
+
+    def enable_image_batches(self, on=True):
+        """Train on batches of images (off by default: like the reference, a step with more than one image is refused).  On:
+        every image is clustered on its own, all of them in one (branch, image) launch; loss_cls_r{k} is the mean over the images
+        of the single-image loss - what a data-parallel job with one image per rank optimises - and _last_state["aux"]["targets"]
+        holds the per-image target dicts (include/drn_wsod.h, "PCL refinement on image batches"; at most ops.PCL_MAX_IMAGES
+        images of at most 4096 proposals).  A graphed step freezes its launch sequence when it is primed, so this has to come
+        first: enable_image_batches() -> build / prime the GraphedTrainStep."""
+        eng = self._engine
+        owner = getattr(eng, "captured_by", None)
+        if bool(on) != self.image_batches and owner is not None and owner() is not None:
+            raise DrnError("enable_image_batches() after a graphed step was primed: its captured launches are the other path's.  "
+                           "Order: enable_image_batches(), then create and prime the GraphedTrainStep / GraphedFullStep")
+        eng.pcl_image_batches = bool(on)
+        return self
 
 
 @ROI_HEADS_REGISTRY.register()

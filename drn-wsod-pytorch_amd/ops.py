@@ -1196,6 +1196,88 @@ def pcl_refine(logits, col0s, K, wsddn_scores, boxes, adj, onehot, dlogits):
     return out
 
 
+PCL_MAX_IMAGES, PCL_MAX_ROWS = 16, 4096  # include/drn_wsod.h DRN_PCL_MAX_IMAGES, the per-image limit of the PCL entries
+
+
+def _pcl_img_off(img_off, n_img, M, max_rows, dev):
+    """img_off of a PCL batch on the device.  A HOST tensor (or list) is checked first, where the sizes are known: ascending
+    from 0 to M, every image within 1 .. max_rows - refused without a launch - and then uploaded.  A device tensor is taken as
+    it is (no read-back): the kernels skip an image outside max_rows and make its loss NaN."""
+    if not 1 <= int(n_img) <= PCL_MAX_IMAGES:
+        raise C.DrnError("PCL image batch: %d images, 1 .. %d are built" % (n_img, PCL_MAX_IMAGES))
+    if not 1 <= int(max_rows) <= PCL_MAX_ROWS:
+        raise C.DrnError("PCL image batch: max_rows = %d, 1 .. %d proposals per image are built" % (max_rows, PCL_MAX_ROWS))
+    if not torch.is_tensor(img_off):
+        img_off = torch.tensor(list(img_off), dtype=torch.int32)
+    assert img_off.dtype == torch.int32 and img_off.numel() == n_img + 1 and img_off.is_contiguous()
+    if not img_off.is_cuda:
+        o = img_off.tolist()
+        rows = [b - a for a, b in zip(o[:-1], o[1:])]
+        if o[0] != 0 or o[-1] != M or min(rows) < 1:
+            raise C.DrnError("PCL image batch: img_off %s does not split %d rows into %d non-empty images" % (o, M, n_img))
+        if max(rows) > max_rows:
+            raise C.DrnError("PCL image batch: an image has %d proposals, max_rows = %d" % (max(rows), max_rows))
+        img_off = img_off.to(dev)
+    return img_off
+
+
+def pcl_adjacency_batch(boxes, img_off, n_img, max_rows, iou_thr=0.4):
+    """[M, ceil(max_rows/32)] uint32: per image the bit matrix of pcl_adjacency, bit columns local to the image, zero beyond
+    its row count (drn_pcl_adjacency_batch).  img_off int32 [n_img + 1]: device tensor, or host tensor (checked, see above)."""
+    M = boxes.shape[0]
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous()
+    img_off = _pcl_img_off(img_off, n_img, M, max_rows, boxes.device)
+    adj = torch.empty((M, (int(max_rows) + 31) // 32), dtype=torch.int32, device=boxes.device)
+    C.call("drn_pcl_adjacency_batch", C.ptr(boxes), C.ptr(img_off), int(n_img), M, int(max_rows), float(iou_thr), C.ptr(adj),
+           C.stream())
+    return adj
+
+
+def pcl_refine_batch(logits, col0s, K, wsddn_scores, boxes, adj, onehot, img_off, n_img, max_rows, dlogits, rows=None):
+    """pcl_refine for every image of a batch in one launch of (branch, image) workgroups (see include/drn_wsod.h: per image
+    bit for bit the single-image results, batch loss = mean over images in ascending order, dlogits * 1 / n_img).
+    onehot [n_img, K]; adj from pcl_adjacency_batch with the same max_rows.  Returns (per_image, loss_img [n_img, NB],
+    loss [NB]): per_image[i][b] is the dict pcl_refine returns for image i alone - views of the batch's buffers, cut at the
+    image's rows when the host knows them (img_off on the host, or rows = the per-image counts); `loss` in it is loss_img[i, b]."""
+    M, dev, nb = boxes.shape[0], boxes.device, len(col0s)
+    if rows is None and torch.is_tensor(img_off) and not img_off.is_cuda:
+        o = img_off.tolist()
+        rows = [b - a for a, b in zip(o[:-1], o[1:])]
+    img_off = _pcl_img_off(img_off, n_img, M, max_rows, dev)
+    assert adj.shape == (M, (int(max_rows) + 31) // 32) and adj.is_contiguous()
+    assert onehot.shape == (n_img, K) and onehot.dtype == torch.float32 and onehot.is_contiguous()
+    pmax = min(640, 5 * K)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    probs = e((nb, M, K + 1), torch.float32)
+    row = dict(labels=e((nb, M), torch.int32), cls_loss_weights=e((nb, M), torch.float32),
+               gt_assignment=e((nb, M), torch.int32))
+    pc = dict(pc_labels=e((n_img, nb, pmax), torch.int32), pc_probs=e((n_img, nb, pmax), torch.float32),
+              pc_count=e((n_img, nb, pmax), torch.int32), img_cls_loss_weights=e((n_img, nb, pmax), torch.float32),
+              pc_rows=e((n_img, nb, pmax), torch.int32), pc_scores=e((n_img, nb, pmax), torch.float32))
+    n_pc = e((n_img, nb), torch.int32)
+    loss_img = e((n_img, nb), torch.float32)
+    losses = e((nb,), torch.float32)
+    c0 = C.host_ints(col0s)
+    C.call("drn_pcl_refine_batch", C.ptr(logits), _2d(logits), ctypes.cast(c0, ctypes.c_void_p), nb, K, C.ptr(wsddn_scores),
+           _2d(wsddn_scores), C.ptr(boxes), C.ptr(adj), C.ptr(onehot), C.ptr(img_off), int(n_img), M, int(max_rows),
+           C.ptr(probs), C.ptr(row["labels"]), C.ptr(row["cls_loss_weights"]), C.ptr(row["gt_assignment"]),
+           C.ptr(pc["pc_labels"]), C.ptr(pc["pc_probs"]), C.ptr(pc["pc_count"]), C.ptr(pc["img_cls_loss_weights"]),
+           C.ptr(pc["pc_rows"]), C.ptr(pc["pc_scores"]), C.ptr(n_pc), pmax, C.ptr(loss_img), C.ptr(losses), C.ptr(dlogits),
+           C.stream())
+    per_image, r0 = [], 0
+    for i in range(n_img):
+        sl = slice(None) if rows is None else slice(r0, r0 + rows[i])
+        out = []
+        for b in range(nb):
+            d = {k: v[b, sl] for k, v in row.items()}
+            d.update({k: v[i, b] for k, v in pc.items()})
+            d.update(n_pc=n_pc[i, b: b + 1], probs=probs[b, sl], loss=loss_img[i, b: b + 1])
+            out.append(d)
+        per_image.append(out)
+        r0 += 0 if rows is None else rows[i]
+    return per_image, loss_img, losses
+
+
 COCO_MAX_GT, COCO_MAX_AREAS, COCO_MAX_REC = 512, 4, 128  # include/drn_wsod.h DRN_COCO_MAX_*
 
 

@@ -804,7 +804,8 @@ int drn_voc_accumulate(const unsigned long long* tp, const unsigned long long* f
  * The reference computes these on the HOST: the targets in numpy + scikit-learn after a device->host copy of the scores
  * (projects/WSL/wsl/modeling/roi_heads/third_party/pcl.py:26-200, called from fast_rcnn.py:1725-1745), the loss in C++ on
  * the CPU (projects/WSL/wsl/layers/csrc/pcl_loss/pcl_loss.h:52-131 always dispatches to pcl_loss_cpu.cpp:8-117).  One
- * image per call (the reference asserts a batch of one, pcl.py:94,149); R <= 4096, K <= 128.
+ * image per call (the reference asserts a batch of one, pcl.py:94,149); R <= 4096, K <= 128.  Image batches: the two
+ * *_batch entries below.
  *
  * drn_pcl_adjacency: `_build_graph` (pcl.py:78-87): bit r2 of word adj[r1][r2/32] = IoU(box r1, box r2) > iou_thr
  * (pairwise_iou, detectron2/structures/boxes.py:329-361).  adj: [R, ceil(R/32)] uint32.  Shared by every branch. */
@@ -825,6 +826,44 @@ int drn_pcl_refine(const float* logits, int ld, const int* cols, int n_branch, i
                    int* labels, float* cls_w, int* assign, int* pc_labels, float* pc_probs, int* pc_count,
                    float* img_w, int* pc_rows, float* pc_scores, int* n_pc, int pmax, float* losses, float* dlogits,
                    void* stream);
+
+/* ---- PCL refinement on image batches ------------------------------------------------------------------------------------
+ * The reference has no batched PCL (pcl.py:90 asserts one image and its recipes run IMS_PER_BATCH = 4 as four processes
+ * of one image); the definition is this package's.  A batch holds n_img images; image i owns rows
+ * [img_off[i], img_off[i+1]) of boxes / logits / wsddn_scores (R_i rows, M rows in all) and the labels onehot[i].
+ * img_off: DEVICE int32 [n_img + 1], ascending from 0 to M (what the MIL entries take); max_rows: a HOST bound on every
+ * R_i.  Nothing is read back, so both entries can be captured into a graph.
+ *   targets   every per-row and per-cluster output of image i and branch b, n_pc and probs are what drn_pcl_adjacency +
+ *             drn_pcl_refine give for that image alone, bit for bit; pc_rows / assign hold rows LOCAL to the image
+ *   loss_img  [n_img, n_branch]: the single-image loss (sum / R_i), bit for bit
+ *   losses    [n_branch]: (float)((sum over i ascending of (double)loss_img[i][b]) / n_img) - the mean over images, in a
+ *             fixed order without float atomics
+ *   dlogits   the rows of image i are the single-image rows, every entry multiplied once more by 1.f / (float)n_img
+ *             (exact for n_img = 1, 2, 4, 8, 16)
+ *   an image without labels follows oracle/pcl_oracle.py like the single-image entry (no centres, loss 0, dlogits 0)
+ * Limits: 1 <= n_img <= DRN_PCL_MAX_IMAGES, max_rows <= 4096 (the per-image limit of the single entries), K <= 128,
+ * pmax <= 640: beyond them DRN_ERR_UNSUPPORTED.  M > n_img * max_rows (some image must exceed the bound) is DRN_ERR_ARG.
+ * What the host cannot see: an image whose R_i on the device is outside 1 .. max_rows (or runs past M) is skipped by
+ * both entries - none of its rows is written, its n_pc is 0 and its loss_img NaN, which makes the batch loss NaN.
+ *
+ * drn_pcl_adjacency_batch: adj [M, W] uint32 with W = ceil(max_rows / 32), the same for every image: bit c of word
+ * adj[img_off[i] + r][c / 32] = IoU(box r, box c of image i) > iou_thr, c LOCAL to the image.  Every word of an image's
+ * rows is written: bits at and beyond R_i, and whole words beyond ceil(R_i / 32), are zero.  Grid: (word, 256-row block,
+ * image). */
+#define DRN_PCL_MAX_IMAGES 16
+int drn_pcl_adjacency_batch(const float* boxes, const int* img_off, int n_img, int M, int max_rows, float iou_thr,
+                            uint32_t* adj, void* stream);
+
+/* drn_pcl_refine_batch: drn_pcl_refine for every (branch, image) pair in one launch of n_branch * n_img workgroups, behind
+ * one row softmax over all M rows and in front of the one-wave mean.  Arguments as for drn_pcl_refine, with: onehot
+ * [n_img, K]; adj as written by drn_pcl_adjacency_batch with the same max_rows; probs [n_branch, M, K+1]; labels / cls_w /
+ * assign [n_branch, M] (image i at columns img_off[i] ..); pc_* / img_w [n_img, n_branch, pmax]; n_pc and loss_img
+ * [n_img, n_branch]; losses [n_branch]; dlogits [M, ld]. */
+int drn_pcl_refine_batch(const float* logits, int ld, const int* cols, int n_branch, int K, const float* wsddn_scores,
+                         int ld_ws, const float* boxes, const uint32_t* adj, const float* onehot, const int* img_off,
+                         int n_img, int M, int max_rows, float* probs, int* labels, float* cls_w, int* assign,
+                         int* pc_labels, float* pc_probs, int* pc_count, float* img_w, int* pc_rows, float* pc_scores,
+                         int* n_pc, int pmax, float* loss_img, float* losses, float* dlogits, void* stream);
 
 /* ---- CSC head (CSCROIHeads) -------------------------------------------------------------------------
  * projects/WSL/wsl/modeling/roi_heads/roi_heads_csc.py:423-510 and wsl/layers/csrc/csc/csc_cuda.cu.  One image per
