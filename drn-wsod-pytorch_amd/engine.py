@@ -744,7 +744,7 @@ class FusedSGD:
         else:
             ops.sgd_step(e.arena_w, self._mom, e.arena_g, segs, nseg, self.momentum, self._steps == 0, 1.0 / world,
                          shadow=e.arena_s, clip=clip, guard=self._gs)
-        if what == "small" and hasattr(e, "sh"):
+        if what == "small" and e.sh is not None:
             e.refresh_transposes()  # fc7 / predictor weights are final for this step: rebuild their K-major twins here
             e._transposes_fresh = True
 
@@ -941,7 +941,7 @@ class DataParallel:
         self.exchange = self.world > 1 or (force_exchange and dist.is_available() and dist.is_initialized())
         self.engine.fc1_grad_slabs = slabs if self.world > 1 else 1
         if self.world > 1:
-            if getattr(self.engine, "grad_ready_hook", None) is not None:
+            if self.engine.grad_ready_hook is not None:
                 raise DrnError("the head engine already has a gradient hook (FusedSGD.enable_pipelined ran first): build "
                                "DataParallel before the optimizer's pipelined mode and pass it as enable_pipelined(dp)")
             self.engine.grad_ready_hook = self._on_ready
@@ -1021,7 +1021,7 @@ class DataParallel:
             raise DrnError("DataParallel.selftest needs an initialised process group")
         g, W = self.group, self.world
         rank = dist.get_rank(g)
-        dev = self.engine.arena_w.device if getattr(self.engine, "arena_w", None) is not None else \
+        dev = self.engine.arena_w.device if self.engine.arena_w is not None else \
             next(self.model.roi_heads.parameters()).device
         es = torch.empty((), dtype=wire_dtype).element_size()
 

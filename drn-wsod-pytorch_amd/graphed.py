@@ -86,7 +86,7 @@ class _StaticInputs:
 
     def _annot_max_gt(self):
         """max_gt of the metrics ring's annotated-box block, 0 without one"""
-        m = getattr(self.engine, "metrics", None)
+        m = self.engine.metrics
         return m.max_gt if m is not None and m.annotated else 0
 
     def _layout_labels(self):
@@ -115,7 +115,7 @@ class _StaticInputs:
         """the annotated-box option may be switched until the step is primed (enable_metrics() is refused afterwards): the block is
         laid out anew while nothing was captured; a captured step keeps the layout its graphs read"""
         if self._annot_max_gt() != self._ann_gt:
-            own = getattr(self.engine, "captured_by", None)
+            own = self.engine.captured_by
             if own is None or own() is not self:
                 self._layout_labels()
 
@@ -123,7 +123,7 @@ class _StaticInputs:
     def metrics(self):
         """the head engine's MetricsRing (ROIHeads.enable_metrics(), BEFORE this step is primed: the two launches are captured
         with the heads like any other), or None"""
-        return getattr(self.engine, "metrics", None)
+        return self.engine.metrics
 
     def _anchor_metrics(self, start_iter):
         """the ring counts records; the next one is iteration start_iter (one small D2H read, at construction)"""
@@ -302,11 +302,11 @@ class GraphedTrainStep(_StaticInputs):
     def release(self):
         """give the fc6 operand sets back (they may grow again); the captured graphs of this object must not be replayed
         afterwards"""
-        own = getattr(self.engine, "pool_sets_pin_owner", None)
+        own = self.engine.pool_sets_pin_owner
         if own is not None and own() is self:
             self.engine.pool_sets_pinned = None
             self.engine.pool_sets_pin_owner = None
-        own = getattr(self.engine, "captured_by", None)
+        own = self.engine.captured_by
         if own is not None and own() is self:
             self.engine.captured_by = None
         self._primed = False
@@ -494,7 +494,7 @@ class GraphedTrainStep(_StaticInputs):
         G, A = self._GA
         # the ring: trunk groups on one GPU, the eager fc6 tail with the pipelined optimizer's hook (its event is the throttle's)
         self._ring_on = (self.trunk_pairs and self.engine.kshard is None and self.split_tail
-                         and getattr(self.engine, "grad_ready_hook", None) is not None and self._ring_want)
+                         and self.engine.grad_ready_hook is not None and self._ring_want)
         P = A if not self.trunk_pairs else self.RING_SLOTS if self._ring_on else 2
         self._GAP = (G, A, P)
         self._sides = [self._side] + [torch.cuda.Stream() for _ in range(A - 2)]

@@ -140,7 +140,7 @@ class GeneralizedRCNNWSL(nn.Module):
         engine's thread hand-over and its scalar add / ones / stack launches).  Returns False when the model has no fused
         head engine state to run (the caller then uses autograd)."""
         eng = getattr(self.roi_heads, "_engine", None)
-        st = getattr(eng, "_last_state", None) if eng is not None else None
+        st = eng._last_state if eng is not None else None
         if st is None:
             return False
         eng._last_state = None

@@ -241,7 +241,7 @@ class GeneralizedRCNNWithTTAAVG(nn.Module):
         # _batch_inference (:200-225): consecutive augmentations in groups of `batch_size` through ONE model.inference (the mapper
         # emits each size's plain and flipped image next to each other, so batch_size = 2 batches same-size pairs: one conv chain
         # per pair); the averages are accumulated per augmentation in the mapper's order either way
-        prev, heads.scores_only = getattr(heads, "scores_only", False), True
+        prev, heads.scores_only = heads.scores_only, True
         try:
             for g0 in range(0, n, self.batch_size):
                 group = augmented_inputs[g0: g0 + self.batch_size]

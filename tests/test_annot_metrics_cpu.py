@@ -147,7 +147,7 @@ def test_pack_annotated_and_max_gt_exceeded():
 def _stub(append_gt=False, refine_K=3, owner=None):
     eng = types.SimpleNamespace(captured_by=owner, arena_w=torch.zeros(1), ensure=lambda dev: None, metrics=None)
     return types.SimpleNamespace(_engine=eng, parameters=lambda: iter([torch.zeros(1)]), proposal_append_gt=append_gt,
-                                 refine_K=refine_K)
+                                 refine_K=refine_K, refine_mode="oicr")
 
 
 def test_enable_metrics_refusals():

@@ -265,7 +265,7 @@ def test_graphed_full_step_trainable_trunk_equals_eager(name, freeze_at):
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_workspace_views_follow_changing_proposal_counts(precision):
     """Real data brings another proposal count every step.  The head engine's workspaces and fc6-operand sets are
-    capacity-based views (roi_heads.py `_HeadEngine.ws` / `pool`): after a LARGER batch the buffers still hold that
+    capacity-based views (head_engine.py `_HeadEngine.ws` / `pool`): after a LARGER batch the buffers still hold that
     batch's values beyond the new M - the K-role pad columns of the transposed twins (read by the dW GEMMs) must be
     zero again.  Losses and every gradient of [large, then small] must equal BIT FOR BIT those of a fresh model that
     only ever saw the small batch (M = 37: pad up to 64 in bf16, to 40 in fp32)."""

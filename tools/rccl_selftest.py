@@ -21,6 +21,7 @@ from __graft_entry__ import load_package  # noqa: E402
 
 class _Eng:
     arena_w = None
+    grad_ready_hook = None
 
 
 class _Model:  # DataParallel only needs the head engine's device here
