@@ -849,14 +849,14 @@ class FusedSGD:
     def refresh_tables(self):
         """Re-evaluate every per-segment (lr, weight decay) table that already lives on the device, IN PLACE: kernels
         captured into a hipGraph keep reading those buffers, so a replay follows scheduler.step() only if the tables
-        are rewritten before it (GraphedTrainStep.step does this)."""
+        are rewritten before it (GraphedTrainStep.step does this).  A table is rewritten only when an lr or weight decay in it
+        changed: the rewrite is a copy from pageable memory, which holds the host until the current stream has drained - done
+        on every step it kept the host of the graphed steps with the plain optimizer from ever running ahead of the device."""
         if self._segs_dev is not None:
-            self._segs_key = None
             self._segs()
         for what in list(getattr(self, "_bucket_segs", {})):
             self._bucket_table(what)
         if self._bb is not None and self._bb["segs_dev"] is not None:
-            self._bb["segs_key"] = None
             self._segs_bb()
 
 

@@ -434,12 +434,13 @@ class GraphedTrainStep(_StaticInputs):
             self.opt.step(1.0)
 
     # ---- the ahead schedule: lookahead L >= 2, trunk groups, the ring ---------------------------------------------------------------
-    def _run_ahead(self, eager, next_batch, upcoming):
+    def _run_ahead(self, eager, next_batch, upcoming, ready=()):
         """Step t at (G, A, P): see ahead_schedule for the indices.
           side : proposals / labels of batch t+1 -> the staging set; when t % G == 0, the images of the group A ahead -> its slot
                  and the conv chain of that slot.  The slot's and the set's last readers are pooling launches of earlier steps: one
                  wait on the main stream orders the side stream behind them, under the ring the host's throttle does.  With A >= 3
-                 the A-1 side streams take turns
+                 the A-1 side streams take turns.  `ready` (step()'s inputs_ready): events behind the producers of the caller's
+                 tensors - the stream that stages them waits for each first; empty, nothing is enqueued
           main : heads graph of batch t (+ eager tail), wait for the trunk of batch t+1's group, pooling piece of batch t+1"""
         main = torch.cuda.current_stream()
         t = self._t
@@ -463,6 +464,9 @@ class GraphedTrainStep(_StaticInputs):
             self._ring_evs.append(ev)
         evp = None
         with torch.cuda.stream(side):
+            if self.stage_ahead or s.launch is not None:
+                for ev in ready:
+                    side.wait_event(ev)
             # proposals of batch t+1 on the side stream (behind the last reader of their staging set, in front of the conv chain):
             # three small launches that sat between the last dW slab and the pooling piece on the main stream (22 us in the timeline)
             if self.stage_ahead:
@@ -478,6 +482,8 @@ class GraphedTrainStep(_StaticInputs):
         if evp is not None:
             main.wait_event(evp)
         else:
+            for ev in ready:
+                main.wait_event(ev)
             self._stage_props(next_batch)
         main.wait_event(self._done[s.pool_slot])
         self._pool_body(s.pool_slot, s.pool_part)
@@ -486,15 +492,25 @@ class GraphedTrainStep(_StaticInputs):
         self._t = t + 1
         return losses
 
+    def _ring_allowed(self):
+        """the ring: trunk groups on ONE GPU, the eager fc6 tail with THIS optimizer's pipelined hook (its event is the throttle's).
+        Any other hook on the head engine (DataParallel's alone) or a job of several ranks gets the waiting schedule"""
+        hook = self.engine.grad_ready_hook
+        own = bool(getattr(self.opt, "_pipelined", False)) and hook is not None and getattr(hook, "__self__", None) is self.opt
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        dp = getattr(self.opt, "_dp", None)
+        if dp is not None:
+            world = max(world, int(dp.world))
+        return bool(self.trunk_pairs and self.engine.kshard is None and self.split_tail and own and world == 1
+                    and self._ring_want)
+
     def _prime_ahead(self, first_batch, next_batch, upcoming):
         """The trunks of groups 0 .. A-1 and the pooling of batch 0, step 0 eagerly (_run_ahead launches group A's chain), then the
         captures: the heads graph and one chain graph per slot."""
         self.heads.train()
         main = torch.cuda.current_stream()
         G, A = self._GA
-        # the ring: trunk groups on one GPU, the eager fc6 tail with the pipelined optimizer's hook (its event is the throttle's)
-        self._ring_on = (self.trunk_pairs and self.engine.kshard is None and self.split_tail
-                         and self.engine.grad_ready_hook is not None and self._ring_want)
+        self._ring_on = self._ring_allowed()
         P = A if not self.trunk_pairs else self.RING_SLOTS if self._ring_on else 2
         self._GAP = (G, A, P)
         self._sides = [self._side] + [torch.cuda.Stream() for _ in range(A - 2)]
@@ -526,7 +542,7 @@ class GraphedTrainStep(_StaticInputs):
         return first
 
     # ---- lookahead = 1 ------------------------------------------------------------------------------------------------------------
-    def _run(self, eager, next_batch=None):
+    def _run(self, eager, next_batch=None, ready=()):
         """One step = three pieces on two torch streams, ordered by events exactly like eager multi-stream code.  (A
         single graph with the backbone as an internal branch was measured first: the HIP graph executor starts that
         branch late whatever the capture order, so the 49 latency-bound conv nodes ended up on the critical path.)
@@ -542,6 +558,8 @@ class GraphedTrainStep(_StaticInputs):
             self.engine.run_fc1_tail()  # eager: dW slabs on this stream, all-reduce + SGD per bucket on the optimizer stream
         with torch.cuda.stream(self._side):
             if next_batch is not None:
+                for ev in ready:  # (step()'s inputs_ready)
+                    self._side.wait_event(ev)
                 # the next batch's image / proposals are consumed by this stream's backbone graph and by the pooling graph
                 # behind it: staging them here keeps five small copies off the front of the heads graph
                 self._stage_next(next_batch)
@@ -577,11 +595,26 @@ class GraphedTrainStep(_StaticInputs):
         self._mark_captured()
         return first
 
-    def step(self, batch, next_batch, *upcoming):
+    def step(self, batch, next_batch, *upcoming, inputs_ready=None):
         """run the step for `batch` (which must be the batch passed as `next_batch` to the previous call); the same
         step prepares `next_batch` (backbone on the side stream, pooling behind the last dW GEMM).  The ahead schedule also takes
         the ahead_arity(G, A) batches after that, of which only the images are read: lookahead=L, batches t+2 .. t+L (the backbone
-        of the last one runs now); trunk_pairs=G, batches t+2 .. t+2G-1 (when t % G == 0 the chain of the last G starts now)."""
+        of the last one runs now); trunk_pairs=G, batches t+2 .. t+2G-1 (when t % G == 0 the chain of the last G starts now).
+
+        When the inputs must be ready.  The step reads the caller's DEVICE tensors - proposal boxes and objectness of `next_batch`,
+        the images of `next_batch` (lookahead=1) or of `upcoming` - on a side stream, and keeps the allocator from reusing them
+        (record_stream) until it has.  What that read is ordered behind depends on the schedule:
+          the waiting schedules (lookahead=L, trunk groups with ring=False or wherever the ring does not apply) : the side stream
+              waits for the stream current at the call, so whatever the caller enqueued THERE before step() - a non-blocking
+              copy, preprocessing - is done first.  Plain stream order suffices
+          the ring : the side stream waits for nothing the caller enqueued.  The tensors must be complete from the HOST's point
+              of view (the producer synchronised, as DatasetMapper.finish does), or the caller passes
+        inputs_ready = an event, or a sequence of events, recorded behind the producers of these tensors (on any stream): every
+        stream that stages caller tensors in this step waits for each of them first (wait_event: the host never blocks).  It is
+        honoured by every schedule; with None nothing is enqueued.  Image-level labels (gt_classes) are read on the host during
+        the call and are outside this contract."""
+        ready = () if inputs_ready is None else (inputs_ready,) if isinstance(inputs_ready, torch.cuda.Event) \
+            else tuple(inputs_ready)
         self._replayed = self._primed
         if not self._primed:
             self._check_label_layout()  # (in front of the first staging: the staging sets follow the block)
@@ -598,18 +631,26 @@ class GraphedTrainStep(_StaticInputs):
                 self._guard.open_window()
         if self._GA is None:
             if not self._primed:
+                self._await(ready)
                 return self.prime(batch, next_batch)
             self._stage_labels_now(batch)
-            return self._run(eager=False, next_batch=next_batch)
+            return self._run(eager=False, next_batch=next_batch, ready=ready)
         if len(upcoming) != ahead_arity(*self._GA):
             if self.trunk_pairs:
                 raise DrnError("GraphedTrainStep(trunk_pairs=%d).step needs batches t+2 .. t+%d" % (self.G, 2 * self.G - 1))
             raise DrnError("GraphedTrainStep(lookahead=%d).step needs the %d batches after next_batch"
                            % (self.lookahead, self.lookahead - 1))
         if not self._primed:
+            self._await(ready)
             return self._prime_ahead(batch, next_batch, upcoming)
         self._stage_labels_now(batch)
-        return self._run_ahead(False, next_batch, upcoming)
+        return self._run_ahead(False, next_batch, upcoming, ready)
+
+    @staticmethod
+    def _await(ready):
+        """priming stages on the current stream and the streams it forks wait for that one: the events go in front of it all"""
+        for ev in ready:
+            torch.cuda.current_stream().wait_event(ev)
 
 
 class GraphedFullStep(_StaticInputs):

@@ -101,7 +101,8 @@ class FrozenBatchNorm2d(nn.Module):
         bn_types = (nn.BatchNorm2d, nn.SyncBatchNorm)
 
         def frozen_from(bn):
-            out = cls(bn.num_features, eps=bn.eps)
+            # on the source's device and in its dtype: a module converted after .to(device) must not be left with CPU buffers
+            out = cls(bn.num_features, eps=bn.eps).to(device=bn.running_mean.device, dtype=bn.running_mean.dtype)
             with torch.no_grad():
                 if bn.affine:
                     out.weight.copy_(bn.weight)

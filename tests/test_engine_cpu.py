@@ -175,6 +175,29 @@ def test_refresh_tables_in_place_after_lr_change():
     assert np.allclose(lr_small, np.asarray(want, dtype=np.float32))
 
 
+def test_refresh_tables_rewrites_the_plain_table_only_after_a_change():
+    """the plain step's table: refresh_tables() leaves it alone while no lr / weight decay moved (the rewrite is a blocking copy on
+    the device: tests/test_step_timing_gpu.py's laggard-main cases need the host to run ahead) and follows the scheduler, in
+    place, when one did"""
+    import numpy as np
+
+    cfg, model = _cpu_model()
+    opt = build_optimizer(cfg, model)
+    segs, n = opt._segs()
+    dt = [("off", "<i8"), ("cnt", "<i8"), ("lr", "<f4"), ("wd", "<f4")]
+    before = np.frombuffer(segs.numpy().tobytes(), dtype=dt).copy()
+    version = segs._version
+    opt.refresh_tables()
+    assert opt._segs_dev is segs and segs._version == version  # not written
+    sched = WarmupMultiStepLR(opt, [2], gamma=0.1, warmup_iters=0)
+    sched.step(), sched.step()
+    opt.refresh_tables()
+    assert opt._segs_dev is segs and segs._version > version
+    after = np.frombuffer(segs.numpy().tobytes(), dtype=dt)
+    assert np.allclose(after["lr"], before["lr"] * 0.1)
+    assert (after["off"] == before["off"]).all() and (after["cnt"] == before["cnt"]).all() and (after["wd"] == before["wd"]).all()
+
+
 def test_single_process_dataparallel_keeps_the_pipelined_hook():
     cfg, model = _cpu_model()
     opt = build_optimizer(cfg, model)

@@ -140,8 +140,10 @@ class _Recorder:
         self.log.append((self.cur[-1].name,) + what)
 
 
-def _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead, steps=13):
-    """_run_ahead for `steps` steps (step 0 eager, as at priming, then replays) on a GraphedTrainStep whose pieces only log"""
+def _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead, steps=13, inputs_ready=None, hook_event=True):
+    """_run_ahead for `steps` steps (step 0 eager, as at priming, then replays) on a GraphedTrainStep whose pieces only log.
+    inputs_ready: "none" passes step()'s default explicitly, "event" one event per replayed step (tagged ("ready", step));
+    hook_event=False: the fc6 tail leaves no small_ready_event behind (no pipelined optimizer's hook)"""
     import torch
 
     rec = _Recorder()
@@ -161,8 +163,9 @@ def _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead, steps=13)
 
         def run_fc1_tail(self):
             rec.say("tail")
-            o.opt.small_ready_event = rec.Event()
-            o.opt.small_ready_event.record()
+            if hook_event:
+                o.opt.small_ready_event = rec.Event()
+                o.opt.small_ready_event.record()
 
     class Graph:
         def __init__(self, slot):
@@ -185,7 +188,11 @@ def _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead, steps=13)
     o.g_pbb = [Graph(slot) for slot in range(P)]
     seq = [[{"id": k}] for k in range(steps + 2 + ahead_arity(G, A))]
     for i in range(steps):
-        o._run_ahead(i == 0, seq[i + 1], tuple(seq[i + 2: i + 2 + ahead_arity(G, A)]))
+        args = (i == 0, seq[i + 1], tuple(seq[i + 2: i + 2 + ahead_arity(G, A)]))
+        if inputs_ready is None:
+            o._run_ahead(*args)
+        else:
+            o._run_ahead(*args, () if inputs_ready == "none" or i == 0 else (rec.Event(("ready", i)),))
     return rec.log
 
 
@@ -214,3 +221,89 @@ def test_launch_order_is_the_recorded_one(monkeypatch, recorded_order, split_tai
         got = _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead)
         want = recorded_order["%s split%d ahead%d" % (name, split_tail, stage_ahead)]
         assert json.loads(json.dumps(got)) == want, name
+
+
+def _cases(split_tail):
+    cases = [("L%d" % L, 1, L, L, False) for L in (2, 3, 4)]
+    return cases + [("G%d ring%d" % (G, ring), G, 1, SLOTS if ring else 2, ring) for G in (2, 3, 4, 8) for ring in (False, True)
+                    if split_tail or not ring]
+
+
+@pytest.mark.parametrize("stage_ahead", [True, False])
+@pytest.mark.parametrize("split_tail", [True, False])
+def test_inputs_ready_none_enqueues_nothing_and_an_event_only_its_waits(monkeypatch, recorded_order, split_tail, stage_ahead):
+    """step(inputs_ready=None) - bench.py's call - issues the recorded order, entry for entry.  With an event per step the order
+    is the same but for wait_event entries on that event: one on the side stream in front of its first staging copy of the step
+    (proposals with stage_ahead, else the images of a launched chain), and with stage_ahead off one on the main stream in front
+    of the proposals staged there."""
+    import json
+
+    for name, G, A, P, ring in _cases(split_tail):
+        want = recorded_order["%s split%d ahead%d" % (name, split_tail, stage_ahead)]
+        none = _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead, inputs_ready="none")
+        assert json.loads(json.dumps(none)) == want, name
+        got = _launch_order(monkeypatch, G, A, P, ring, split_tail, stage_ahead, inputs_ready="event")
+        is_wait = lambda e: e[1] == "wait_event" and isinstance(e[2], tuple) and e[2][0] == "ready"
+        # (events are known by the position of their record: compare with the waits' own positions taken out)
+        strip = lambda log: [tuple(x for x in e if not (isinstance(x, tuple) and x and x[0] == "rec")) for e in log]
+        assert strip([e for e in got if not is_wait(e)]) == strip(none), name
+        waits = [(k, e) for k, e in enumerate(got) if is_wait(e)]
+        assert {e[2][1] for _, e in waits} <= set(range(1, 13)) and waits, name
+        for k, e in waits:
+            nxt = got[k + 1]
+            if e[0] == "main":
+                assert not stage_ahead and nxt[:2] == ("main", "props"), (name, e, nxt)
+            else:
+                assert nxt[0] == e[0] and nxt[1] == ("props" if stage_ahead else "images"), (name, e, nxt)
+        for i in range(1, 13):  # every step that stages caller tensors on a stream has that stream wait first
+            mine = [e for _, e in waits if e[2][1] == i]
+            assert len(mine) >= 1, (name, i)
+            assert len(mine) == len({e[0] for e in mine}), (name, i)
+
+
+class _Hooks:
+    def on_ready(self, what):
+        pass
+
+
+def _gated(hook_owner, pipelined, ring=True):
+    o = GraphedTrainStep.__new__(GraphedTrainStep)
+
+    class Engine:
+        kshard = None
+
+    o.opt = _Hooks()
+    o.opt._pipelined = pipelined
+    o.engine = Engine()
+    o.engine.grad_ready_hook = {"opt": o.opt.on_ready, "dp": _Hooks().on_ready, "none": None}[hook_owner]
+    o.trunk_pairs, o.split_tail, o._ring_want = True, True, ring
+    return o
+
+
+def test_ring_needs_this_optimizers_pipelined_hook_and_one_rank(monkeypatch):
+    """The ring's throttle is the event FusedSGD's hook leaves behind the heads.  Another object's hook alone (DataParallel's
+    without enable_pipelined) or a job of several ranks gets the waiting schedule - and the step runs: it used to raise "the ring
+    schedule needs the pipelined optimizer's hook" at the first replay."""
+    import torch.distributed as dist
+
+    assert _gated("opt", True)._ring_allowed() is True
+    assert _gated("opt", True, ring=False)._ring_allowed() is False
+    assert _gated("dp", False)._ring_allowed() is False
+    assert _gated("dp", True)._ring_allowed() is False
+    assert _gated("none", True)._ring_allowed() is False
+    o = _gated("opt", True)
+    o.opt._dp = type("Dp", (), {"world": 2})()
+    assert o._ring_allowed() is False
+    monkeypatch.setattr(dist, "is_initialized", lambda: True)
+    monkeypatch.setattr(dist, "get_world_size", lambda *a: 2)
+    assert _gated("opt", True)._ring_allowed() is False
+    monkeypatch.undo()
+    # DataParallel's hook only, ring=True asked for: _ring_on is False and thirteen steps run, in the waiting schedule's order
+    ring_on = _gated("dp", False)._ring_allowed()
+    assert ring_on is False
+    got = _launch_order(monkeypatch, 2, 1, 2, ring_on, True, True, hook_event=False)
+    want = _launch_order(monkeypatch, 2, 1, 2, False, True, True)
+    want = [e for k, e in enumerate(want) if not (e == ("main", "record") and want[k - 1] == ("main", "tail"))]  # (the hook's event)
+    strip = lambda log: [tuple(x for x in e if not (isinstance(x, tuple) and x and x[0] == "rec")) for e in log]
+    assert strip(got) == strip(want) and len(got) > 13 * 8
+    assert ("side0", "wait_stream", "main") in got and not any(e[:2] == ("host", "sync") for e in got)
