@@ -66,6 +66,8 @@ _SIGS = {
     "drn_mean_softmax": "plpiipiip",
     "drn_box_reg_loss": "pliippppplppifp",
     "drn_apply_deltas": "plppiipfp",
+    "drn_annot_box_reg": "plpii" + "ppiii" + "pppi" + "ppi" + "p" + "plf" + "ppp" + "p" + "p",
+    "drn_apply_deltas_mean": "plpii" + "ppii" + "pfp",
     "drn_sum_small": "pifpp",
     "drn_sgd_step": "pppilpipififp",
     "drn_sgd_step_block": "pppilpip" + "iiiil" + "fifp",

@@ -12,6 +12,7 @@
 //   apply_deltas       Box2BoxTransform.apply_deltas box_regression.py:73-110
 //   sgd_step           torch.optim.SGD as built by detectron2/solver/build.py:93-137
 #include "drn_common.h"
+#include "box_shared.h"
 #include "tune.h"
 #include <stdlib.h>
 #include <float.h>
@@ -968,15 +969,7 @@ struct BoxRegParams {
   float* dlogits; long ld_d; float* loss; int M; float wx, wy, ww, wh, loss_scale;
 };
 
-__device__ __forceinline__ void box_target(const float* s, const float* t, float wx, float wy, float ww, float wh,
-                                           float (&d)[4]) {
-  const float sw = s[2] - s[0], sh = s[3] - s[1];
-  const float sx = s[0] + 0.5f * sw, sy = s[1] + 0.5f * sh;
-  const float tw = t[2] - t[0], th = t[3] - t[1];
-  const float tx = t[0] + 0.5f * tw, ty = t[1] + 0.5f * th;
-  d[0] = wx * (tx - sx) / sw; d[1] = wy * (ty - sy) / sh;
-  d[2] = ww * logf(tw / sw); d[3] = wh * logf(th / sh);
-}
+using drn_box::box_target;  // (box_shared.h: drn_annot_box_reg forms its targets with the same code)
 
 __global__ __launch_bounds__(256) void boxreg_rows_kernel(BoxRegParams p, float* partial) {
   __shared__ float sh[256];
@@ -1088,17 +1081,8 @@ __global__ void apply_deltas_kernel(const float* deltas, long ld_d, const float*
   if (i >= (long)M * K) return;
   const int r = i / K, k = i - (long)r * K;
   const float x1 = boxes[4 * (long)r], y1 = boxes[4 * (long)r + 1], x2 = boxes[4 * (long)r + 2], y2 = boxes[4 * (long)r + 3];
-  const float w = x2 - x1, h = y2 - y1;
-  const float cx = x1 + 0.5f * w, cy = y1 + 0.5f * h;
-  float dx = 0.f, dy = 0.f, dw = 0.f, dh = 0.f;
-  if (deltas) {
-    const float* d = deltas + (long)r * ld_d + 4 * k;
-    dx = d[0] / wx; dy = d[1] / wy; dw = fminf(d[2] / ww, clampv); dh = fminf(d[3] / wh, clampv);
-  }
-  const float pcx = dx * w + cx, pcy = dy * h + cy;
-  const float pw = expf(dw) * w, ph = expf(dh) * h;
-  float* o = out + (long)r * 4 * K + 4 * k;
-  o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;
+  drn_box::decode_box(deltas ? deltas + (long)r * ld_d + 4 * k : nullptr, x1, y1, x2, y2, wx, wy, ww, wh, clampv,
+                      out + (long)r * 4 * K + 4 * k);
 }
 
 // p -= lr * (buf = mom*buf + (g + wd*p)); first step: buf = g + wd*p.  One launch over the flat parameter

@@ -5,6 +5,7 @@
 // annotated-box block: drn_label_proposals (roi_heads.py:256-353) and drn_mil_metrics (fast_rcnn.py:213-235) in front of
 // drn_metrics_record_annot.
 #include "drn_common.h"
+#include "box_shared.h"
 #include "../../include/drn_wsod.h"
 
 namespace {
@@ -116,10 +117,14 @@ __global__ __launch_bounds__(HM_THREADS) void head_metrics_kernel(const float* _
 // consecutive rows of ONE image, one thread per row, the image's annotated boxes and their areas in LDS (every lane reads the same
 // box: a broadcast).  fp32, the reference's operation order, no contraction (this file is built with -ffp-contract=off): the IoU
 // equals torch's bit for bit.  The three label counters go wave -> LDS -> one integer atomicAdd per non-zero counter and workgroup.
-enum { LP_THREADS = 256, LP_WAVES = LP_THREADS / 64, LP_MAX_GT = DRN_LABEL_MAX_GT };
+using drn_box::AnnotLds;
+using drn_box::LP_MAX_GT;
+using drn_box::LP_THREADS;
+using drn_box::LP_WAVES;
+using drn_box::MatcherArgs;
+static_assert(LP_MAX_GT == DRN_LABEL_MAX_GT, "box_shared.h and include/drn_wsod.h disagree");
 
-struct MatcherArgs { float thr[3]; int lab[4]; int nthr; };
-
+// (the staging of the boxes, the IoU and the Matcher are box_shared.h's: drn_annot_box_reg labels with the same code)
 __global__ __launch_bounds__(LP_THREADS) void label_proposals_kernel(const float* __restrict__ props,
                                                                      const int* __restrict__ img_off,
                                                                      const float* __restrict__ gt_boxes,
@@ -127,9 +132,7 @@ __global__ __launch_bounds__(LP_THREADS) void label_proposals_kernel(const float
                                                                      const int* __restrict__ gt_count, int max_gt, MatcherArgs a,
                                                                      int K, int M, int* __restrict__ labels,
                                                                      int* __restrict__ matched, int* __restrict__ counts) {
-  __shared__ float s_box[LP_MAX_GT][4];
-  __shared__ float s_area[LP_MAX_GT];
-  __shared__ int s_cls[LP_MAX_GT];
+  __shared__ AnnotLds s_ann;
   __shared__ int s_cnt[LP_WAVES][3];
   const int img = blockIdx.y;
   const int r0 = img_off[img], r1 = min(img_off[img + 1], M);
@@ -144,34 +147,10 @@ __global__ __launch_bounds__(LP_THREADS) void label_proposals_kernel(const float
     const f32x4_t b = *reinterpret_cast<const f32x4_t*>(props + 4 * (long)r);
     x1 = b[0]; y1 = b[1]; x2 = b[2]; y2 = b[3];
   }
-  for (int g = threadIdx.x; g < G; g += LP_THREADS) {
-    const float* gb = gt_boxes + ((long)img * max_gt + g) * 4;
-    const float gx1 = gb[0], gy1 = gb[1], gx2 = gb[2], gy2 = gb[3];
-    s_box[g][0] = gx1; s_box[g][1] = gy1; s_box[g][2] = gx2; s_box[g][3] = gy2;
-    s_area[g] = (gx2 - gx1) * (gy2 - gy1);
-    s_cls[g] = gt_classes[(long)img * max_gt + g];
-  }
+  drn_box::stage_annot(s_ann, gt_boxes, gt_classes, img, max_gt, G);
   __syncthreads();
-  const float a2 = (x2 - x1) * (y2 - y1);
-  float best = -1.f;  // every IoU is >= 0: box 0 is always taken, a later box only when strictly better (lowest index on ties)
-  int bg = 0;
-  for (int g = 0; g < G; ++g) {
-    const float iw = fmaxf(fminf(s_box[g][2], x2) - fmaxf(s_box[g][0], x1), 0.f);
-    const float ih = fmaxf(fminf(s_box[g][3], y2) - fmaxf(s_box[g][1], y1), 0.f);
-    const float inter = iw * ih;
-    const float iou = inter > 0.f ? inter / (s_area[g] + a2 - inter) : 0.f;
-    if (iou > best) { best = iou; bg = g; }
-  }
-  int cls = K;  // an image without annotated boxes: every row background, matched 0 (roi_heads.py:234-246)
-  if (G > 0) {
-    int ml = 1;  // Matcher: labels default 1, then per interval low <= v < high over [-inf, thr.., +inf]
-    for (int q = 0; q <= a.nthr; ++q) {
-      const float lo = q == 0 ? -INFINITY : a.thr[q - 1];
-      const float hi = q == a.nthr ? INFINITY : a.thr[q];
-      if (best >= lo && best < hi) ml = a.lab[q];
-    }
-    cls = ml == 0 ? K : ml == -1 ? -1 : s_cls[bg];
-  }
+  int bg;
+  const int cls = drn_box::label_row(s_ann, G, x1, y1, x2, y2, a, K, bg);
   if (live) {
     labels[r] = cls;
     matched[r] = bg;
@@ -283,13 +262,8 @@ int drn_label_proposals(const float* proposals, const int* img_off, int n_img, i
   if (!proposals || !img_off || !gt_boxes || !gt_classes || !gt_count || !thresholds || !match_labels || !labels || !matched ||
       !counts || ((uintptr_t)proposals & 15))
     return DRN_ERR_ARG;
-  MatcherArgs a = {};
-  a.nthr = nthr;
-  for (int q = 0; q < nthr; ++q) a.thr[q] = thresholds[q];
-  for (int q = 0; q <= nthr; ++q) {
-    a.lab[q] = match_labels[q];
-    if (a.lab[q] < -1 || a.lab[q] > 1) return DRN_ERR_ARG;
-  }
+  MatcherArgs a;
+  if (!drn_box::matcher_args(thresholds, match_labels, nthr, a)) return DRN_ERR_ARG;
   const dim3 grid((max_rows + LP_THREADS - 1) / LP_THREADS, n_img);
   hipLaunchKernelGGL(label_proposals_kernel, grid, dim3(LP_THREADS), 0, (hipStream_t)stream, proposals, img_off, gt_boxes,
                      gt_classes, gt_count, max_gt, a, K, M, labels, matched, counts);

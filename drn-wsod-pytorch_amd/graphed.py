@@ -85,9 +85,17 @@ class _StaticInputs:
         self.engine.captured_by = None  # weakref to the step whose captured graphs hold the engine's launch sequence
 
     def _annot_max_gt(self):
-        """max_gt of the metrics ring's annotated-box block, 0 without one"""
+        """annotated boxes per image in the label buffer: max_gt of the metrics ring's annotated-box block and / or the capacity
+        of a regressing PCL head (ONE block; ROIHeads._annot_capacity), 0 without either"""
+        cap = getattr(self.heads, "_annot_capacity", None)
+        if cap is not None:
+            return cap()
         m = self.engine.metrics
         return m.max_gt if m is not None and m.annotated else 0
+
+    def _annot_setter(self):
+        f = getattr(self.heads, "_annot_setter", None)
+        return (f(),) if f is not None else ()
 
     def _layout_labels(self):
         """image-level labels live in ONE device block (one H2D copy per step): [onehot f32 | classes i32 | count i32], and - only
@@ -166,7 +174,7 @@ class _StaticInputs:
         if self._ann_gt:  # the annotated boxes ride in the same pinned buffer and the same copy
             from .modeling.roi_heads import pack_annotated
 
-            buf[self._gt_words:].copy_(pack_annotated([x["instances"] for x in batch], self._ann_gt))
+            buf[self._gt_words:].copy_(pack_annotated([x["instances"] for x in batch], self._ann_gt, *self._annot_setter()))
         (self._gt_block if dst is None else dst).copy_(buf, non_blocking=True)
         slot["ev"] = torch.cuda.Event()
         slot["ev"].record()

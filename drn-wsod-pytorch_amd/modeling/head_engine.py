@@ -836,7 +836,8 @@ class _HeadEngine:
 
     def _losses_pcl(self, s):
         """PCLROIHeads (roi_heads_pcl.py:311-334): the MIL loss, then every branch's targets from the previous branch's
-        probabilities through proposal clustering; targets, loss and dlogits of all branches in three launches."""
+        probabilities through proposal clustering; targets, loss and dlogits of all branches in three launches.  Branches with
+        WSL.REFINE_REG add loss_box_reg_r{k} against the annotated boxes (one more launch pair)."""
         h = self.h
         w, col, gt, dl = s.w, s.col, s.gt, s.w["dlogits"]
         K, RK = h.num_classes, h.refine_K
@@ -847,8 +848,6 @@ class _HeadEngine:
         batches = self.pcl_image_batches
         if s.n_img != 1 and not batches:
             raise DrnError("PCL clusters the proposals of ONE image per step (third_party/pcl.py:94 asserts it)")
-        if any(h.refine_reg[:RK]):
-            raise DrnError("PCL with box regression branches is not on the built path (no reference config uses it)")
         rcols = [col["r%d" % k] for k in range(RK)]
         if batches:
             # PCLROIHeads.enable_image_batches(): one (branch, image) grid clusters every image; loss_cls_r{k} is the mean
@@ -864,10 +863,28 @@ class _HeadEngine:
             res = ops.pcl_refine(w["logits"], rcols, K, scores, gt["props"], adj, gt["onehot"].view(-1), dl)
             aux["targets"] = list(res)
             branch_loss = [r["loss"] for r in res]
+        # regressing branches (reg/pcl_* recipes; PCLOutputs.box_reg_loss, fast_rcnn.py:1746-1811): the proposals regress onto the
+        # matched ANNOTATED box - PCL never relabels against pseudo ground truth - and nothing feeds back into the clustering
+        # above.  Labelling, target, loss and dlogits of all such branches and all images: one launch pair (drn_annot_box_reg)
+        reg = [k for k in range(RK) if h.refine_reg[k]]
+        lreg = None
+        if reg:
+            if "ann_boxes" not in gt:
+                raise DrnError("a regressing PCL branch needs the annotated boxes in this step's labels (PCLROIHeads packs them; a "
+                               "graphed step lays its label buffer out before it is primed)")
+            pm = h.proposal_matcher
+            lreg = ops.annot_box_reg(w["logits"], [col["b%d" % k] for k in reg], K, gt["props"], s.img_off, s.n_img,
+                                     gt["ann_boxes"], gt["ann_classes"], gt["ann_count"], pm.thresholds[1:-1], pm.labels,
+                                     h.box_refinery[reg[0]].box2box_transform.weights, dlogits=dl, max_rows=gt.get("max_rows"))
         for k in range(RK):
             loss_names.append("loss_cls_r%d" % k)
             loss_list.append(branch_loss[k].view(()))
             head_cols.append(("r%d" % k, len(loss_list) - 1))
+            if h.refine_reg[k]:  # (right behind loss_cls_r{k}, as in the reference's dict)
+                i = reg.index(k)
+                loss_names.append("loss_box_reg_r%d" % k)
+                loss_list.append(lreg[i: i + 1].view(()))
+                head_cols.append(("b%d" % k, len(loss_list) - 1))
         # (no branch for the metrics: the reference logs no label accuracy for PCL)
         return self._finish(s, loss_names, [], loss_list=loss_list, head_cols=head_cols, aux=aux)
 

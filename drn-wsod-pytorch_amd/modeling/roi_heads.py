@@ -334,10 +334,11 @@ class ROIHeads(nn.Module):
         }
 
 
-def pack_annotated(targets, max_gt):
+def pack_annotated(targets, max_gt, setter="enable_metrics(max_gt=%d)"):
     """the annotated boxes of a step, packed on the host for the label upload: int32 words [boxes fp32 n_img * max_gt * 4 |
     classes n_img * max_gt | counts n_img] (views: annotated_views).  Feeds the un-suffixed logging scalars of the metrics ring
-    and no loss (roi_heads.py:256-353).  More than max_gt boxes in an image: DrnError - the length is known here, without a sync."""
+    (roi_heads.py:256-353) and the box regression of a regressing PCL branch.  More than max_gt boxes in an image: DrnError - the
+    length is known here, without a sync (`setter`: the call that sized the block, for the message)."""
     n_img = len(targets)
     words = torch.zeros((annotated_words(n_img, max_gt),), dtype=torch.int32)
     v = annotated_views(words, n_img, max_gt)
@@ -347,8 +348,8 @@ def pack_annotated(targets, max_gt):
         if b.shape[0] != c.shape[0]:
             raise DrnError("image %d: %d annotated boxes, %d classes" % (i, b.shape[0], c.shape[0]))
         if b.shape[0] > max_gt:
-            raise DrnError("image %d has %d annotated boxes, enable_metrics(max_gt=%d) holds at most %d: enable with a larger "
-                           "max_gt" % (i, b.shape[0], max_gt, max_gt))
+            raise DrnError("image %d has %d annotated boxes, %s holds at most %d: enable with a larger "
+                           "max_gt" % (i, b.shape[0], setter % max_gt, max_gt))
         v["ann_boxes"][i, : b.shape[0]] = b
         v["ann_classes"][i, : c.shape[0]] = c.to(torch.int32)
         v["ann_count"][i] = b.shape[0]
@@ -505,6 +506,15 @@ class OICRROIHeads(ROIHeads):
         eng.metrics = MetricsRing(slots, eng.arena_w.device, annotated, max_gt)
         return eng.metrics
 
+    def _annot_capacity(self):
+        """annotated boxes per image that a training step's label upload carries; 0 = none.  The metrics ring's annotated-box block
+        sizes it (enable_metrics(annotated=True, max_gt=)); PCLROIHeads with a regressing branch needs the block as well."""
+        ring = self._engine.metrics
+        return ring.max_gt if ring is not None and ring.annotated else 0
+
+    def _annot_setter(self):
+        return "enable_metrics(max_gt=%d)"
+
     def disable_metrics(self):
         """back to the launch sequence without metrics (eager steps at once; a primed graphed step keeps what it captured)"""
         self._engine.metrics = None
@@ -558,10 +568,10 @@ class OICRROIHeads(ROIHeads):
             gt = dict(onehot=oh.to(dev, non_blocking=True), classes=gcl.to(dev, non_blocking=True),
                       count=torch.tensor([len(g) for g in ints], dtype=torch.int32).to(dev, non_blocking=True),
                       props=self._take_props(rois), max_rows=max(nper), rows=nper)
-            ring = self._engine.metrics
-            if ring is not None and ring.annotated:  # the annotated boxes, packed on the host: one more small upload
-                words = pack_annotated(targets, ring.max_gt).to(dev, non_blocking=True)
-                gt.update(annotated_views(words, n_img, ring.max_gt))
+            cap = self._annot_capacity()
+            if cap:  # the annotated boxes (metrics ring and / or a regressing PCL branch: ONE block), packed on the host
+                words = pack_annotated(targets, cap, self._annot_setter()).to(dev, non_blocking=True)
+                gt.update(annotated_views(words, n_img, cap))
             losses, state = self._engine.forward(nhwc, rois, obj, True, off.to(dev, non_blocking=True), n_img, gt,
                                                  pooled=pooled)
             self.pred_class_img_logits = state["aux"]["img_scores"]
@@ -586,6 +596,18 @@ class OICRROIHeads(ROIHeads):
             probs = torch.zeros((sc.shape[0], K + 1), dtype=torch.float32, device=dev)
             probs[:, :K].copy_(sc)
             boxes = ops.apply_deltas(None, props, K, last.box2box_transform.weights)
+        elif self.refine_mode == "pcl":
+            # roi_heads_pcl.py:342-349 -> inference(pcl_bg=True): the mean softmax of ALL branches, background rotated to the last
+            # column, and the decode of the mean of ALL branches' deltas - a non-regressing branch contributes zeros
+            # (fast_rcnn.py:1377-1386), so the regressing branches' deltas are divided by REFINE_NUM; the boxes stay in true
+            # class order (fast_rcnn.py:1465).  Not OICR's rule below (last branch, undivided).
+            probs = ops.mean_softmax(w["logits"], [col["r%d" % k] for k in heads], K + 1, bg_first=True)
+            reg = [k for k in heads if self.refine_reg[k]]
+            if reg:
+                boxes = ops.apply_deltas_mean(w["logits"], [col["b%d" % k] for k in reg], self.refine_K, props, K,
+                                              last.box2box_transform.weights)
+            else:
+                boxes = ops.apply_deltas(None, props, K, last.box2box_transform.weights)
         elif self.refine_reg[-1]:
             probs, _ = ops.softmax_ce(w["logits"], col["r%d" % heads[-1]], K + 1)
             boxes = ops.apply_deltas(w["logits"], props, K, last.box2box_transform.weights, col0=col["b%d" % heads[-1]])
@@ -623,6 +645,57 @@ class PCLROIHeads(OICRROIHeads):
     (csrc/pcl.hip)."""
 
     refine_mode = "pcl"
+    ANNOT_MAX_GT = 64    # annotated boxes per image of a regressing branch's label upload, unless set_annotated_capacity() says else
+    _annot_cap = None    # what set_annotated_capacity() set
+
+    @property
+    def regresses(self):
+        """a branch with WSL.REFINE_REG (the reg/pcl_* recipes): box regression onto the ANNOTATED boxes"""
+        return any(self.refine_reg[: self.refine_K])
+
+    def set_annotated_capacity(self, max_gt):
+        """Annotated boxes per image that the label upload of a regressing head holds (default ANNOT_MAX_GT = 64; an image with more
+        raises DrnError on the host).  ONE RULE: with the metrics ring's annotated-box block on (enable_metrics(annotated=True,
+        max_gt=)) the ring's max_gt is the capacity - the regression and the ring read one block, uploaded once - and a capacity
+        set here that differs from it is refused; without the block the capacity set here (else the default) holds.  A graphed
+        step lays its label buffer out when it is primed, so this has to come first."""
+        from .. import ops
+
+        if not 1 <= int(max_gt) <= ops.LABEL_MAX_GT:
+            raise DrnError("set_annotated_capacity(%d): 1 .. %d annotated boxes per image are built" % (max_gt, ops.LABEL_MAX_GT))
+        owner = self._engine.captured_by
+        if int(max_gt) != self._annot_capacity_quiet() and owner is not None and owner() is not None:
+            raise DrnError("set_annotated_capacity() after a graphed step was primed: its label buffer is laid out.  Order: "
+                           "set_annotated_capacity(), then create and prime the GraphedTrainStep / GraphedFullStep")
+        self._annot_cap = int(max_gt)
+        self._annot_capacity()  # (refuses a contradiction with the ring at once)
+        return self
+
+    def _annot_capacity_quiet(self):
+        try:
+            return self._annot_capacity()
+        except DrnError:
+            return -1
+
+    def _annot_capacity(self):
+        ring_gt = super()._annot_capacity()
+        if not self.regresses:
+            return ring_gt
+        if self.proposal_append_gt:
+            raise DrnError("PCLROIHeads with a regressing branch and MODEL.ROI_HEADS.PROPOSAL_APPEND_GT = True: appending the "
+                           "annotated boxes to the proposals is not built (every shipped reg/pcl recipe sets it False)")
+        if ring_gt:
+            if self._annot_cap is not None and self._annot_cap != ring_gt:
+                raise DrnError("set_annotated_capacity(%d) contradicts enable_metrics(annotated=True, max_gt=%d): with the "
+                               "annotated-box block on, the ring's max_gt is the capacity" % (self._annot_cap, ring_gt))
+            return ring_gt
+        return self._annot_cap if self._annot_cap is not None else self.ANNOT_MAX_GT
+
+    def _annot_setter(self):
+        ring = self._engine.metrics
+        if ring is not None and ring.annotated:
+            return "enable_metrics(max_gt=%d)"
+        return "PCLROIHeads.set_annotated_capacity(%d)"
 
     @property
     def image_batches(self):

@@ -871,6 +871,56 @@ def apply_deltas(deltas, boxes, K, weights=(10.0, 10.0, 5.0, 5.0), col0=0):
     return out
 
 
+BOXREG_MAX_HEADS, BOXREG_MAX_IMAGES = 8, 16  # include/drn_wsod.h
+
+
+def apply_deltas_mean(logits, col0s, n_total, boxes, K, weights=(10.0, 10.0, 5.0, 5.0)):
+    """drn_apply_deltas_mean: boxes decoded from the mean of n_total branches' deltas, of which the branches at columns `col0s`
+    (ascending; may be empty) regress and the others contribute zeros (PCLROIHeads' inference, predict_boxes_K) -> [M, 4K]."""
+    M = boxes.shape[0]
+    out = torch.empty((M, 4 * K), dtype=torch.float32, device=boxes.device)
+    w, cz = C.host_floats(weights), C.host_ints(col0s)
+    C.call("drn_apply_deltas_mean", C.ptr(logits) if len(col0s) else None, _2d(logits) if len(col0s) else 0,
+           ctypes.cast(cz, ctypes.c_void_p), len(col0s), int(n_total), C.ptr(boxes), C.ptr(out), M, K,
+           ctypes.cast(w, ctypes.c_void_p), float(SCALE_CLAMP), C.stream())
+    return out
+
+
+def annot_box_reg(logits, col0s, K, props, img_off, n_img, gt_boxes, gt_classes, gt_count, thresholds=(0.5,), labels=(0, 1),
+                  weights=(10.0, 10.0, 5.0, 5.0), dlogits=None, loss_scale=1.0, max_rows=None, want_labels=False):
+    """drn_annot_box_reg: loss_box_reg of the regressing PCL branches at delta columns `col0s` against the ANNOTATED boxes (the
+    label_proposals() labelling, get_deltas targets, L1 / M_i, mean over the images), fused with its dlogits - one launch pair for
+    all branches and images.  -> loss fp32 [len(col0s)], or (loss, labels, matched) with want_labels.  No synchronisation;
+    capturable."""
+    M, dev = props.shape[0], props.device
+    max_gt, nthr, nh = gt_classes.shape[1], len(thresholds), len(col0s)
+    if (max_gt > LABEL_MAX_GT or not 1 <= nthr <= 3 or len(labels) != nthr + 1 or not 1 <= nh <= BOXREG_MAX_HEADS or
+            n_img > BOXREG_MAX_IMAGES):
+        raise C.DrnError("annot_box_reg(): max_gt %d, %d thresholds, %d labels, %d branches, %d images (at most %d boxes per image, "
+                         "1 .. 3 thresholds and one label more, 1 .. %d branches, %d images are built)"
+                         % (max_gt, nthr, len(labels), nh, n_img, LABEL_MAX_GT, BOXREG_MAX_HEADS, BOXREG_MAX_IMAGES))
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] >= M
+    assert props.dtype == torch.float32 and props.dim() == 2 and props.shape[1] == 4 and props.is_contiguous()
+    assert img_off.dtype == torch.int32 and img_off.numel() == n_img + 1 and img_off.is_contiguous()
+    assert gt_boxes.dtype == torch.float32 and gt_boxes.shape == (n_img, max_gt, 4) and gt_boxes.is_contiguous()
+    assert gt_classes.dtype == torch.int32 and gt_classes.shape == (n_img, max_gt) and gt_classes.is_contiguous()
+    assert gt_count.dtype == torch.int32 and gt_count.numel() == n_img and gt_count.is_contiguous()
+    if dlogits is not None:
+        assert dlogits.dtype == torch.float32 and dlogits.dim() == 2 and dlogits.stride(1) == 1 and dlogits.shape[0] >= M
+    max_rows = int(max_rows or M)
+    loss = torch.zeros((nh,), dtype=torch.float32, device=dev)
+    scratch = torch.empty((max(1, nh * n_img * ((max_rows + 255) // 256)),), dtype=torch.float32, device=dev)
+    lab = torch.empty((M,), dtype=torch.int32, device=dev) if want_labels else None
+    mat = torch.empty((M,), dtype=torch.int32, device=dev) if want_labels else None
+    th, lb, w, cz = C.host_floats(thresholds), C.host_ints(labels), C.host_floats(weights), C.host_ints(col0s)
+    C.call("drn_annot_box_reg", C.ptr(logits), _2d(logits), ctypes.cast(cz, ctypes.c_void_p), nh, int(K), C.ptr(props),
+           C.ptr(img_off), int(n_img), M, max_rows, C.ptr(gt_boxes), C.ptr(gt_classes), C.ptr(gt_count), max_gt,
+           ctypes.cast(th, ctypes.c_void_p), ctypes.cast(lb, ctypes.c_void_p), nthr, ctypes.cast(w, ctypes.c_void_p),
+           C.ptr(dlogits), _2d(dlogits) if dlogits is not None else 0, float(loss_scale), C.ptr(loss), C.ptr(lab), C.ptr(mat),
+           C.ptr(scratch), C.stream())
+    return (loss, lab, mat) if want_labels else loss
+
+
 def sum_small(x, scale=1.0):
     out = torch.empty((1,), dtype=torch.float32, device=x.device)
     C.call("drn_sum_small", C.ptr(x), x.numel(), float(scale), C.ptr(out), C.stream())

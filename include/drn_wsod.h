@@ -502,6 +502,51 @@ int drn_apply_deltas(const float* deltas, long ld_d, const float* boxes, float* 
 
 int drn_sum_small(const float* in, int n, float scale, float* out, void* stream);
 
+/* ---- box regression of the PCL heads (reg/pcl_* recipes) ------------------------------------------
+ * PCLROIHeads labels its proposals against the ANNOTATED boxes (roi_heads_pcl.py:233-235 -> roi_heads.py:214-353: pairwise_iou,
+ * Matcher, no sampling) and never relabels them against pseudo ground truth, so a regressing PCL branch (WSL.REFINE_REG[k])
+ * regresses onto the matched annotated box (PCLOutputs.box_reg_loss, fast_rcnn.py:1746-1811): restated as it is.
+ *
+ * drn_annot_box_reg: labelling, target, loss and gradient of n_heads (1 .. DRN_BOXREG_MAX_HEADS) regressing branches and n_img
+ * images in one launch pair.  logits = fp32 [M, ld]; col0s_host = HOST array of the branches' first delta column (their 4K deltas
+ * are columns col0 .. col0 + 4K, class c in TRUE class indexing at 4c .. 4c + 3); proposals, img_off, gt_boxes, gt_classes,
+ * gt_count, max_gt, thresholds, match_labels, nthr, K, max_rows: exactly drn_label_proposals' (below), and labels / matched
+ * (each optional, int32 [M]) are BIT-EQUAL to what that entry writes for the same inputs - the same device code labels here.
+ * weights4_host = Box2BoxTransform's four weights.  Per image i with M_i rows, fg = {r : 0 <= labels[r] < K}:
+ *   t_r   = Box2BoxTransform.get_deltas(proposal r, annotated box matched[r] of image i)       (fp32, drn_box_reg_loss' order)
+ *   L_i,h = (sum_fg-rows sum_e |logits[r, col0_h + 4 labels[r] + e] - t_r[e]|) / M_i
+ * with the row sums, the 256-row tree and the ascending combine of drn_box_reg_loss; an image without rows contributes 0.
+ *   loss[h] = L_0,h for one image, else the mean over the images: an fp64 sum in ascending image order, rounded to fp32 once
+ *             (drn_pcl_refine_batch's definition)
+ *   dlogits[r, col0_h + 4 labels[r] + e] = sign(pred - t) / M_i * (1.f / n_img) * loss_scale on fg rows, 0 in every other of the 4K
+ *             columns of every row (dlogits optional; fp32 [M, ld_d]); for n_img == 1 bit-equal to drn_box_reg_loss fed with
+ *             labels and the gathered matched boxes.
+ * 256 rows of ONE image per workgroup, the image's boxes in LDS, the gradient block stored with the lanes along the columns; the
+ * per-workgroup partial sums go to scratch = fp32 [n_heads * n_img * ceil(max_rows / 256)] and are combined in a fixed order.  No
+ * atomics, no host sync, capturable.  loss = fp32 [n_heads].
+ * Shape class: 0 <= n_img <= DRN_BOXREG_MAX_IMAGES, M >= 0, 1 <= max_gt <= DRN_LABEL_MAX_GT, 1 <= nthr <= 3, 1 <= n_heads <=
+ * DRN_BOXREG_MAX_HEADS, 1 <= K <= DRN_BOXREG_MAX_K (n_img, M or max_rows == 0: no launch, nothing is written).
+ * Errors: DRN_ERR_UNSUPPORTED (above the class), DRN_ERR_ARG (null / misaligned pointer, sizes, columns outside ld / ld_d, a Matcher
+ * label outside {-1, 0, 1}).
+ *
+ * drn_apply_deltas_mean: OICROutputLayers.predict_boxes_K (fast_rcnn.py:1534-1559) as PCLROIHeads' inference uses it
+ * (roi_heads_pcl.py:342-349): the deltas of ALL n_total = WSL.REFINE_NUM branches are averaged - a non-regressing branch
+ * contributes zeros (fast_rcnn.py:1377-1386) - and decoded, in true class order (no pcl_bg rotation, :1465).  col0s_host = HOST
+ * array of the n_heads (0 .. DRN_BOXREG_MAX_HEADS) REGRESSING branches' first delta columns, ascending.  Per element
+ *   d = ((+0.0f + d_k0) + d_k1 + ...) / (float)n_total            (IEEE division)
+ * then drn_apply_deltas' decode of d, by the same device function: bit-equal to drn_apply_deltas on that d.  n_heads == 0 is the
+ * zero-delta decode (drn_apply_deltas with deltas == NULL).  out = fp32 [M, 4K]. */
+#define DRN_BOXREG_MAX_HEADS 8
+#define DRN_BOXREG_MAX_IMAGES 16
+#define DRN_BOXREG_MAX_K 4096
+int drn_annot_box_reg(const float* logits, long ld, const int* col0s_host, int n_heads, int K, const float* proposals,
+                      const int* img_off, int n_img, int M, int max_rows, const float* gt_boxes, const int* gt_classes,
+                      const int* gt_count, int max_gt, const float* thresholds, const int* match_labels, int nthr,
+                      const float* weights4_host, float* dlogits, long ld_d, float loss_scale, float* loss, int* labels,
+                      int* matched, float* scratch, void* stream);
+int drn_apply_deltas_mean(const float* logits, long ld, const int* col0s_host, int n_heads, int n_total, const float* boxes,
+                          float* out, int M, int K, const float* weights4_host, float scale_clamp, void* stream);
+
 /* ---- optimizer ------------------------------------------------------------------------------- */
 
 /* torch.optim.SGD(momentum) with the per-parameter groups of detectron2/solver/build.py:93-137, applied to a
