@@ -93,6 +93,10 @@ _SIGS = {
     "drn_csc_cpg": "piiiiippp",
     "drn_csc_weights": "piifpipiiifppp",
     "drn_csc_loss": "pliiiippppiiipplp",
+    "drn_csc_seed_batch": "pliiippp" + "iip" + "plp",
+    "drn_csc_cpg_batch": "piii" + "iiippip" + "ppp",
+    "drn_csc_weights_batch": "pppiiil" + "ppi" + "f" + "ppipi" + "if" + "ppp",
+    "drn_csc_loss_batch": "pliiipppp" + "piii" + "ppplp",
     "drn_trunk_shapes": "p" + "iiiiiiii" + "pp",
     "drn_trunk_forward": "piiip" + "iiiii" + "p",
 }

@@ -6,6 +6,8 @@
 //   drn_csc_loss      the two weighted image-level BCE losses and d loss / d logits through the WSDDN score product,
 //                     or (mode 1) d (sum_r score[r, c*]) / d logits, the seed of the image-gradient pass
 //                                                                           fast_rcnn.py:887-931, roi_heads_csc.py:441-455
+//   drn_csc_{seed,cpg,weights,loss}_batch   the same bodies per image / per (image, class) pair of an image batch
+//                     (CSCROIHeads.enable_image_batches; the definition is this package's, include/drn_wsod.h)
 // The reference runs the table, the normalisation and the blend on the HOST (three device<->host copies per class and
 // a cudaDeviceSynchronize); here everything stays on the stream.  Integer / index work (threshold, counts, rounded box
 // corners) is bit-exact with oracle/csc_ops.c; this file builds with -ffp-contract=off, and `/` / sqrtf() are the
@@ -13,6 +15,7 @@
 #include <float.h>
 
 #include "drn_common.h"
+#include "../../include/drn_wsod.h"
 
 namespace {
 
@@ -44,11 +47,8 @@ __global__ __launch_bounds__(256) void csc_scale_kernel(float* map, long npx, co
 // ---- thresholded summed-area table --------------------------------------------------------------------------------
 // rows: one workgroup per row, every thread counts a contiguous run, block scan of the run counts, second sweep writes
 // the running count.  columns: one thread per column.  Counts are integers < 2^24, so fp32 adds are exact in any order.
-__global__ __launch_bounds__(256) void csc_rowscan_kernel(const float* cpg, float* table, int W, float thr) {
-  __shared__ int sc[256];
-  const int y = blockIdx.x, tid = threadIdx.x;
-  const float* src = cpg + (long)y * W;
-  float* dst = table + (long)y * W;
+__device__ __forceinline__ void csc_rowscan_row(const float* src, float* dst, int W, float thr, int* sc) {
+  const int tid = threadIdx.x;
   const int per = (W + 255) / 256, x0 = min(W, tid * per), x1 = min(W, x0 + per);
   int cnt = 0;
   for (int x = x0; x < x1; ++x) cnt += src[x] >= thr ? 1 : 0;
@@ -65,6 +65,12 @@ __global__ __launch_bounds__(256) void csc_rowscan_kernel(const float* cpg, floa
     run += src[x] >= thr ? 1 : 0;
     dst[x] = (float)run;
   }
+}
+
+__global__ __launch_bounds__(256) void csc_rowscan_kernel(const float* cpg, float* table, int W, float thr) {
+  __shared__ int sc[256];
+  const int y = blockIdx.x;
+  csc_rowscan_row(cpg + (long)y * W, table + (long)y * W, W, thr, sc);
 }
 
 __global__ __launch_bounds__(256) void csc_colscan_kernel(float* table, int H, int W) {
@@ -149,10 +155,9 @@ __device__ __forceinline__ float csc_block_reduce(float v, float* red) {
   return red[0];
 }
 
-__global__ __launch_bounds__(CSC_T) void csc_pool_kernel(const float* table, int H, int W, const float* rois, int M,
-                                                         const float* scores, int K, int c, int area_sqrt,
-                                                         float context_scale, float* Wout) {
-  __shared__ float red[CSC_T];
+__device__ __forceinline__ void csc_pool_body(const float* table, int H, int W, const float* rois, int M,
+                                              const float* scores, int K, int c, int area_sqrt, float context_scale,
+                                              float* Wout, float* red) {
   const int tid = threadIdx.x;
   float vmax = 0.f, vmin = 0.f, ssum = 0.f;
   for (int r = tid; r < M; r += CSC_T) {
@@ -178,6 +183,13 @@ __global__ __launch_bounds__(CSC_T) void csc_pool_kernel(const float* table, int
   }
 }
 
+__global__ __launch_bounds__(CSC_T) void csc_pool_kernel(const float* table, int H, int W, const float* rois, int M,
+                                                         const float* scores, int K, int c, int area_sqrt,
+                                                         float context_scale, float* Wout) {
+  __shared__ float red[CSC_T];
+  csc_pool_body(table, H, W, rois, M, scores, K, c, area_sqrt, context_scale, Wout, red);
+}
+
 // ---- losses / seeds through the WSDDN product s[r,c] = softmax_c(cls)[r,c] * softmax_r(det)[r,c] -------------------
 struct CscLossParams {
   const float* logits; long ld; int c_cls, c_det, K, M;
@@ -186,10 +198,11 @@ struct CscLossParams {
   float* loss; float* dlogits; long ld_d;
 };
 
-template <int LPR>
-__global__ __launch_bounds__(CSC_T) void csc_loss_kernel(CscLossParams p) {
-  constexpr int RPP = CSC_T / LPR, CPL = LPR == 64 ? 2 : 1, NC = LPR * CPL;
-  __shared__ float red[RPP][NC];
+// SCALE: `dscale` multiplies every dlogits entry once more (drn_csc_loss_batch: 1.f / n_img; its seed mode: 1.f, exact)
+template <int LPR, bool SCALE>
+__device__ __forceinline__ void csc_loss_body(const CscLossParams& p, float dscale,
+                                              float (*red)[LPR * (LPR == 64 ? 2 : 1)]) {
+  constexpr int RPP = CSC_T / LPR, CPL = LPR == 64 ? 2 : 1;
   const int l = threadIdx.x % LPR, ph = threadIdx.x / LPR, K = p.K, M = p.M;
   int col[CPL];
   bool ok[CPL];
@@ -285,10 +298,195 @@ __global__ __launch_bounds__(CSC_T) void csc_loss_kernel(CscLossParams p) {
     for (int j = 0; j < CPL; ++j)
       if (ok[j]) {
         const float b = expf(p.logits[(long)r * p.ld + p.c_det + col[j]] - cmax[j]) / csum[j];
-        p.dlogits[(long)r * p.ld_d + p.c_cls + col[j]] = gs[j] - p.rowsm[(long)r * K + col[j]] * dot;
-        p.dlogits[(long)r * p.ld_d + p.c_det + col[j]] = gs[j] - b * T[j];
+        const float dc = gs[j] - p.rowsm[(long)r * K + col[j]] * dot, dd = gs[j] - b * T[j];
+        p.dlogits[(long)r * p.ld_d + p.c_cls + col[j]] = SCALE ? dc * dscale : dc;
+        p.dlogits[(long)r * p.ld_d + p.c_det + col[j]] = SCALE ? dd * dscale : dd;
       }
   }
+}
+
+template <int LPR>
+__global__ __launch_bounds__(CSC_T) void csc_loss_kernel(CscLossParams p) {
+  __shared__ float red[CSC_T / LPR][LPR * (LPR == 64 ? 2 : 1)];
+  csc_loss_body<LPR, false>(p, 1.f, red);
+}
+
+// ---- image batches (CSCROIHeads.enable_image_batches; the definition is in include/drn_wsod.h) ----------------------
+// Every kernel below runs the single-image body above on one image's rows / one image's crop, so its results are the
+// single-image entry's bit for bit.  What the host cannot see (a row range, a size or a class read from device memory
+// that is out of range) skips the image or the pair: nothing of it is written.
+struct CscBatchLossParams {
+  CscLossParams p;         // pointers of the whole batch, M = all rows; onehot [n_img][K]
+  const int* img_off;      // [n_img + 1]
+  const long* slot_cls;    // mode 1: class of each image in this slot, -1 = none
+  float* loss_img;         // mode 0: [n_img][2]
+  int n_img;
+};
+
+template <int LPR>
+__global__ __launch_bounds__(CSC_T) void csc_loss_batch_kernel(CscBatchLossParams q) {
+  __shared__ float red[CSC_T / LPR][LPR * (LPR == 64 ? 2 : 1)];
+  const int i = blockIdx.x;
+  CscLossParams p = q.p;
+  const int o0 = q.img_off[i], o1 = q.img_off[i + 1], K = p.K;
+  if (o0 < 0 || o1 > p.M || o1 <= o0) {
+    if (p.mode == 0 && threadIdx.x < 2) q.loss_img[2 * i + threadIdx.x] = __int_as_float(0x7fc00000);  // NaN: the mean shows it
+    return;
+  }
+  p.M = o1 - o0;
+  p.logits += (long)o0 * p.ld;
+  p.scores += (long)o0 * K;
+  p.rowsm += (long)o0 * K;
+  if (p.W) p.W += (long)o0 * K;
+  if (p.dlogits) p.dlogits += (long)o0 * p.ld_d;
+  float dscale = 1.f;
+  if (p.mode == 1) {
+    const long c = q.slot_cls[i];
+    if (c < 0 || c >= K) {  // no class in this slot: the d/dx pass carries an exact zero for the image
+      for (long e = threadIdx.x; e < (long)p.M * K; e += CSC_T) {
+        const long r = e / K;
+        const int k = (int)(e - r * K);
+        p.dlogits[r * p.ld_d + p.c_cls + k] = 0.f;
+        p.dlogits[r * p.ld_d + p.c_det + k] = 0.f;
+      }
+      return;
+    }
+    p.cstar = (int)c;
+  } else {
+    p.onehot += (long)i * K;
+    p.loss = q.loss_img + 2 * i;
+    dscale = 1.f / (float)q.n_img;
+  }
+  csc_loss_body<LPR, true>(p, dscale, red);
+}
+
+// loss[j] = (float)((sum over images i, ascending, of (double)loss_img[i][j]) / n): one thread per loss, fixed order
+__global__ __launch_bounds__(64) void csc_batch_mean_kernel(const float* loss_img, float* loss, int n_img) {
+  const int j = threadIdx.x;
+  if (j >= 2) return;
+  double acc = 0.0;
+  for (int i = 0; i < n_img; ++i) acc += (double)loss_img[2 * i + j];
+  loss[j] = (float)(acc / (double)n_img);
+}
+
+struct CscCpgBatchParams {
+  const void* dimg;        // [n_img][Hmax][Wmax][cpad]
+  int cpad, C, n_img, Hmax, Wmax, K;
+  const long* hw;          // [n_img][2]
+  const long* slot_cls;    // [n_img]
+  const long* map_off;     // [n_img]: image i's [K][H_i][W_i] block of `maps`, in floats
+  float* maps;
+  unsigned* gmax;          // [n_img]
+};
+
+// the map of image i's slot class and its crop -> false: nothing to do for this image
+__device__ __forceinline__ bool csc_cpg_image(const CscCpgBatchParams& q, int i, int& H, int& W, float*& map) {
+  const long c = q.slot_cls[i];
+  H = (int)q.hw[2 * i];
+  W = (int)q.hw[2 * i + 1];
+  if (c < 0 || c >= q.K || H < 1 || W < 1 || H > q.Hmax || W > q.Wmax) return false;
+  map = q.maps + q.map_off[i] + c * (long)H * W;
+  return true;
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void csc_absmax_batch_kernel(CscCpgBatchParams q) {
+  using E = ElemOf<DT>;
+  const int i = blockIdx.y;
+  int H, W;
+  float* map;
+  if (!csc_cpg_image(q, i, H, W, map)) return;
+  const long npx = (long)H * W;
+  const typename E::type* img = (const typename E::type*)q.dimg + (long)i * q.Hmax * q.Wmax * q.cpad;
+  float best = 0.f;
+  for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
+    const long y = px / W, x = px - y * W;  // the crop: rows beyond H and columns beyond W of the padded tensor are never read
+    const typename E::type* p = img + (y * q.Wmax + x) * q.cpad;
+    float m = fabsf(E::ld(p));
+    for (int c = 1; c < q.C; ++c) m = fmaxf(m, fabsf(E::ld(p + c)));
+    map[px] = m;
+    best = fmaxf(best, m);
+  }
+  best = wave_max(best);
+  if ((threadIdx.x & 63) == 0) atomicMax(q.gmax + i, __float_as_uint(best));  // max is exact in any order
+}
+
+__global__ __launch_bounds__(256) void csc_scale_batch_kernel(CscCpgBatchParams q) {
+  const int i = blockIdx.y;
+  int H, W;
+  float* map;
+  if (!csc_cpg_image(q, i, H, W, map)) return;
+  const long npx = (long)H * W;
+  const float mx = __uint_as_float(q.gmax[i]);
+  for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x)
+    map[px] = map[px] / mx;
+}
+
+struct CscPairParams {
+  const float* maps; const long* map_off; const long* hw; const long* pairs; const long* tab_off;
+  float* tables;
+  int n_img, K, Hmax, Wmax, M;
+  const int* img_off;
+};
+
+// pair p = (image, class) -> false: skipped
+__device__ __forceinline__ bool csc_pair(const CscPairParams& q, int p, int& i, int& c, int& H, int& W) {
+  const long li = q.pairs[2 * p], lc = q.pairs[2 * p + 1];
+  if (li < 0 || li >= q.n_img || lc < 0 || lc >= q.K) return false;
+  i = (int)li;
+  c = (int)lc;
+  H = (int)q.hw[2 * i];
+  W = (int)q.hw[2 * i + 1];
+  return H >= 1 && W >= 1 && H <= q.Hmax && W <= q.Wmax;
+}
+
+// grid (Hmax, pairs): one workgroup per (row, pair), the single-image row scan
+__global__ __launch_bounds__(256) void csc_rowscan_batch_kernel(CscPairParams q, float thr) {
+  __shared__ int sc[256];
+  int i, c, H, W;
+  if (!csc_pair(q, blockIdx.y, i, c, H, W)) return;
+  const int y = blockIdx.x;
+  if (y >= H) return;
+  const float* map = q.maps + q.map_off[i] + (long)c * H * W;
+  csc_rowscan_row(map + (long)y * W, q.tables + q.tab_off[blockIdx.y] + (long)y * W, W, thr, sc);
+}
+
+// grid (ceil(Wmax / 64), pairs): 64 columns x 16 row segments per workgroup.  Every thread sums its segment of its column,
+// the 16 segment sums of a column are prefix-added through LDS, a second sweep writes the running count.  Integer counts
+// < 2^24 in fp32: exact in any order, so the table is csc_colscan_kernel's.
+__global__ __launch_bounds__(CSC_T) void csc_colscan_batch_kernel(CscPairParams q) {
+  constexpr int SEG = CSC_T / 64;
+  __shared__ float part[SEG][64];
+  int i, c, H, W;
+  if (!csc_pair(q, blockIdx.y, i, c, H, W)) return;
+  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6, x = blockIdx.x * 64 + lane;
+  if (blockIdx.x * 64 >= W) return;  // (the whole workgroup: no barrier is left behind)
+  float* t = q.tables + q.tab_off[blockIdx.y];
+  const int per = (H + SEG - 1) / SEG, y0 = min(H, seg * per), y1 = min(H, y0 + per);
+  float acc = 0.f;
+  if (x < W)
+    for (int y = y0; y < y1; ++y) acc += t[(long)y * W + x];
+  part[seg][lane] = acc;
+  __syncthreads();
+  acc = 0.f;
+  for (int s = 0; s < seg; ++s) acc += part[s][lane];
+  if (x < W)
+    for (int y = y0; y < y1; ++y) {
+      acc += t[(long)y * W + x];
+      t[(long)y * W + x] = acc;
+    }
+}
+
+// grid (pairs): csc_pool_kernel on the rows of the pair's image, its boxes clamped to the image's own (H_i, W_i)
+__global__ __launch_bounds__(CSC_T) void csc_pool_batch_kernel(CscPairParams q, const float* rois, const float* scores,
+                                                               int area_sqrt, float context_scale, float* Wout) {
+  __shared__ float red[CSC_T];
+  int i, c, H, W;
+  if (!csc_pair(q, blockIdx.x, i, c, H, W)) return;
+  const int o0 = q.img_off[i], o1 = q.img_off[i + 1];
+  if (o0 < 0 || o1 > q.M || o1 <= o0) return;
+  csc_pool_body(q.tables + q.tab_off[blockIdx.x], H, W, rois + 5 * (long)o0, o1 - o0, scores + (long)o0 * q.K, q.K, c,
+                area_sqrt, context_scale, Wout + (long)o0 * q.K, red);
 }
 
 }  // namespace
@@ -344,6 +542,87 @@ int drn_csc_loss(const float* logits, long ld, int c_cls, int c_det, int K, int 
     hipLaunchKernelGGL((csc_loss_kernel<32>), dim3(1), dim3(CSC_T), 0, st, p);
   else
     hipLaunchKernelGGL((csc_loss_kernel<64>), dim3(1), dim3(CSC_T), 0, st, p);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// ---- image batches: see "CSC on image batches" in include/drn_wsod.h ----
+static int csc_batch_limits(int n_img, int K) {
+  if (n_img < 1 || K < 1) return DRN_ERR_ARG;
+  if (n_img > DRN_CSC_MAX_IMAGES || K > 128) return DRN_ERR_UNSUPPORTED;
+  return DRN_OK;
+}
+
+int drn_csc_seed_batch(const float* logits, long ld, int c_cls, int c_det, int K, const float* scores,
+                       const float* row_softmax, const int* img_off, int n_img, int M, const long* slot_cls,
+                       float* dlogits, long ld_d, void* stream) {
+  if (const int rc = csc_batch_limits(n_img, K)) return rc;
+  if (!logits || !scores || !row_softmax || !img_off || !slot_cls || !dlogits || M < n_img) return DRN_ERR_ARG;
+  CscBatchLossParams q{};
+  q.p = CscLossParams{logits, ld, c_cls, c_det, K, M, scores, row_softmax, nullptr, nullptr, 1, 0, 0, nullptr, dlogits, ld_d};
+  q.img_off = img_off; q.slot_cls = slot_cls; q.loss_img = nullptr; q.n_img = n_img;
+  hipStream_t st = (hipStream_t)stream;
+  if (K <= 32)
+    hipLaunchKernelGGL((csc_loss_batch_kernel<32>), dim3(n_img), dim3(CSC_T), 0, st, q);
+  else
+    hipLaunchKernelGGL((csc_loss_batch_kernel<64>), dim3(n_img), dim3(CSC_T), 0, st, q);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+int drn_csc_cpg_batch(const void* dimg, int dtype, int cpad, int C, int n_img, int Hmax, int Wmax, const long* hw,
+                      const long* slot_cls, int K, const long* map_off, float* maps, void* scratch, void* stream) {
+  if (const int rc = csc_batch_limits(n_img, K)) return rc;
+  if (!dimg || !hw || !slot_cls || !map_off || !maps || !scratch || C < 1 || C > cpad || Hmax < 1 || Wmax < 1) return DRN_ERR_ARG;
+  if (dtype != DRN_F32 && dtype != DRN_BF16) return DRN_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(scratch, 0, 4 * (size_t)n_img, st) != hipSuccess) return DRN_ERR_LAUNCH;
+  const long npx = (long)Hmax * Wmax;
+  const dim3 grid((unsigned)((npx + 255) / 256 < 2048 ? (npx + 255) / 256 : 2048), (unsigned)n_img);
+  CscCpgBatchParams q{dimg, cpad, C, n_img, Hmax, Wmax, K, hw, slot_cls, map_off, maps, (unsigned*)scratch};
+  if (dtype == DRN_F32)
+    hipLaunchKernelGGL((csc_absmax_batch_kernel<DRN_F32>), grid, dim3(256), 0, st, q);
+  else
+    hipLaunchKernelGGL((csc_absmax_batch_kernel<DRN_BF16>), grid, dim3(256), 0, st, q);
+  hipLaunchKernelGGL(csc_scale_batch_kernel, grid, dim3(256), 0, st, q);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+int drn_csc_weights_batch(const float* maps, const long* map_off, const long* hw, int n_img, int Hmax, int Wmax,
+                          long max_px, const long* pairs, const long* tab_off, int n_pairs, float fg_threshold,
+                          const float* rois, const int* img_off, int M, const float* scores, int K, int area_sqrt,
+                          float context_scale, float* tables, float* Wout, void* stream) {
+  if (const int rc = csc_batch_limits(n_img, K)) return rc;
+  if (!maps || !map_off || !hw || !pairs || !tab_off || !rois || !img_off || !scores || !tables || !Wout || Hmax < 1 ||
+      Wmax < 1 || max_px < 1 || max_px > (long)Hmax * Wmax || n_pairs < 0 || n_pairs > n_img * K || M < n_img)
+    return DRN_ERR_ARG;
+  if (max_px >= (1L << 24)) return DRN_ERR_UNSUPPORTED;  // fp32 counts stay exact below 2^24 pixels per image
+  if (n_pairs == 0) return DRN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  CscPairParams q{maps, map_off, hw, pairs, tab_off, tables, n_img, K, Hmax, Wmax, M, img_off};
+  hipLaunchKernelGGL(csc_rowscan_batch_kernel, dim3(Hmax, n_pairs), dim3(256), 0, st, q, 1.f * fg_threshold);
+  hipLaunchKernelGGL(csc_colscan_batch_kernel, dim3((Wmax + 63) / 64, n_pairs), dim3(CSC_T), 0, st, q);
+  hipLaunchKernelGGL(csc_pool_batch_kernel, dim3(n_pairs), dim3(CSC_T), 0, st, q, rois, scores, area_sqrt, context_scale,
+                     Wout);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+int drn_csc_loss_batch(const float* logits, long ld, int c_cls, int c_det, int K, const float* scores,
+                       const float* row_softmax, const float* W, const float* onehot, const int* img_off, int n_img, int M,
+                       int mean_loss, float* loss_img, float* loss, float* dlogits, long ld_d, void* stream) {
+  if (const int rc = csc_batch_limits(n_img, K)) return rc;
+  if (!logits || !scores || !row_softmax || !onehot || !img_off || !loss_img || !loss || M < n_img) return DRN_ERR_ARG;
+  CscBatchLossParams q{};
+  q.p = CscLossParams{logits, ld, c_cls, c_det, K, M, scores, row_softmax, W, onehot, 0, 0, mean_loss, nullptr, dlogits, ld_d};
+  q.img_off = img_off; q.slot_cls = nullptr; q.loss_img = loss_img; q.n_img = n_img;
+  hipStream_t st = (hipStream_t)stream;
+  if (K <= 32)
+    hipLaunchKernelGGL((csc_loss_batch_kernel<32>), dim3(n_img), dim3(CSC_T), 0, st, q);
+  else
+    hipLaunchKernelGGL((csc_loss_batch_kernel<64>), dim3(n_img), dim3(CSC_T), 0, st, q);
+  hipLaunchKernelGGL(csc_batch_mean_kernel, dim3(1), dim3(64), 0, st, (const float*)loss_img, loss, n_img);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

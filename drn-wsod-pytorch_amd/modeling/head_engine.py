@@ -894,6 +894,8 @@ class _HeadEngine:
         h = self.h
         w, col, gt = s.w, s.col, s.gt
         K = h.num_classes
+        if getattr(h, "image_batches", False):
+            return self._losses_csc_batch(s)
         if s.n_img != 1:
             raise DrnError("CSCROIHeads works on ONE image per step (roi_heads_csc.py:433,442 read image_sizes[0] / "
                            "gt_classes_img_oh[0])")
@@ -906,6 +908,26 @@ class _HeadEngine:
         return self._finish(s, ["loss_cls_pos", "loss_cls_neg"], [], loss_list=[loss[0].view(()), loss[1].view(())],
                             head_cols=[("cls", 0), ("det", 0)], csc=True,
                             aux=dict(scores=scores, img_scores=img_scores, targets=[], W=W, cpgs=cpgs))
+
+    def _losses_csc_batch(self, s):
+        """CSCROIHeads.enable_image_batches(): the MIL scores of all images, one image-gradient pass per class SLOT over the
+        whole batch (CSCROIHeads._csc_weights_batch), one weights launch set for every (image, labelled class), one loss launch:
+        loss_cls_pos / loss_cls_neg are the mean over the images of the single-image losses and dlogits carries the 1 / n_img
+        (include/drn_wsod.h, "CSC on image batches")"""
+        h = self.h
+        w, col, gt = s.w, s.col, s.gt
+        K = h.num_classes
+        ops.csc_batch_limits(s.n_img, K)
+        mean_loss = h.box_predictor.mean_loss
+        scores, img_scores, _, rowsm = ops.wsddn_fwd_bwd(w["logits"], col["cls"], col["det"], K, s.img_off, s.n_img, gt["onehot"],
+                                                         dlogits=None, mean_loss=mean_loss, max_rows=gt["max_rows"],
+                                                         return_rowsm=True)
+        W, cpgs = h._csc_weights_batch(self, s, scores, rowsm)
+        loss_img, loss = ops.csc_loss_batch(w["logits"], col["cls"], col["det"], K, scores, rowsm, W, gt["onehot"], s.img_off,
+                                            s.n_img, mean_loss, dlogits=w["dlogits"])
+        return self._finish(s, ["loss_cls_pos", "loss_cls_neg"], [], loss_list=[loss[0].view(()), loss[1].view(())],
+                            head_cols=[("cls", 0), ("det", 0)], csc=True,
+                            aux=dict(scores=scores, img_scores=img_scores, targets=[], W=W, cpgs=cpgs, csc_loss_img=loss_img))
 
     def _finish(self, s, loss_names, col0s, **fields):
         """the one ending of a training forward: the state backward() takes (`fields`: loss_list, head_cols, aux, csc), the

@@ -725,6 +725,23 @@ class WSDDNROIHeads(OICRROIHeads):
     _refine_from_cfg = False
 
 
+def csc_slot_schedule(labelled, img_scores, tau):
+    """The image-gradient passes of one CSC step on an image batch (pure host function; include/drn_wsod.h, "CSC on image
+    batches").  labelled[i]: the labelled classes of image i; img_scores[i][c]: its image-level scores; tau: the threshold a
+    class has to reach to get a map.  ->
+      active  per image the ascending labelled classes with score >= tau
+      slots   S = max_i |active[i]| rows of one class per image: slots[j][i] = active[i][j], or -1 where image i has fewer
+              (one d/dx pass over the whole batch per row)
+      pairs   every (image, labelled class), active or not: a labelled class below tau keeps a zero map and still goes through
+              the weights op, as in the reference"""
+    labelled = [sorted({int(c) for c in L}) for L in labelled]
+    active = [[c for c in L if img_scores[i][c] >= tau] for i, L in enumerate(labelled)]
+    n_slots = max([len(a) for a in active] or [0])
+    slots = [[a[j] if j < len(a) else -1 for a in active] for j in range(n_slots)]
+    pairs = [(i, c) for i, L in enumerate(labelled) for c in L]
+    return dict(active=active, slots=slots, pairs=pairs)
+
+
 @ROI_HEADS_REGISTRY.register()
 class CSCROIHeads(OICRROIHeads):
     """roi_heads_csc.py:40-551: the WSDDN MIL head trained with two image-level BCE losses on CSC-weighted score sums.
@@ -745,6 +762,7 @@ class CSCROIHeads(OICRROIHeads):
         self.tau, self.fg_threshold, self.bg_threshold = 0.7, 0.1, 0.005  # roi_heads_csc.py:107-109
         self.context_scale, self.area_sqrt = 1.8, True  # :110-118 (mass / density thresholds are unused by the op)
         self.image_grad_fn = None  # set by GeneralizedRCNNWSL: feature-map gradient -> image gradient (NHWC)
+        self._image_batches = False  # enable_image_batches()
 
     @classmethod
     def from_config(cls, cfg, input_shape):
@@ -782,6 +800,49 @@ class CSCROIHeads(OICRROIHeads):
                 ops.csc_cpg(self.image_grad_fn(dfeat), 3, out=cpgs[c])
             # (a labelled class below tau keeps a zero map and still goes through the op, as in the reference)
             ops.csc_weights(cpgs[c], self.fg_threshold, fg["rois"], scores, c, self.area_sqrt, self.context_scale, W, table)
+        return W, cpgs
+
+    @property
+    def image_batches(self):
+        return self._image_batches
+
+    def enable_image_batches(self, on=True):
+        """Train on batches of images (off by default: like the reference, a step with more than one image is refused).  On:
+        every image gets the maps of its own labelled classes from its own crop of the batch's image gradient - slot j of the
+        step carries the j-th active class of EVERY image through one d/dx pass, so a step costs max_i |active_i| passes
+        instead of their sum; loss_cls_pos / loss_cls_neg are the mean over the images of the single-image losses - what a
+        data-parallel job with one image per rank optimises - and _last_state["aux"]["cpgs"] is a list of [K, H_i, W_i] maps
+        (include/drn_wsod.h, "CSC on image batches"; at most ops.CSC_MAX_IMAGES images).  Graphed steps stay refused."""
+        self._image_batches = bool(on)
+        return self
+
+    def _csc_weights_batch(self, eng, s, scores, rowsm):
+        """_csc_weights for the n_img images of an opted-in step -> (W [M, K] or None past CSC_MAX_ITER, list of maps or None)"""
+        K, n, w, col = self.num_classes, s.n_img, s.w, s.col
+        sizes = [(int(hw[0]), int(hw[1])) for hw in self.images.image_sizes]
+        ops.csc_batch_limits(n, K, sizes)
+        if self.iter > self.csc_max_iter:
+            return None, None
+        if self.image_grad_fn is None:
+            raise DrnError("CSCROIHeads needs the meta-architecture's image-gradient pass (GeneralizedRCNNWSL with cpg)")
+        if len(sizes) != n or self.images.nhwc.shape[0] != n:
+            raise DrnError("CSC image batch: %d images for %d proposal lists" % (len(sizes), n))
+        dev = scores.device
+        # the one host read of the step: n * K image scores, each image's the column sum the single-image head reads
+        bounds = [0]
+        for r in s.gt["rows"]:
+            bounds.append(bounds[-1] + r)
+        img = torch.stack([scores[a:b].sum(dim=0) for a, b in zip(bounds[:-1], bounds[1:])]).tolist()
+        sched = csc_slot_schedule([g.tolist() for g in self.gt_classes_img_int], img, self.tau)
+        plan = ops.CscBatchPlan(sizes, K, sched["slots"], sched["pairs"], dev)  # (the one upload)
+        flat, cpgs = plan.new_maps(dev)
+        W = torch.ones((s.M, K), dtype=torch.float32, device=dev)
+        for j in range(len(plan.slots)):
+            ops.csc_seed_batch(w["logits"], col["cls"], col["det"], K, scores, rowsm, s.img_off, n, plan.d_slots[j], w["dlogits"])
+            dfeat = eng.input_gradient(w, s.M, s.dtype, s.fg, s.masks, s.drop_p, refresh_w1t=j == 0)
+            ops.csc_cpg_batch(self.image_grad_fn(dfeat), 3, plan, j, flat)
+        ops.csc_weights_batch(flat, plan, self.fg_threshold, s.fg["rois"], s.img_off, scores, self.area_sqrt,
+                              self.context_scale, W)
         return W, cpgs
 
 

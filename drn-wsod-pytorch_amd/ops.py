@@ -739,6 +739,138 @@ def csc_loss(logits, c_cls, c_det, K, scores, rowsm, W, onehot, mean_loss, dlogi
     return loss
 
 
+CSC_MAX_IMAGES, CSC_MAX_K = 16, 128  # include/drn_wsod.h DRN_CSC_MAX_IMAGES, the K limit of drn_csc_loss
+
+
+def csc_batch_limits(n_img, K, sizes=None):
+    """the limits of CSC on image batches (include/drn_wsod.h), refused on the host before any launch or upload"""
+    if not 1 <= int(n_img) <= CSC_MAX_IMAGES:
+        raise C.DrnError("CSC image batch: %d images, 1 .. %d are built" % (n_img, CSC_MAX_IMAGES))
+    if not 1 <= int(K) <= CSC_MAX_K:
+        raise C.DrnError("CSC image batch: K = %d classes, 1 .. %d are built" % (K, CSC_MAX_K))
+    for H, W in sizes or ():
+        if H < 1 or W < 1 or H * W >= 1 << 24:
+            raise C.DrnError("CSC image batch: an image of %d x %d pixels; 1 .. 2^24 - 1 pixels keep the fp32 counts of the "
+                             "summed-area table exact" % (H, W))
+
+
+class CscBatchPlan:
+    """What one CSC step on an image batch tells the device, as ONE int64 upload (the layout of include/drn_wsod.h, "CSC on
+    image batches"): hw [n, 2] | map_off [n] | slots [S, n] | pairs [P, 2] | tab_off [P].  `sizes`: (H_i, W_i) per image;
+    `slots`: S rows of n classes (-1 = none), `pairs`: every (image, labelled class).  Host copies stay for the wrappers:
+    map_floats / table_floats are what `maps` / `tables` have to hold."""
+
+    def __init__(self, sizes, K, slots, pairs, device):
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        n = len(sizes)
+        csc_batch_limits(n, K, sizes)
+        slots = [[int(c) for c in row] for row in slots]
+        pairs = [(int(i), int(c)) for i, c in pairs]
+        if any(len(row) != n or any(not -1 <= c < K for c in row) for row in slots):
+            raise C.DrnError("CSC image batch: a slot row must hold one class (or -1) per image")
+        if len(set(pairs)) != len(pairs) or any(not (0 <= i < n and 0 <= c < K) for i, c in pairs):
+            raise C.DrnError("CSC image batch: the (image, class) pairs must be distinct and in range")
+        self.n_img, self.K, self.sizes, self.slots, self.pairs = n, int(K), sizes, slots, pairs
+        self.Hmax, self.Wmax = max(h for h, _ in sizes), max(w for _, w in sizes)
+        self.max_px = max(h * w for h, w in sizes)
+        self.map_off, off = [], 0
+        for h, w in sizes:
+            self.map_off.append(off)
+            off += K * h * w
+        self.map_floats = off
+        self.tab_off, off = [], 0
+        for i, _ in pairs:
+            self.tab_off.append(off)
+            off += sizes[i][0] * sizes[i][1]
+        self.table_floats = off
+        words = [v for hw in sizes for v in hw] + self.map_off + [c for row in slots for c in row]
+        words += [v for p in pairs for v in p] + self.tab_off
+        dev = torch.tensor(words, dtype=torch.int64).to(device, non_blocking=True)  # the step's one schedule upload
+        S, P = len(slots), len(pairs)
+        o = 0
+        self.d_hw = dev[o: o + 2 * n]; o += 2 * n
+        self.d_map_off = dev[o: o + n]; o += n
+        self.d_slots = [dev[o + j * n: o + (j + 1) * n] for j in range(S)]; o += S * n
+        self.d_pairs = dev[o: o + 2 * P]; o += 2 * P
+        self.d_tab_off = dev[o: o + P]
+        self.words = dev
+
+    def new_maps(self, device):
+        """zero maps of every image -> (flat buffer, list of [K, H_i, W_i] views)"""
+        flat = torch.zeros((self.map_floats,), dtype=torch.float32, device=device)
+        return flat, self.map_views(flat)
+
+    def map_views(self, flat):
+        K = self.K
+        return [flat[o: o + K * h * w].view(K, h, w) for o, (h, w) in zip(self.map_off, self.sizes)]
+
+    def table_views(self, tables):
+        return [tables[o: o + self.sizes[i][0] * self.sizes[i][1]].view(self.sizes[i])
+                for o, (i, _) in zip(self.tab_off, self.pairs)]
+
+
+def csc_seed_batch(logits, c_cls, c_det, K, scores, rowsm, img_off, n_img, slot_cls, dlogits):
+    """drn_csc_seed_batch: per image d (sum of the image's rows of s[r, slot_cls[i]]) / d logits into its rows of dlogits
+    (zeros where slot_cls[i] = -1).  img_off int32 [n_img + 1] and slot_cls int64 [n_img] on the device."""
+    csc_batch_limits(n_img, K)
+    assert img_off.dtype == torch.int32 and img_off.numel() == n_img + 1 and img_off.is_contiguous()
+    assert slot_cls.dtype == torch.int64 and slot_cls.numel() == n_img and slot_cls.is_contiguous()
+    assert scores.is_contiguous() and rowsm.is_contiguous()
+    C.call("drn_csc_seed_batch", C.ptr(logits), _2d(logits), c_cls, c_det, K, C.ptr(scores), C.ptr(rowsm), C.ptr(img_off),
+           int(n_img), scores.shape[0], C.ptr(slot_cls), C.ptr(dlogits), _2d(dlogits), C.stream())
+    return dlogits
+
+
+def csc_cpg_batch(dimg_nhwc, n_colours, plan, slot, maps):
+    """drn_csc_cpg_batch: the padded gradient [n, Hmax, Wmax, Cpad] -> for every image with a class in slot `slot` of `plan`
+    the normalised map of its own crop, into `maps` (plan.new_maps)"""
+    csc_batch_limits(plan.n_img, plan.K)
+    n, H, W, cp = dimg_nhwc.shape
+    if n != plan.n_img or H < plan.Hmax or W < plan.Wmax:
+        raise C.DrnError("CSC image batch: the gradient %s does not hold %d images of up to %d x %d" % (
+            tuple(dimg_nhwc.shape), plan.n_img, plan.Hmax, plan.Wmax))
+    assert dimg_nhwc.is_contiguous() and maps.is_contiguous() and maps.numel() == plan.map_floats
+    scratch = torch.empty((n,), dtype=torch.int32, device=dimg_nhwc.device)
+    C.call("drn_csc_cpg_batch", C.ptr(dimg_nhwc), C.dt(dimg_nhwc.dtype), cp, n_colours, n, H, W, C.ptr(plan.d_hw),
+           C.ptr(plan.d_slots[slot]), plan.K, C.ptr(plan.d_map_off), C.ptr(maps), C.ptr(scratch), C.stream())
+    return maps
+
+
+def csc_weights_batch(maps, plan, fg_threshold, rois5, img_off, scores, area_sqrt, context_scale, W_out, tables=None):
+    """drn_csc_weights_batch: every (image, class) pair of `plan` -> its column of its image's rows of W_out [M, K].
+    Returns the tables scratch (plan.table_views: the summed-area table of every pair)."""
+    csc_batch_limits(plan.n_img, plan.K, plan.sizes)
+    M, K = scores.shape
+    assert K == plan.K and W_out.shape == (M, K) and maps.numel() == plan.map_floats
+    assert maps.is_contiguous() and rois5.is_contiguous() and scores.is_contiguous() and W_out.is_contiguous()
+    assert img_off.dtype == torch.int32 and img_off.numel() == plan.n_img + 1
+    if tables is None:
+        tables = torch.empty((max(1, plan.table_floats),), dtype=torch.float32, device=scores.device)
+    assert tables.numel() >= plan.table_floats
+    if plan.pairs:
+        C.call("drn_csc_weights_batch", C.ptr(maps), C.ptr(plan.d_map_off), C.ptr(plan.d_hw), plan.n_img, plan.Hmax, plan.Wmax,
+               plan.max_px, C.ptr(plan.d_pairs), C.ptr(plan.d_tab_off), len(plan.pairs), float(fg_threshold), C.ptr(rois5),
+               C.ptr(img_off), M, C.ptr(scores), K, int(area_sqrt), float(context_scale), C.ptr(tables), C.ptr(W_out),
+               C.stream())
+    return tables
+
+
+def csc_loss_batch(logits, c_cls, c_det, K, scores, rowsm, W, onehot, img_off, n_img, mean_loss, dlogits=None):
+    """drn_csc_loss_batch -> (loss_img [n_img, 2], loss [2]): per image the single-image losses, their mean over the images
+    (fp64 sum in ascending order, rounded once), and the 1 / n_img-scaled dlogits rows.  W None = ones."""
+    csc_batch_limits(n_img, K)
+    M = scores.shape[0]
+    assert onehot.shape == (n_img, K) and onehot.dtype == torch.float32 and onehot.is_contiguous()
+    assert img_off.dtype == torch.int32 and img_off.numel() == n_img + 1
+    assert scores.is_contiguous() and rowsm.is_contiguous() and (W is None or W.is_contiguous())
+    loss_img = torch.empty((n_img, 2), dtype=torch.float32, device=scores.device)
+    loss = torch.empty((2,), dtype=torch.float32, device=scores.device)
+    C.call("drn_csc_loss_batch", C.ptr(logits), _2d(logits), c_cls, c_det, K, C.ptr(scores), C.ptr(rowsm), C.ptr(W),
+           C.ptr(onehot), C.ptr(img_off), int(n_img), M, int(mean_loss), C.ptr(loss_img), C.ptr(loss), C.ptr(dlogits),
+           _2d(dlogits) if dlogits is not None else 0, C.stream())
+    return loss_img, loss
+
+
 def oicr_targets(prev_scores, prev_boxes, props, img_off, n_img, gt_classes, gt_count, img_scores, K,
                  thresholds=(0.5,), labels=(0, 1), zero_delta_decode=False):
     M = props.shape[0]

@@ -938,6 +938,60 @@ int drn_csc_loss(const float* logits, long ld, int c_cls, int c_det, int K, int 
                  const float* row_softmax, const float* W, const float* onehot, int mode, int cstar, int mean_loss,
                  float* loss, float* dlogits, long ld_d, void* stream);
 
+/* ---- CSC on image batches (CSCROIHeads.enable_image_batches) ---------------------------------------------------------------
+ * The reference has no batched CSC (roi_heads_csc.py:433-466 reads image_sizes[0] / gt_classes_img_oh[0]; its recipes run
+ * IMS_PER_BATCH = 4 as four processes of one image); the definition is this package's.  A batch holds n_img images;
+ * image i has its own size (H_i, W_i) inside the padded batch tensor [n_img, Hmax, Wmax, cpad], owns rows
+ * [img_off[i], img_off[i+1]) of logits / scores / rois / W (M rows in all) and the labels onehot[i].
+ *   map of image i, class c   the image gradient of (sum over image i's rows of score[r, c]) w.r.t. the padded batch tensor,
+ *             cropped to (H_i, W_i), then |.|, max over the colours, divided by the maximum OF THAT CROP.  The padding is
+ *             never read and never enters a maximum, a table or a box sum; CSCPool clamps image i's boxes to (H_i, W_i).
+ *   per image the seed rows, the map, the table, W[rows of i, :] and loss_img[i] are what drn_csc_loss (mode 1) / drn_csc_cpg
+ *             / drn_csc_weights / drn_csc_loss (mode 0) give for that image's slice alone, bit for bit: the same kernel
+ *             bodies run on the slice.  (The image-gradient pass between seed and map is the trunk's and has its own tolerance.)
+ *   loss      [2] = (float)((sum over i ascending of (double)loss_img[i][j]) / n_img): the mean over images in a fixed order,
+ *             no float atomics; W NULL (past WSL.CSC_MAX_ITER: W = ones, no maps) takes the same mean
+ *   dlogits   the rows of image i are the single-image rows, every entry multiplied once more by 1.f / (float)n_img
+ * Slots: per image the labelled classes whose image score reaches tau, ascending, are its active classes; slot j carries the
+ * j-th active class of every image (-1 where an image has fewer), so max_i |A_i| image-gradient passes over ALL rows serve the
+ * batch.  A labelled class below tau keeps a zero map and still goes through drn_csc_weights_batch, as in the reference.
+ * Integers that describe the step (hw, slot_cls, map_off, pairs, tab_off) are DEVICE int64 words: one upload per step holds
+ * them all.  img_off: DEVICE int32 [n_img + 1], ascending from 0 to M (what the MIL entries take).
+ * Limits: 1 <= n_img <= DRN_CSC_MAX_IMAGES, K <= 128 (as drn_csc_loss), H_i * W_i < 2^24 (as drn_csc_weights): beyond them
+ * DRN_ERR_UNSUPPORTED, on the host, before any launch.  What the host cannot see - a row range outside 0 .. M, a size outside
+ * 1 .. (Hmax, Wmax), a pair's image or class out of range - skips that image / pair: nothing of it is written (mode 0: its
+ * loss_img is NaN, which makes the batch loss NaN).
+ *
+ * drn_csc_seed_batch: one workgroup per image, drn_csc_loss (mode 1) with cstar = slot_cls[i] on the image's rows.  Rows of an
+ * image with slot_cls[i] = -1 are written as zeros (cls / det columns), so the d/dx pass carries an exact zero for it. */
+#define DRN_CSC_MAX_IMAGES 16
+int drn_csc_seed_batch(const float* logits, long ld, int c_cls, int c_det, int K, const float* scores,
+                       const float* row_softmax, const int* img_off, int n_img, int M, const long* slot_cls,
+                       float* dlogits, long ld_d, void* stream);
+
+/* drn_csc_cpg_batch: dimg = the padded gradient [n_img, Hmax, Wmax, cpad] (the first C channels are colours).  For every image
+ * with slot_cls[i] >= 0: drn_csc_cpg of the crop [H_i, W_i] -> maps + map_off[i] + slot_cls[i] * H_i * W_i (image i's
+ * [K, H_i, W_i] block, offsets in floats); hw [n_img][2] = (H_i, W_i).  An image with -1 is not touched.  The maxima are per
+ * image (integer atomicMax on the bits of non-negative floats: exact).  scratch: 4 * n_img bytes. */
+int drn_csc_cpg_batch(const void* dimg, int dtype, int cpad, int C, int n_img, int Hmax, int Wmax, const long* hw,
+                      const long* slot_cls, int K, const long* map_off, float* maps, void* scratch, void* stream);
+
+/* drn_csc_weights_batch: drn_csc_weights for every pair p = (image pairs[2p], class pairs[2p+1]) of the step in three launches:
+ * row scans over (row, pair), column scans over (64-column block, pair) - integer counts, exact in any order - and one CSCPool
+ * workgroup per pair with csc_pool's fixed reduction order (`pred` is an fp32 sum) -> W[rows of the image, class].  Pairs must be
+ * distinct.  tables + tab_off[p]: H_i * W_i floats of scratch per pair, the pair's summed-area table afterwards.  max_px: HOST
+ * bound on every H_i * W_i (< 2^24).  Columns of W that no pair names are not touched. */
+int drn_csc_weights_batch(const float* maps, const long* map_off, const long* hw, int n_img, int Hmax, int Wmax,
+                          long max_px, const long* pairs, const long* tab_off, int n_pairs, float fg_threshold,
+                          const float* rois, const int* img_off, int M, const float* scores, int K, int area_sqrt,
+                          float context_scale, float* tables, float* Wout, void* stream);
+
+/* drn_csc_loss_batch: one workgroup per image, drn_csc_loss (mode 0) on the image's rows with onehot[i] -> loss_img [n_img][2]
+ * and, when dlogits != NULL, the 1 / n_img-scaled rows; then one wave forms loss [2] as defined above. */
+int drn_csc_loss_batch(const float* logits, long ld, int c_cls, int c_det, int K, const float* scores,
+                       const float* row_softmax, const float* W, const float* onehot, const int* img_off, int n_img, int M,
+                       int mean_loss, float* loss_img, float* loss, float* dlogits, long ld_d, void* stream);
+
 /* ---- launch plans (round 3): the frozen trunk's whole layer sequence in ONE call ----
  * Replaces the per-layer Python walk of `ResNet.forward` / `BasicStem.forward` / `BottleneckBlock.forward` /
  * `BasicBlock.forward` (projects/WSL/wsl/modeling/backbone/resnet_ws.py:479-502, :405-416, :217-237, :93-112) and
