@@ -97,6 +97,7 @@ _SIGS = {
     "drn_csc_cpg_batch": "piii" + "iiippip" + "ppp",
     "drn_csc_weights_batch": "pppiiil" + "ppi" + "f" + "ppipi" + "if" + "ppp",
     "drn_csc_loss_batch": "pliiipppp" + "piii" + "ppplp",
+    "drn_csc_stats": "ppipiip" + "pipp" + "p",
     "drn_trunk_shapes": "p" + "iiiiiiii" + "pp",
     "drn_trunk_forward": "piiip" + "iiiii" + "p",
 }

@@ -8,6 +8,8 @@
 //                                                                           fast_rcnn.py:887-931, roi_heads_csc.py:441-455
 //   drn_csc_{seed,cpg,weights,loss}_batch   the same bodies per image / per (image, class) pair of an image batch
 //                     (CSCROIHeads.enable_image_batches; the definition is this package's, include/drn_wsod.h)
+//   drn_csc_stats     the table of the reference's `Statistic` log (third_party/cpg_stats.py), counted on the device
+//                     (CSCROIHeads.enable_csc_stats)                         fast_rcnn.py:910-918
 // The reference runs the table, the normalisation and the blend on the HOST (three device<->host copies per class and
 // a cudaDeviceSynchronize); here everything stays on the stream.  Integer / index work (threshold, counts, rounded box
 // corners) is bit-exact with oracle/csc_ops.c; this file builds with -ffp-contract=off, and `/` / sqrtf() are the
@@ -489,6 +491,124 @@ __global__ __launch_bounds__(CSC_T) void csc_pool_batch_kernel(CscPairParams q, 
                 area_sqrt, context_scale, Wout + (long)o0 * q.K, red);
 }
 
+// ---- weight statistics (CSCROIHeads.enable_csc_stats; "CSC weight statistics" in include/drn_wsod.h) ----------------------
+// Two launches.  csc_stats_image_kernel: one workgroup per image; the image's rows of scores / W travel through LDS in tiles
+// of whole rows (every global read runs along K, all 1024 threads load), and one thread per (column, quantity) walks the
+// tile row by row - so each of the three sums of a column is ONE fp64 chain in ascending row order, whatever the tile or the
+// grid is.
+// It writes one record per (image, class): nothing is accumulated across images here.  csc_stats_fold_kernel: one workgroup,
+// thread c folds the images' records of class c into the table in ascending image order (plain fp64 / int64 adds: the
+// stream orders the launches, no atomics are needed).
+constexpr int CSC_ST_TILE = 4096;  // floats of one LDS tile per tensor: >= 32 whole rows at K = 128
+constexpr int CSC_ST_REC = 6;      // 8-byte words per (image, class) record: pred, pos, neg (fp64), #pos, #neg, #zero (int64)
+
+__device__ __forceinline__ float csc_clampf(float v, float lo, float hi) {  // torch.clamp: a NaN stays a NaN
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// part: per image 1 + CSC_ST_REC * K words; word 0 = R (0: the image's row range is invalid, nothing of it counts)
+__global__ __launch_bounds__(CSC_T) void csc_stats_image_kernel(const float* scores, const float* W, const int* img_off,
+                                                                int M, int K, long long* part) {
+  __shared__ float ts[CSC_ST_TILE], tw[CSC_ST_TILE];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  long long* rec = part + (long)i * (1 + CSC_ST_REC * K);
+  const int o0 = img_off[i], o1 = img_off[i + 1];
+  if (o0 < 0 || o1 > M || o1 <= o0) {  // (the whole workgroup: no barrier is left behind)
+    if (tid == 0) rec[0] = 0;
+    return;
+  }
+  // thread (what, c) = (tid / 128, tid % 128): the four quantities of a column - the score sum, the two weighted sums, the
+  // sign counts - are four chains in four different waves, each of them ascending over the rows
+  const int R = o1 - o0, rpt = CSC_ST_TILE / K, what = tid >> 7, c = tid & 127;
+  const bool mine = what < 4 && c < K;
+  double acc = 0.0;
+  int npos = 0, nneg = 0;
+  for (int r0 = 0; r0 < R; r0 += rpt) {
+    const int nr = min(rpt, R - r0), n = nr * K;
+    const long base = ((long)o0 + r0) * K;
+    for (int e = tid; e < n; e += CSC_T) {
+      ts[e] = scores[base + e];
+      tw[e] = W[base + e];
+    }
+    __syncthreads();
+    if (mine) {
+      if (what == 0) {
+#pragma unroll 8
+        for (int r = 0; r < nr; ++r) acc += (double)ts[r * K + c];
+      } else if (what == 1) {  // (the product of two floats is exact in fp64)
+#pragma unroll 8
+        for (int r = 0; r < nr; ++r) acc += (double)ts[r * K + c] * (double)fmaxf(tw[r * K + c], 0.f);
+      } else if (what == 2) {
+#pragma unroll 8
+        for (int r = 0; r < nr; ++r) acc += (double)ts[r * K + c] * (double)fmaxf(-tw[r * K + c], 0.f);
+      } else {
+#pragma unroll 8
+        for (int r = 0; r < nr; ++r) {
+          const float w = tw[r * K + c];
+          npos += w > 0.f ? 1 : 0;
+          nneg += w < 0.f ? 1 : 0;  // -0.0 and NaN are neither: they count as zero weights
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) rec[0] = R;
+  if (!mine) return;
+  long long* q = rec + 1 + CSC_ST_REC * c;
+  double* qd = (double*)q;
+  if (what == 0) {
+    qd[0] = (double)csc_clampf((float)acc, 1e-6f, (float)(1.0 - 1e-6));  // predict_probs_img, fast_rcnn.py:959-961
+  } else if (what < 3) {
+    qd[what] = (double)csc_clampf((float)acc, 1e-20f, 1.0f);             // csc_loss :900-908 (1.0 - 1e-20 IS 1.0 in fp32)
+  } else {
+    q[3] = npos;
+    q[4] = nneg;
+    q[5] = (long long)R - npos - nneg;
+  }
+}
+
+// table: DRN_CSC_STATS_HEAD int64 words (steps, num_img), DRN_CSC_STATS_INT int64 fields [K], DRN_CSC_STATS_FP fp64 fields [K]
+__global__ __launch_bounds__(128) void csc_stats_fold_kernel(const long long* part, const float* onehot, const long* slots,
+                                                             int n_slots, int n_img, int K, long long* table) {
+  __shared__ unsigned char act[DRN_CSC_MAX_IMAGES][128];
+  const int c = threadIdx.x;
+  for (int e = c; e < DRN_CSC_MAX_IMAGES * 128; e += 128) (&act[0][0])[e] = 0;
+  __syncthreads();
+  for (int e = c; e < n_slots * n_img; e += 128) {  // slot rows [n_slots][n_img]: the class image i builds a map for, or -1
+    const long k = slots[e];
+    if (k >= 0 && k < K) act[e % n_img][k] = 1;
+  }
+  __syncthreads();
+  if (c == 0) {
+    long long ni = 0;
+    for (int i = 0; i < n_img; ++i) ni += part[(long)i * (1 + CSC_ST_REC * K)] > 0 ? 1 : 0;
+    table[0] += 1;
+    table[1] += ni;
+  }
+  if (c >= K) return;
+  long long* ti = table + DRN_CSC_STATS_HEAD;
+  double* tf = (double*)(table + DRN_CSC_STATS_HEAD + (long)DRN_CSC_STATS_INT * K);
+  for (int i = 0; i < n_img; ++i) {  // ascending image order: every image is one UpdateIterStats call
+    const long long* rec = part + (long)i * (1 + CSC_ST_REC * K);
+    const long long R = rec[0];
+    if (R <= 0 || !(onehot[(long)i * K + c] > 0.5f)) continue;  // cpg_stats.py:60
+    const long long* q = rec + 1 + CSC_ST_REC * c;
+    const double* qd = (const double*)q;
+    ti[0 * K + c] += 1;      // ori_label
+    ti[1 * K + c] += R;      // ori_num_roi
+    tf[0 * K + c] += qd[0];  // ori_pred
+    if (!act[i][c]) continue;
+    ti[2 * K + c] += 1;      // csc_label
+    ti[3 * K + c] += R;      // csc_num_roi
+    ti[4 * K + c] += q[3];   // csc_roi_pos
+    ti[5 * K + c] += q[4];   // csc_roi_neg
+    ti[6 * K + c] += q[5];   // csc_roi_zero
+    tf[1 * K + c] += qd[0];  // csc_pred
+    tf[2 * K + c] += qd[1];  // csc_pred_pos
+    tf[3 * K + c] += qd[2];  // csc_pred_neg
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -623,6 +743,21 @@ int drn_csc_loss_batch(const float* logits, long ld, int c_cls, int c_det, int K
   else
     hipLaunchKernelGGL((csc_loss_batch_kernel<64>), dim3(n_img), dim3(CSC_T), 0, st, q);
   hipLaunchKernelGGL(csc_batch_mean_kernel, dim3(1), dim3(64), 0, st, (const float*)loss_img, loss, n_img);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// ---- weight statistics: see "CSC weight statistics" in include/drn_wsod.h ----
+int drn_csc_stats(const float* scores, const float* W, int K, const int* img_off, int n_img, int M, const float* onehot,
+                  const long* slots, int n_slots, void* scratch, long* table, void* stream) {
+  if (const int rc = csc_batch_limits(n_img, K)) return rc;
+  if (!scores || !W || !img_off || !onehot || !scratch || !table || M < n_img || n_slots < 0 || n_slots > K ||
+      (n_slots > 0 && !slots))
+    return DRN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(csc_stats_image_kernel, dim3(n_img), dim3(CSC_T), 0, st, scores, W, img_off, M, K, (long long*)scratch);
+  hipLaunchKernelGGL(csc_stats_fold_kernel, dim3(1), dim3(128), 0, st, (const long long*)scratch, onehot, slots, n_slots,
+                     n_img, K, (long long*)table);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

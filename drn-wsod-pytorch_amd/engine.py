@@ -1201,7 +1201,11 @@ class Trainer:
 
     def flush_metrics(self):
         """drain now and wait for that one copy: everything recorded so far is in self.storage afterwards.  Returns the
-        number of records lost (overwritten in the ring before a drain reached them)."""
+        number of records lost (overwritten in the ring before a drain reached them).  A CSC head's weight statistics
+        (CSCROIHeads.enable_csc_stats) are flushed as well: CscStats.flush() drains the open period and waits for its copy."""
+        stats = getattr(getattr(getattr(self.model, "roi_heads", None), "_engine", None), "csc_stats", None)
+        if stats is not None:
+            stats.flush()
         if self.metrics is None:
             return 0
         lost = self._feed_metrics(True)

@@ -16,9 +16,16 @@ the annotated boxes - they feed no loss -
 from two more launches in front of the record (drn_label_proposals, drn_mil_metrics), published in the record's unused space.
 
 More than one rank: every rank records its own losses and counts; the reference's cross-rank average of _write_metrics
-(comm.gather + np.mean) is not built."""
+(comm.gather + np.mean) is not built.
+
+CscStats (CSCROIHeads.enable_csc_stats): the reference's `Statistic` log of the CSC weights (third_party/cpg_stats.py, csc.txt)
+from a table one launch pair per training forward counts on the device (drn_csc_stats; include/drn_wsod.h, "CSC weight
+statistics"); one stream-ordered copy per LOG_PERIOD, no per-step read."""
+import math
+import os
 import struct
 
+import numpy as np
 import torch
 
 from . import ops
@@ -158,3 +165,142 @@ class MetricsRing:
             out.append((self.iter0 + i, decode_record(rec, self.names, self.n_img)))
         self.collected = max(self.collected, count)
         return out, lost
+
+
+_CSC_LINE = "----------------------------------------------"
+_CSC_HEAD = "#class\tpred\t#roi\t#class\tpred\tpos\tneg\t#roi\t#pos\t%\t#neg\t%\t#zero\t%\tclass"
+
+
+def decode_csc_stats(words, K):
+    """one table of drn_csc_stats (csc_stats_words(K) int64 words, the layout of include/drn_wsod.h) -> {field: numpy array [K]
+    (int64 counts, float64 sums), "steps": int, "num_img": int}; the ONE place that knows the word order"""
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.int64))
+    if w.shape != (ops.csc_stats_words(K),):
+        raise DrnError("a CSC statistics table of %d classes has %d words, not %s" % (K, ops.csc_stats_words(K), w.shape))
+    nh, ni = len(ops.CSC_STATS_HEAD), len(ops.CSC_STATS_INT)
+    out = {name: int(w[j]) for j, name in enumerate(ops.CSC_STATS_HEAD)}
+    for j, name in enumerate(ops.CSC_STATS_INT):
+        out[name] = w[nh + j * K: nh + (j + 1) * K].copy()
+    fp = w[nh + ni * K:].view(np.float64)
+    for j, name in enumerate(ops.CSC_STATS_FP):
+        out[name] = fp[j * K: (j + 1) * K].copy()
+    return out
+
+
+def format_csc_stats(table, iteration):
+    """Statistic.LogIterStats (third_party/cpg_stats.py:99-199) of one period's table, character for character: the 4-decimal
+    placeholder rows, int(a / b) truncation, csc_acm_label printed as a float, no newline behind the last row.  The acm row is
+    the sum of the per-class rows (the reference adds both in the same statements)."""
+    t = {k: ([float(x) for x in v] if isinstance(v, np.ndarray) else v) for k, v in table.items()}
+    K = len(t["ori_label"])
+    out = _CSC_LINE + str(iteration) + _CSC_LINE + "\n" + _CSC_HEAD + "\n"
+    for c in range(K):
+        n = t["ori_label"][c]
+        if n > 0:
+            out += "{}\t{:.5f}\t{}\t".format(int(n), t["ori_pred"][c] / n, int(t["ori_num_roi"][c] / n))
+        else:
+            out += "0\t0.0000\t0\t"
+        n = t["csc_label"][c]
+        if n > 0:
+            roi = t["csc_num_roi"][c]
+            out += "{}\t{:.5f}\t{:.5f}\t{:.5f}\t{}\t{}\t{:.5f}\t{}\t{:.5f}\t{}\t{:.5f}\t{}".format(
+                int(n), t["csc_pred"][c] / n, t["csc_pred_pos"][c] / n, t["csc_pred_neg"][c] / n, int(roi / n),
+                int(t["csc_roi_pos"][c] / n), 1.0 * t["csc_roi_pos"][c] / roi, int(t["csc_roi_neg"][c] / n),
+                1.0 * t["csc_roi_neg"][c] / roi, int(t["csc_roi_zero"][c] / n), 1.0 * t["csc_roi_zero"][c] / roi, c)
+        else:
+            out += "0\t0.0000\t0.0000\t0.0000\t0\t0\t0.0000\t0\t0.0000\t0\t0.0000\t{}".format(c)
+        out += "\n"
+    a = {k: math.fsum(v) for k, v in t.items() if isinstance(v, list)}
+    if a["ori_label"] > 0 and a["csc_label"] > 0:
+        n, m, roi = a["ori_label"], a["csc_label"], a["csc_num_roi"]
+        out += "{}\t{:.5f}\t{}\t{}\t{:.5f}\t{:.5f}\t{:.5f}\t{}\t{}\t{:.5f}\t{}\t{:.5f}\t{}\t{:.5f}\t{}".format(
+            int(n), a["ori_pred"] / n, int(a["ori_num_roi"] / n), m, a["csc_pred"] / m, a["csc_pred_pos"] / m,
+            a["csc_pred_neg"] / m, int(roi / m), int(a["csc_roi_pos"] / m), 1.0 * a["csc_roi_pos"] / roi,
+            int(a["csc_roi_neg"] / m), 1.0 * a["csc_roi_neg"] / roi, int(a["csc_roi_zero"] / m), 1.0 * a["csc_roi_zero"] / roi,
+            int(t["num_img"]))
+    return out
+
+
+class CscStats:
+    """The device-side `Statistic` of one CSCROIHeads (made by enable_csc_stats; the head engine calls forward()).  Owns the
+    table, the scratch of drn_csc_stats and a small pool of pinned host copies.  cur_iter counts training forwards from
+    start_iter, as the reference's own counter does - one per micro-step of an ITER_SIZE window, also for a step the anomaly
+    guard skips: the statistics describe the forward.  After the forward with cur_iter % period == 0 and cur_iter <= max_iter
+    the table is drained: a non-blocking copy to pinned memory, a stream-ordered re-zero and an event, no host sync.  collect()
+    decodes what has completed; with output_dir set every decoded block is appended to <output_dir>/<prefix>csc.txt.
+    blocks: every (iteration, text) handed out so far."""
+
+    def __init__(self, K, max_iter, period=320, output_dir=None, prefix="", start_iter=0, device="cuda"):
+        if int(period) < 1:
+            raise DrnError("enable_csc_stats(period=%r): a positive number of training forwards" % (period,))
+        ops.csc_batch_limits(1, K)
+        self.K, self.max_iter, self.period = int(K), int(max_iter), int(period)
+        self.cur_iter = int(start_iter)
+        self.path = None if output_dir is None else os.path.join(output_dir, prefix + "csc.txt")
+        self.table = torch.zeros((ops.csc_stats_words(K),), dtype=torch.int64, device=device)
+        self.scratch = torch.empty((ops.csc_stats_scratch_words(ops.CSC_MAX_IMAGES, K),), dtype=torch.int64, device=device)
+        self.blocks = []
+        self._pending, self._free = [], []  # drains under way (iteration, host copy, event); host copies to use again
+        self._last = None                   # iteration of the last counted forward that no drain has taken yet
+
+    # ---- device side: what the head engine calls once W is final -----------------------------------------------------------
+    def forward(self, scores, W, img_off, n_img, onehot, slots, launch=True):
+        """one training forward: the step's launch pair on the current stream (launch=False past CSC_MAX_ITER: W is None there
+        and the reference prints nothing either), then the reference's LogIterStats rule"""
+        if launch:
+            ops.csc_stats(scores, W, img_off, n_img, onehot, slots, self.table, self.scratch)
+        it = self._last = self.cur_iter
+        self.cur_iter += 1
+        if it % self.period == 0 and it <= self.max_iter:
+            self.drain(it)
+        elif self._pending:
+            self.collect()
+
+    # ---- host side -------------------------------------------------------------------------------------------------------
+    def drain(self, iteration=None):
+        """copy the table to pinned memory and re-zero it, both on the CURRENT stream - the one the heads run on, so the copy
+        sees whole forwards only - and an event behind them.  The block is labelled `iteration` (default: the last forward)."""
+        it = self._last if iteration is None else int(iteration)
+        host = self._free.pop() if self._free else torch.zeros_like(self.table, device="cpu")
+        if self.table.is_cuda and not host.is_pinned():
+            host = host.pin_memory()
+        host.copy_(self.table, non_blocking=True)
+        self.table.zero_()
+        ev = None
+        if self.table.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record()
+        self._pending.append((it, host, ev))
+        self._last = None
+
+    def collect(self, wait=False):
+        """-> [(iteration, table), ...]: every drain whose copy has completed, oldest first (wait=True: after synchronising the
+        drains' own events, nothing else).  table: decode_csc_stats' dict of numpy arrays.  Appends the blocks to csc.txt."""
+        out = []
+        while self._pending:
+            it, host, ev = self._pending[0]
+            if ev is not None:
+                if wait:
+                    ev.synchronize()
+                elif not ev.query():
+                    break
+            self._pending.pop(0)
+            out.append((it, decode_csc_stats(host.numpy(), self.K)))
+            self._free.append(host)
+        for it, table in out:
+            text = self.format(table, it)
+            self.blocks.append((it, text))
+            if self.path is not None:
+                os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
+                with open(self.path, "a") as f:
+                    f.write(text + "\n")
+        return out
+
+    def flush(self):
+        """drain what the forwards since the last drain have counted (a block labelled with the last forward's iteration; nothing
+        when there was none) and wait for every copy under way -> collect(wait=True)"""
+        if self._last is not None:
+            self.drain()
+        return self.collect(wait=True)
+
+    format = staticmethod(format_csc_stats)

@@ -155,7 +155,7 @@ class _HeadEngine:
         "fc1_tn", "fused_fc7_fwd", "fused_loss_tail", "fused_pred_dx", "fc7_dx_split", "fc7_bwd_pair", "fc7_pair_dx_splits",
         "fc1_joint_peel", "fc1_fused_all", "fc1_grad_slabs", "fc1_slab_ends",
         # what other objects install
-        "grad_ready_hook", "feature_grad_hook", "loss_guard", "metrics", "fc1_fused_tn", "fc1_fused_cols", "fc1_grad_bucket",
+        "grad_ready_hook", "feature_grad_hook", "loss_guard", "metrics", "csc_stats", "fc1_fused_tn", "fc1_fused_cols", "fc1_grad_bucket",
         "kshard", "accum_window", "accum_small", "defer_colsum", "defer_fc1_tail", "pcl_image_batches", "pool_sets_pinned",
         "pool_sets_pin_owner", "captured_by",
         # layout made by ensure()
@@ -187,6 +187,7 @@ class _HeadEngine:
         self.feature_grad_hook = None    # GeneralizedRCNNWSL.forward / GraphedFullStep: takes the feature-map gradient (FREEZE_AT < 5)
         self.loss_guard = None           # FusedSGD(nonfinite=...): the LossGuard whose check follows the loss tail
         self.metrics = None              # ROIHeads.enable_metrics / disable_metrics: the MetricsRing
+        self.csc_stats = None            # CSCROIHeads.enable_csc_stats / disable_csc_stats: the metrics.CscStats
         self.fc1_fused_tn = None         # FusedSGD.enable_pipelined / enable_fused_fc1_tn: fc6 dW + SGD as one launch
         self.fc1_fused_cols = None       # FusedSGD.enable_pipelined(exchange="fc6_kshard"): the same for the owned columns
         self.fc1_grad_bucket = None      # FusedSGD.enable_pipelined: [D1, K1] bf16 exchange buffer instead of the arena
@@ -903,6 +904,8 @@ class _HeadEngine:
                                                          dlogits=None, mean_loss=h.box_predictor.mean_loss,
                                                          max_rows=gt["max_rows"], return_rowsm=True)
         W, cpgs = h._csc_weights(self, w, col, scores, rowsm, s.M, s.dtype, s.fg, s.masks, s.drop_p)
+        if self.csc_stats is not None:
+            self._csc_stats_forward(s, scores, W)
         loss = ops.csc_loss(w["logits"], col["cls"], col["det"], K, scores, rowsm, W, gt["onehot"].view(-1),
                             h.box_predictor.mean_loss, dlogits=w["dlogits"])
         return self._finish(s, ["loss_cls_pos", "loss_cls_neg"], [], loss_list=[loss[0].view(()), loss[1].view(())],
@@ -923,11 +926,32 @@ class _HeadEngine:
                                                          dlogits=None, mean_loss=mean_loss, max_rows=gt["max_rows"],
                                                          return_rowsm=True)
         W, cpgs = h._csc_weights_batch(self, s, scores, rowsm)
+        if self.csc_stats is not None:
+            self._csc_stats_forward(s, scores, W)
         loss_img, loss = ops.csc_loss_batch(w["logits"], col["cls"], col["det"], K, scores, rowsm, W, gt["onehot"], s.img_off,
                                             s.n_img, mean_loss, dlogits=w["dlogits"])
         return self._finish(s, ["loss_cls_pos", "loss_cls_neg"], [], loss_list=[loss[0].view(()), loss[1].view(())],
                             head_cols=[("cls", 0), ("det", 0)], csc=True,
                             aux=dict(scores=scores, img_scores=img_scores, targets=[], W=W, cpgs=cpgs, csc_loss_img=loss_img))
+
+    def _csc_stats_forward(self, s, scores, W):
+        """the weight statistics (CSCROIHeads.enable_csc_stats; drn_csc_stats) once W is final, on the stream the losses run on:
+        one launch pair for all images of the step while head.iter <= CSC_MAX_ITER - past it W is None and the forward is only
+        counted.  Which (image, class) pairs are ACTIVE is the decision the step itself took (CSCROIHeads._csc_sched): an image
+        batch's slot rows sit in the plan it uploaded already; the single image's active classes - at most K - go up as one small
+        pinned copy, in a step that has just read K image scores back."""
+        h = self.h
+        launch = h.iter <= h.csc_max_iter
+        slots = None
+        if launch:
+            sched = h._csc_sched
+            if isinstance(sched, ops.CscBatchPlan):
+                slots = sched.d_slot_rows
+            elif sched:
+                slots = torch.tensor(sched, dtype=torch.int64)
+                if scores.is_cuda:
+                    slots = slots.pin_memory().to(scores.device, non_blocking=True)
+        self.csc_stats.forward(scores, W, s.img_off, s.n_img, s.gt["onehot"], slots, launch)
 
     def _finish(self, s, loss_names, col0s, **fields):
         """the one ending of a training forward: the state backward() takes (`fields`: loss_list, head_cols, aux, csc), the

@@ -749,8 +749,8 @@ class CSCROIHeads(OICRROIHeads):
     input image gives a saliency map (`_forward_cpg`: here the d/dx half of the explicit backward through the predictor,
     fc7, fc6, RoIPool and EVERY trunk layer down to the pixels); the map, thresholded and summed into a table, scores
     each proposal by its frame / context contrast (CSCPool) and becomes the signed weight W (csc.hip).  After
-    WSL.CSC_MAX_ITER iterations W_pos = 1, W_neg = 0.  Inference is WSDDN's.  Debug dumps (`_save_mask`) and the
-    `Statistic` log writer are the reference's control plane and are not rebuilt."""
+    WSL.CSC_MAX_ITER iterations W_pos = 1, W_neg = 0.  Inference is WSDDN's.  Debug dumps (`_save_mask`) are the
+    reference's control plane and are not rebuilt; its `Statistic` log (csc.txt) is enable_csc_stats()."""
 
     _refine_from_cfg = False
     csc_head = True
@@ -763,6 +763,9 @@ class CSCROIHeads(OICRROIHeads):
         self.context_scale, self.area_sqrt = 1.8, True  # :110-118 (mass / density thresholds are unused by the op)
         self.image_grad_fn = None  # set by GeneralizedRCNNWSL: feature-map gradient -> image gradient (NHWC)
         self._image_batches = False  # enable_image_batches()
+        # what the last training forward built maps for: the active classes of the one image (a list), the CscBatchPlan of an
+        # image batch, None past CSC_MAX_ITER.  Read by the weight statistics (enable_csc_stats), which are handed the decision.
+        self._csc_sched = None
 
     @classmethod
     def from_config(cls, cfg, input_shape):
@@ -773,9 +776,32 @@ class CSCROIHeads(OICRROIHeads):
     def prefetch_pooled(self, features, proposals):
         raise DrnError("the CSC head differentiates through RoIPool and the trunk: no prefetched operands")
 
+    def enable_csc_stats(self, period=320, output_dir=None, prefix="", start_iter=0):
+        """Record the reference's CSC weight statistics (`Statistic`, third_party/cpg_stats.py, driven from CSCOutputs.csc_loss,
+        fast_rcnn.py:910-918) on the device: per labelled class how many proposals W marks positive / negative / leaves at zero
+        and how the score mass splits between them.  Every training forward up to WSL.CSC_MAX_ITER adds to a table in device
+        memory (drn_csc_stats: two small launches once W is final, nothing is read back); after every `period`-th forward - the
+        reference's LOG_PERIOD = 1280 / 4 - the table is copied to pinned memory on the heads' stream and re-zeroed, and the
+        decoded block is appended to <output_dir>/<prefix>csc.txt (output_dir None: kept in CscStats.blocks only).  start_iter:
+        the training-forward count the log continues from (a resumed job).  Returns the metrics.CscStats.  Off by default:
+        without this call no launch, buffer or upload of a step changes.  Every rank writes its own file."""
+        from ..metrics import CscStats
+
+        eng = self._engine
+        eng.ensure(next(self.parameters()).device)
+        eng.csc_stats = CscStats(self.num_classes, self.csc_max_iter, period, output_dir, prefix, start_iter, eng.arena_w.device)
+        return eng.csc_stats
+
+    def disable_csc_stats(self):
+        """back to the launch sequence without the statistics; what was drained stays collectable on the returned object"""
+        eng = self._engine
+        st, eng.csc_stats = eng.csc_stats, None
+        return st
+
     def _csc_weights(self, eng, w, col, scores, rowsm, M, dtype, fg, masks, drop_p):
         """roi_heads_csc.py:423-510 (_forward_cpg + _forward_csc). Returns (W [M, K] or None past CSC_MAX_ITER, cpgs)."""
         K = self.num_classes
+        self._csc_sched = None
         if self.iter > self.csc_max_iter:
             return None, None
         if self.image_grad_fn is None:
@@ -791,6 +817,7 @@ class CSCROIHeads(OICRROIHeads):
         W = torch.ones((M, K), dtype=torch.float32, device=dev)
         table = torch.empty((H, Wd), dtype=torch.float32, device=dev)
         first = True
+        self._csc_sched = [c for c in labelled if img[c] >= self.tau]  # the classes this step builds a map for
         for c in labelled:
             if img[c] >= self.tau:
                 ops.csc_loss(w["logits"], col["cls"], col["det"], K, scores, rowsm, None, None,
@@ -821,6 +848,7 @@ class CSCROIHeads(OICRROIHeads):
         K, n, w, col = self.num_classes, s.n_img, s.w, s.col
         sizes = [(int(hw[0]), int(hw[1])) for hw in self.images.image_sizes]
         ops.csc_batch_limits(n, K, sizes)
+        self._csc_sched = None
         if self.iter > self.csc_max_iter:
             return None, None
         if self.image_grad_fn is None:
@@ -834,7 +862,7 @@ class CSCROIHeads(OICRROIHeads):
             bounds.append(bounds[-1] + r)
         img = torch.stack([scores[a:b].sum(dim=0) for a, b in zip(bounds[:-1], bounds[1:])]).tolist()
         sched = csc_slot_schedule([g.tolist() for g in self.gt_classes_img_int], img, self.tau)
-        plan = ops.CscBatchPlan(sizes, K, sched["slots"], sched["pairs"], dev)  # (the one upload)
+        plan = self._csc_sched = ops.CscBatchPlan(sizes, K, sched["slots"], sched["pairs"], dev)  # (the one upload)
         flat, cpgs = plan.new_maps(dev)
         W = torch.ones((s.M, K), dtype=torch.float32, device=dev)
         for j in range(len(plan.slots)):

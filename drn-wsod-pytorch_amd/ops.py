@@ -790,6 +790,7 @@ class CscBatchPlan:
         o = 0
         self.d_hw = dev[o: o + 2 * n]; o += 2 * n
         self.d_map_off = dev[o: o + n]; o += n
+        self.d_slot_rows = dev[o: o + S * n]  # all slot rows [S, n] at once (a view: what drn_csc_stats reads)
         self.d_slots = [dev[o + j * n: o + (j + 1) * n] for j in range(S)]; o += S * n
         self.d_pairs = dev[o: o + 2 * P]; o += 2 * P
         self.d_tab_off = dev[o: o + P]
@@ -869,6 +870,44 @@ def csc_loss_batch(logits, c_cls, c_det, K, scores, rowsm, W, onehot, img_off, n
            C.ptr(onehot), C.ptr(img_off), int(n_img), M, int(mean_loss), C.ptr(loss_img), C.ptr(loss), C.ptr(dlogits),
            _2d(dlogits) if dlogits is not None else 0, C.stream())
     return loss_img, loss
+
+
+# the table of drn_csc_stats (include/drn_wsod.h, "CSC weight statistics"): 8-byte words, two int64 head words, then [field][K]
+CSC_STATS_HEAD = ("steps", "num_img")
+CSC_STATS_INT = ("ori_label", "ori_num_roi", "csc_label", "csc_num_roi", "csc_roi_pos", "csc_roi_neg", "csc_roi_zero")
+CSC_STATS_FP = ("ori_pred", "csc_pred", "csc_pred_pos", "csc_pred_neg")
+
+
+def csc_stats_words(K):
+    return len(CSC_STATS_HEAD) + (len(CSC_STATS_INT) + len(CSC_STATS_FP)) * int(K)
+
+
+def csc_stats_scratch_words(n_img, K):
+    return int(n_img) * (1 + 6 * int(K))
+
+
+def csc_stats(scores, W, img_off, n_img, onehot, slots, table, scratch=None):
+    """drn_csc_stats: add one training forward's weight statistics to `table` (int64 [csc_stats_words(K)], zeroed by its owner).
+    scores / W [M, K] fp32, img_off int32 [n_img + 1], onehot fp32 [n_img, K]; slots: DEVICE int64 [n_slots, n_img] - the class
+    image i builds a map for in slot j, -1 = none (CscBatchPlan.d_slot_rows; a single image: its active classes) - or None."""
+    M, K = scores.shape
+    csc_batch_limits(n_img, K)
+    n_slots = 0 if slots is None else slots.numel() // int(n_img)
+    if W is None or W.shape != scores.shape or n_slots > K:
+        raise C.DrnError("csc_stats: W %s for scores %s, %d slot rows" % (None if W is None else tuple(W.shape),
+                                                                         tuple(scores.shape), n_slots))
+    assert scores.dtype == torch.float32 and W.dtype == torch.float32 and scores.is_contiguous() and W.is_contiguous()
+    assert onehot.numel() == n_img * K and onehot.dtype == torch.float32 and onehot.is_contiguous()
+    assert img_off.dtype == torch.int32 and img_off.numel() == n_img + 1 and img_off.is_contiguous()
+    assert table.dtype == torch.int64 and table.numel() == csc_stats_words(K) and table.is_contiguous()
+    if n_slots:
+        assert slots.dtype == torch.int64 and slots.numel() == n_slots * n_img and slots.is_contiguous()
+    if scratch is None:
+        scratch = torch.empty((csc_stats_scratch_words(n_img, K),), dtype=torch.int64, device=scores.device)
+    assert scratch.dtype == torch.int64 and scratch.numel() >= csc_stats_scratch_words(n_img, K)
+    C.call("drn_csc_stats", C.ptr(scores), C.ptr(W), K, C.ptr(img_off), int(n_img), M, C.ptr(onehot),
+           C.ptr(slots) if n_slots else None, n_slots, C.ptr(scratch), C.ptr(table), C.stream())
+    return table
 
 
 def oicr_targets(prev_scores, prev_boxes, props, img_off, n_img, gt_classes, gt_count, img_scores, K,

@@ -992,6 +992,43 @@ int drn_csc_loss_batch(const float* logits, long ld, int c_cls, int c_det, int K
                        const float* row_softmax, const float* W, const float* onehot, const int* img_off, int n_img, int M,
                        int mean_loss, float* loss_img, float* loss, float* dlogits, long ld_d, void* stream);
 
+/* ---- CSC weight statistics (CSCROIHeads.enable_csc_stats; metrics.CscStats) ------------------------------------------------
+ * The reference's `Statistic` (projects/WSL/wsl/modeling/roi_heads/third_party/cpg_stats.py, driven from CSCOutputs.csc_loss,
+ * fast_rcnn.py:910-918) copies W_pos / W_neg [M, K] to the host every iteration and walks M x labelled classes in Python; every
+ * LOG_PERIOD iterations it prints a table to csc.txt.  drn_csc_stats counts the same table on the device, one call per training
+ * forward for all n_img images of the step, on the stream the losses run on, once W is final.
+ * For image i with rows [img_off[i], img_off[i+1]) (R of them) and every class c with onehot[i][c] > 0.5:
+ *   pred = clamp((float)(sum_r scores[r][c]), 1e-6, 1 - 1e-6)              predict_probs_img, fast_rcnn.py:950-962
+ *   ori_label[c] += 1, ori_pred[c] += pred, ori_num_roi[c] += R
+ *   and if (i, c) is ACTIVE:
+ *   csc_label[c] += 1, csc_pred[c] += pred, csc_num_roi[c] += R
+ *   csc_pred_pos[c] += clamp((float)(sum_r scores * max(W, 0)), 1e-20, 1.0),  csc_pred_neg[c] likewise with max(-W, 0)
+ *   csc_roi_pos[c] += #{r: W[r][c] > 0}, csc_roi_neg[c] += #{W < 0}, csc_roi_zero[c] += #{neither} (-0.0 and NaN are zero
+ *   weights, as the reference's `if > 0 / elif < 0 / else`)
+ * num_img += 1 per image, steps += 1 per call.
+ * ACTIVE is "this step built a map for (i, c)".  The host takes that decision (image score >= tau, CSCROIHeads._csc_weights /
+ * csc_slot_schedule) and hands it over as the slot rows of the step - slots [n_slots][n_img] DEVICE int64, slots[j][i] = the
+ * class image i carries in slot j or -1, exactly the plan of "CSC on image batches" (a single image: its active classes, one per
+ * row).  The kernel never re-derives it from its own sums: a tie with tau in the last bit would make the log contradict the step.
+ * Arithmetic: every row sum is ONE fp64 chain in ascending row order (the products scores * max(+-W, 0) are exact in fp64),
+ * rounded to fp32 once and clamped; the table's sums are fp64, its counts int64; the images are folded into the table in
+ * ascending image order by one thread per class.  No floating-point atomics, no atomics at all: the table after a call does not
+ * depend on the launch geometry.
+ * On an image batch each image is one `UpdateIterStats` call, in ascending image order - this package's definition, like the
+ * batch itself (the reference's IMS_PER_BATCH = 4 are four processes that each write their own csc.txt).
+ * table: DRN_CSC_STATS_WORDS(K) 8-byte words - int64 steps, num_img; int64 [DRN_CSC_STATS_INT][K] = ori_label, ori_num_roi,
+ * csc_label, csc_num_roi, csc_roi_pos, csc_roi_neg, csc_roi_zero; fp64 [DRN_CSC_STATS_FP][K] = ori_pred, csc_pred, csc_pred_pos,
+ * csc_pred_neg.  The caller zeroes it (and re-zeroes it after reading it).  scratch: DRN_CSC_STATS_SCRATCH_WORDS(n_img, K)
+ * 8-byte words.  Limits as the batch entries: n_img <= DRN_CSC_MAX_IMAGES, K <= 128 (DRN_ERR_UNSUPPORTED beyond), n_slots <= K.
+ * An image whose device-side row range is invalid (outside 0 .. M, or empty) is skipped whole: nothing of it is counted. */
+#define DRN_CSC_STATS_HEAD 2
+#define DRN_CSC_STATS_INT 7
+#define DRN_CSC_STATS_FP 4
+#define DRN_CSC_STATS_WORDS(K) (DRN_CSC_STATS_HEAD + (DRN_CSC_STATS_INT + DRN_CSC_STATS_FP) * (K))
+#define DRN_CSC_STATS_SCRATCH_WORDS(n_img, K) ((n_img) * (1 + 6 * (K)))
+int drn_csc_stats(const float* scores, const float* W, int K, const int* img_off, int n_img, int M, const float* onehot,
+                  const long* slots, int n_slots, void* scratch, long* table, void* stream);
+
 /* ---- launch plans (round 3): the frozen trunk's whole layer sequence in ONE call ----
  * Replaces the per-layer Python walk of `ResNet.forward` / `BasicStem.forward` / `BottleneckBlock.forward` /
  * `BasicBlock.forward` (projects/WSL/wsl/modeling/backbone/resnet_ws.py:479-502, :405-416, :217-237, :93-112) and
