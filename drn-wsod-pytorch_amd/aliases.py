@@ -38,7 +38,8 @@ def _table():
         "detectron2.utils": {},
         "detectron2.utils.events": pick(events, "EventStorage", "get_event_storage"),
         "detectron2.utils.registry": pick(registry, "Registry"),
-        "detectron2.evaluation": pick(evaluation, "PascalVOCDetectionEvaluator"),
+        "detectron2.evaluation": pick(evaluation, "PascalVOCDetectionEvaluator", "inference_on_dataset", "inference_context",
+                                      "DatasetEvaluators"),
         "detectron2.evaluation.pascal_voc_evaluation": pick(evaluation, "PascalVOCDetectionEvaluator", "voc_eval", "voc_ap",
                                                             "voc_eval_corloc", "parse_rec"),
         "detectron2.data": pick(data, "DatasetMapper", "build_detection_train_loader", "build_batch_data_loader", "MapDataset"),

@@ -158,16 +158,16 @@ struct NmsParams {
 
 constexpr int NMS_MAXK = 1024;
 
-// one wave per image
-__global__ __launch_bounds__(64) void nms_topk_kernel(NmsParams p) {
+// one wave per image: the n candidates order[0 .. n) of one image, its own largest coordinate; leaves keep[0 .. n_keep[0])
+__device__ __forceinline__ void nms_topk_wave(const NmsParams& p, const int* order, const int n, const float* maxcoord,
+                                              int* keep, int* n_keep) {
   __shared__ float kb[NMS_MAXK][4];
   __shared__ float ka[NMS_MAXK];
   __shared__ int kc[NMS_MAXK];
   const int lane = threadIdx.x;
-  const int n = p.count[0];
   // detectron2/layers/nms.py:19-29: >= 40000 boxes => per-class NMS on the raw boxes, no offsets
   const bool per_class = n >= p.per_class_from;
-  const float offs = per_class ? 0.f : p.maxcoord[0] + 1.f;
+  const float offs = per_class ? 0.f : maxcoord[0] + 1.f;
   int nk = 0;
   for (int start = 0; start < n && nk < p.topk; start += 64) {
     const int i = start + lane;
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64) void nms_topk_kernel(NmsParams p) {
     int id = -1, cls = -1;
     bool alive = valid;
     if (valid) {
-      id = p.order[i];
+      id = order[i];
       cls = p.c_cls[id];
       const float off = (float)cls * offs;  // idxs.to(boxes) * (boxes.max() + 1)
       x1 = p.c_box[4 * (long)id] + off; y1 = p.c_box[4 * (long)id + 1] + off;
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64) void nms_topk_kernel(NmsParams p) {
       const float ba = __shfl(area, l, 64);
       const int bid = __shfl(id, l, 64);
       const int bcls = __shfl(cls, l, 64);
-      if (lane == 0) { kc[nk] = bcls; kb[nk][0] = bx1; kb[nk][1] = by1; kb[nk][2] = bx2; kb[nk][3] = by2; ka[nk] = ba; p.keep[nk] = bid; }
+      if (lane == 0) { kc[nk] = bcls; kb[nk][0] = bx1; kb[nk][1] = by1; kb[nk][2] = bx2; kb[nk][3] = by2; ka[nk] = ba; keep[nk] = bid; }
       ++nk;
       if (alive && lane > l && (!per_class || bcls == cls)) {
         const float w = fmaxf(0.f, fminf(bx2, x2) - fmaxf(bx1, x1));
@@ -211,7 +211,11 @@ __global__ __launch_bounds__(64) void nms_topk_kernel(NmsParams p) {
     }
     __syncthreads();
   }
-  if (lane == 0) p.n_keep[0] = nk;
+  if (lane == 0) n_keep[0] = nk;
+}
+
+__global__ __launch_bounds__(64) void nms_topk_kernel(NmsParams p) {
+  nms_topk_wave(p, p.order, p.count[0], p.maxcoord, p.keep, p.n_keep);
 }
 
 }  // namespace
@@ -250,6 +254,276 @@ inline Ws carve(void* workspace, long bytes, int cap) {
   k.count = (int*)w; k.maxcoord = (float*)(w + 8); w += 256;
   k.hist = (int*)w;
   return k;
+}
+
+// ---- the batched tail: all images of a call through ONE launch chain ----------------------------------------------
+// The rows of image b are img_off[b] .. img_off[b+1]; every per-image rule of the reference stays per image (finite-row
+// numbering, the boxes.max() + 1 offset, the >= 40000 switch, the clip, the early exit).  Global row-major entry order is
+// already image-major, so ONE ordered compaction serves all images; it also leaves seg_off[b] = candidates in front of
+// image b.  Three stable score passes over all candidates and one stable pass by image id then put every image's segment
+// in descending score order with ties in candidate order; the NMS and the gather / postprocess run one wave per image.
+constexpr int DET_MAX_IMAGES = 16;                      // include/drn_wsod.h DRN_DETECT_MAX_IMAGES
+constexpr long DET_MAX_ENTRIES = (long)SORT_BINS * CAND_TILE;  // DRN_DETECT_BATCH_MAX_ENTRIES: the tile counts live in the histogram area
+
+struct BatchGeom {
+  int img_off[DET_MAX_IMAGES + 1];
+  float h[DET_MAX_IMAGES], w[DET_MAX_IMAGES];    // the candidates are clipped to the image they were predicted on
+  float oh[DET_MAX_IMAGES], ow[DET_MAX_IMAGES];  // detector_postprocess: scale by (sx, sy), clip to (oh, ow), drop empty
+  float sx[DET_MAX_IMAGES], sy[DET_MAX_IMAGES];
+  int n_img;
+};
+
+struct BatchParams {
+  const float* boxes; const float* scores;
+  int M, K, nreg;
+  float thresh;
+  float* c_box; float* c_score; int* c_row; int* c_cls;
+  int* count;       // [1] candidates of all images
+  int* seg_off;     // [n_img + 1]
+  float* maxcoord;  // [n_img]
+  int cap;
+  int* rowmap;      // [M]
+};
+
+__device__ __forceinline__ int image_of(const int* off, int n_img, int v) {
+  int b = 0;
+  while (b + 1 < n_img && v >= off[b + 1]) ++b;
+  return b;
+}
+
+// one workgroup per image: rows_number_kernel on the image's own rows
+__global__ __launch_bounds__(1024) void rows_number_batch_kernel(BatchParams p, BatchGeom g) {
+  __shared__ int wcnt[16];
+  __shared__ int base;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r0 = g.img_off[blockIdx.x], r1 = g.img_off[blockIdx.x + 1];
+  if (threadIdx.x == 0) {
+    base = 0;
+    p.maxcoord[blockIdx.x] = -INFINITY;
+  }
+  __syncthreads();
+  for (int start = r0; start < r1; start += 1024) {
+    const int r = start + threadIdx.x;
+    const bool finite = r < r1 && p.rowmap[r] >= 0;
+    const unsigned long long bal = __ballot(finite);
+    const int wprefix = __popcll(bal & ((1ULL << lane) - 1ULL));
+    if (lane == 0) wcnt[w] = __popcll(bal);
+    __syncthreads();
+    int woff = 0, tot = 0;
+    for (int q = 0; q < 16; ++q) { if (q < w) woff += wcnt[q]; tot += wcnt[q]; }
+    if (r < r1) p.rowmap[r] = finite ? base + woff + wprefix : -1;
+    __syncthreads();
+    if (threadIdx.x == 0) base += tot;
+    __syncthreads();
+  }
+}
+
+// candidates_kernel over the M x K entries of all images.  Pass 1 also leaves seg_off: the thread that holds an image's first entry
+// knows how many candidates lie in front of it.  The largest clipped coordinate is kept per image (integer-bits atomic max: exact
+// whatever the order); a thread whose entries cross an image boundary hands in what it has when the image changes.
+template <int PASS>
+__global__ __launch_bounds__(CAND_THREADS) void candidates_batch_kernel(BatchParams p, BatchGeom g, int* tile_cnt, int ntiles) {
+  __shared__ int wcnt[CAND_THREADS / 64];
+  __shared__ int sbase;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long total = (long)p.M * p.K;
+  const long i0 = (long)blockIdx.x * CAND_TILE + (long)threadIdx.x * CAND_EPT;
+  unsigned flags = 0;
+  float sv[CAND_EPT];
+  int n_mine = 0;
+#pragma unroll
+  for (int e = 0; e < CAND_EPT; ++e) {
+    const long i = i0 + e;
+    sv[e] = 0.f;
+    if (i < total) {
+      const int r = (int)(i / p.K), c = (int)(i - (long)r * p.K);
+      sv[e] = p.scores[(long)r * (p.K + 1) + c];
+      if (p.rowmap[r] >= 0 && sv[e] > p.thresh) flags |= 1u << e, ++n_mine;
+    }
+  }
+  int incl = n_mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += u;
+  }
+  if (lane == 63) wcnt[w] = incl;
+  if (PASS == 1 && threadIdx.x == 0) {
+    int b = 0;
+    for (int t = 0; t < (int)blockIdx.x; ++t) b += tile_cnt[t];
+    sbase = b;
+  }
+  __syncthreads();
+  int woff = 0, tot = 0;
+  for (int q = 0; q < CAND_THREADS / 64; ++q) { if (q < w) woff += wcnt[q]; tot += wcnt[q]; }
+  if (PASS == 0) {
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
+    return;
+  }
+  int pos = sbase + woff + incl - n_mine;
+  int img = -1;
+  bool crossed = false;
+  float mymax = -INFINITY;
+#pragma unroll
+  for (int e = 0; e < CAND_EPT; ++e) {
+    const long i = i0 + e;
+    if (i >= total) break;
+    const int r = (int)(i / p.K), c = (int)(i - (long)r * p.K);
+    if (c == 0)  // the first entry of image b (an image without rows shares it with its successor)
+      for (int b = 0; b < g.n_img; ++b)
+        if (g.img_off[b] == r) p.seg_off[b] = pos;
+    if (flags >> e & 1) {
+      const int b = image_of(g.img_off, g.n_img, r);
+      if (b != img) {
+        if (mymax >= 0.f) atomicMax((int*)p.maxcoord + img, __builtin_bit_cast(int, mymax));
+        crossed = crossed || img >= 0;
+        img = b;
+        mymax = -INFINITY;
+      }
+      if (pos < p.cap) {
+        const float* bx = p.boxes + (long)r * 4 * p.nreg + (p.nreg == 1 ? 0 : 4 * c);
+        const float iw = g.w[b], ih = g.h[b];
+        const float x1 = fminf(fmaxf(bx[0], 0.f), iw), y1 = fminf(fmaxf(bx[1], 0.f), ih);
+        const float x2 = fminf(fmaxf(bx[2], 0.f), iw), y2 = fminf(fmaxf(bx[3], 0.f), ih);
+        p.c_box[4 * (long)pos] = x1; p.c_box[4 * (long)pos + 1] = y1; p.c_box[4 * (long)pos + 2] = x2; p.c_box[4 * (long)pos + 3] = y2;
+        p.c_score[pos] = sv[e]; p.c_row[pos] = p.rowmap[r]; p.c_cls[pos] = c;
+        mymax = fmaxf(mymax, fmaxf(fmaxf(x1, y1), fmaxf(x2, y2)));
+      }
+      ++pos;
+    }
+  }
+  // one atomic per wave where all its candidates lie in one image, one per lane where an image boundary runs through the wave
+  int lo = img < 0 ? DET_MAX_IMAGES : img, hi = img;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = min(lo, __shfl_xor(lo, o, 64));
+    hi = max(hi, __shfl_xor(hi, o, 64));
+  }
+  if (__ballot(crossed) == 0 && lo >= hi) {
+    mymax = wave_max(mymax);
+    if (lane == 0 && hi >= 0 && mymax >= 0.f) atomicMax((int*)p.maxcoord + hi, __builtin_bit_cast(int, mymax));
+  } else if (img >= 0 && mymax >= 0.f) {
+    atomicMax((int*)p.maxcoord + img, __builtin_bit_cast(int, mymax));
+  }
+  if ((int)blockIdx.x == ntiles - 1 && threadIdx.x == 0) {
+    const int n = sbase + tot;
+    p.count[0] = n < p.cap ? n : p.cap;
+    for (int b = 0; b <= g.n_img; ++b)  // images without rows at the end, and the end itself
+      if (g.img_off[b] >= p.M) p.seg_off[b] = n;
+  }
+}
+
+// key[j] = image of the candidate at sorted position j: candidate ids are image-major, seg_off bounds them
+__global__ void image_key_kernel(const int* __restrict__ order, const int* __restrict__ count, const int* __restrict__ seg_off,
+                                 int n_img, unsigned* __restrict__ key) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count[0]) return;
+  key[j] = (unsigned)image_of(seg_off, n_img, order[j]);
+}
+
+// one wave per image on its own segment of the sorted order
+__global__ __launch_bounds__(64) void nms_topk_batch_kernel(NmsParams p, const int* seg_off) {
+  const int b = blockIdx.x, s0 = seg_off[b];
+  nms_topk_wave(p, p.order + s0, seg_off[b + 1] - s0, p.maxcoord + b, p.keep + (long)b * p.topk, p.n_keep + b);
+}
+
+struct PostParams {
+  const float* c_box; const float* c_score; const int* c_row; const int* c_cls;
+  const int* keep; const int* n_keep;
+  int topk, postprocess;
+  float* ob; float* os; int* oc; int* orow; int* ocount;
+};
+
+// one wave per image: drn_detect_gather, then detector_postprocess (scale, clip to the output size, drop boxes with w <= 0 or
+// h <= 0 keeping the order: a ballot prefix), then the fill of the slots at and beyond the count
+__global__ __launch_bounds__(64) void gather_post_kernel(PostParams p, BatchGeom g) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int nk = min(p.n_keep[b], p.topk);
+  const float sx = g.sx[b], sy = g.sy[b], ow = g.ow[b], oh = g.oh[b];
+  const long o0 = (long)b * p.topk;
+  int base = 0;
+  for (int start = 0; start < nk; start += 64) {
+    const int s = start + lane;
+    bool live = s < nk;
+    float x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+    int id = 0;
+    if (live) {
+      id = p.keep[o0 + s];
+      x1 = p.c_box[4 * (long)id]; y1 = p.c_box[4 * (long)id + 1]; x2 = p.c_box[4 * (long)id + 2]; y2 = p.c_box[4 * (long)id + 3];
+      if (p.postprocess) {
+        x1 = x1 * sx; x2 = x2 * sx; y1 = y1 * sy; y2 = y2 * sy;
+        x1 = fminf(fmaxf(x1, 0.f), ow); y1 = fminf(fmaxf(y1, 0.f), oh);
+        x2 = fminf(fmaxf(x2, 0.f), ow); y2 = fminf(fmaxf(y2, 0.f), oh);
+        live = (x2 - x1) > 0.f && (y2 - y1) > 0.f;
+      }
+    }
+    const unsigned long long bal = __ballot(live);
+    if (live) {
+      const long o = o0 + base + __popcll(bal & ((1ULL << lane) - 1ULL));
+      p.ob[4 * o] = x1; p.ob[4 * o + 1] = y1; p.ob[4 * o + 2] = x2; p.ob[4 * o + 3] = y2;
+      p.os[o] = p.c_score[id]; p.oc[o] = p.c_cls[id]; p.orow[o] = p.c_row[id];
+    }
+    base += __popcll(bal);
+  }
+  for (int s = base + lane; s < p.topk; s += 64) {
+    const long o = o0 + s;
+    p.ob[4 * o] = 0.f; p.ob[4 * o + 1] = 0.f; p.ob[4 * o + 2] = 0.f; p.ob[4 * o + 3] = 0.f;
+    p.os[o] = 0.f; p.oc[o] = -1; p.orow[o] = -1;
+  }
+  if (lane == 0) p.ocount[b] = base;
+}
+
+struct BatchWs {
+  int* seg_off; float* maxcoord; int* n_keep; int* keep;
+};
+constexpr long BATCH_WS_HEAD = 512;
+inline long batch_ws_bytes(int cap, int n_img) { return ws_fixed_bytes(cap) + BATCH_WS_HEAD + (long)n_img * NMS_MAXK * 4; }
+inline BatchWs carve_batch(void* workspace, int cap) {
+  char* w = (char*)workspace + ws_fixed_bytes(cap);
+  return BatchWs{(int*)w, (float*)(w + 128), (int*)(w + 256), (int*)(w + BATCH_WS_HEAD)};
+}
+
+// ---- padded blocks -> packed detections -------------------------------------------------------------------------------
+// off[b] = sum of the counts (held to 0 .. topk) in front of block b, off[B] = n: one workgroup
+__global__ __launch_bounds__(1024) void compact_offsets_kernel(const int* __restrict__ count, int B, int topk, int* __restrict__ off,
+                                                               int* __restrict__ out_n) {
+  __shared__ int wsum[16];
+  __shared__ int base;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (threadIdx.x == 0) base = 0;
+  __syncthreads();
+  for (int start = 0; start < B; start += 1024) {
+    const int b = start + threadIdx.x;
+    const int c = b < B ? min(max(count[b], 0), topk) : 0;
+    int incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    int woff = 0, tot = 0;
+    for (int q = 0; q < 16; ++q) { if (q < w) woff += wsum[q]; tot += wsum[q]; }
+    if (b < B) off[b] = base + woff + incl - c;
+    __syncthreads();
+    if (threadIdx.x == 0) base += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { off[B] = base; out_n[0] = base; }
+}
+
+__global__ __launch_bounds__(64) void compact_gather_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                            const int* __restrict__ classes, const int* __restrict__ image_index,
+                                                            const int* __restrict__ off, int topk, float* __restrict__ ob,
+                                                            float* __restrict__ os, int* __restrict__ oc, int* __restrict__ oi) {
+  const int b = blockIdx.x;
+  const int o0 = off[b], n = off[b + 1] - o0, im = image_index[b];
+  for (int s = threadIdx.x; s < n; s += 64) {
+    const long i = (long)b * topk + s, o = o0 + s;
+    for (int e = 0; e < 4; ++e) ob[4 * o + e] = boxes[4 * i + e];
+    os[o] = scores[i]; oc[o] = classes[i]; oi[o] = im;
+  }
 }
 
 }  // namespace
@@ -337,6 +611,102 @@ int drn_detect_gather(const void* workspace, long workspace_bytes, int cap, cons
   Ws k = carve((void*)workspace, workspace_bytes, cap);
   hipLaunchKernelGGL(gather_kernel, dim3((topk + 63) / 64), dim3(64), 0, (hipStream_t)stream, k.c_box, k.c_score,
                      k.c_row, k.c_cls, keep_ids, n_keep, out_boxes, out_scores, out_classes, out_rows);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// bytes of scratch drn_detect_topk_batch needs for n_images images with total_cap = M * K entries in all
+long drn_detect_batch_workspace_bytes(int total_cap, int n_images) {
+  return batch_ws_bytes(total_cap < 1 ? 1 : total_cap, n_images < 1 ? 1 : n_images) + 256;
+}
+
+// All images of a call (see include/drn_wsod.h).  img_off_host [n_images + 1] and geom_host [n_images][6] =
+// (h, w, out_h, out_w, sx, sy) are HOST arrays, read before the call returns.  Nothing is read back from the device.
+int drn_detect_topk_batch(const float* boxes, const float* scores, const int* img_off_host, int n_images, int K, int nreg,
+                          const float* geom_host, int postprocess, float score_thresh, float nms_thresh, int topk,
+                          void* workspace, long workspace_bytes, int total_cap, float* out_boxes, float* out_scores,
+                          int* out_classes, int* out_rows, int* out_count, void* stream) {
+  if (!boxes || !scores || !img_off_host || !geom_host || !workspace || !out_boxes || !out_scores || !out_classes ||
+      !out_rows || !out_count || topk < 1 || topk > NMS_MAXK || total_cap < 1 || K < 1)
+    return DRN_ERR_ARG;
+  if (nreg != 1 && nreg != K) return DRN_ERR_ARG;
+  if (n_images < 1 || n_images > DET_MAX_IMAGES) return DRN_ERR_UNSUPPORTED;
+  BatchGeom g{};
+  g.n_img = n_images;
+  if (img_off_host[0] != 0) return DRN_ERR_ARG;
+  for (int b = 0; b <= n_images; ++b) {
+    g.img_off[b] = img_off_host[b];
+    if (b > 0 && img_off_host[b] < img_off_host[b - 1]) return DRN_ERR_ARG;
+  }
+  for (int b = n_images + 1; b <= DET_MAX_IMAGES; ++b) g.img_off[b] = img_off_host[n_images];
+  for (int b = 0; b < n_images; ++b) {
+    const float* q = geom_host + 6 * b;
+    g.h[b] = q[0]; g.w[b] = q[1]; g.oh[b] = q[2]; g.ow[b] = q[3]; g.sx[b] = q[4]; g.sy[b] = q[5];
+  }
+  const int M = img_off_host[n_images];
+  const long total = (long)M * K;
+  if (total > DET_MAX_ENTRIES) return DRN_ERR_UNSUPPORTED;
+  if ((long)total_cap < total || total_cap > DET_MAX_ENTRIES) return DRN_ERR_ARG;
+  const int cap = total_cap;
+  if (workspace_bytes < drn_detect_batch_workspace_bytes(cap, n_images)) return DRN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Ws k = carve(workspace, workspace_bytes, cap);
+  BatchWs bw = carve_batch(workspace, cap);
+  CandParams fp{boxes, scores, M, K, nreg, 0.f, 0.f, score_thresh, k.c_box, k.c_score, k.c_row, k.c_cls, k.count,
+                k.maxcoord, cap, (int*)k.key0};  // key0 doubles as the row map until the sort's second pass overwrites it
+  BatchParams bp{boxes, scores, M, K, nreg, score_thresh, k.c_box, k.c_score, k.c_row, k.c_cls, k.count, bw.seg_off,
+                 bw.maxcoord, cap, (int*)k.key0};
+  if (M > 0) hipLaunchKernelGGL(rows_finite_kernel, dim3((M + 3) / 4), dim3(256), 0, st, fp);
+  hipLaunchKernelGGL(rows_number_batch_kernel, dim3(n_images), dim3(1024), 0, st, bp, g);
+  const int ntiles = (int)((total + CAND_TILE - 1) / CAND_TILE);
+  if (ntiles > 0) {
+    hipLaunchKernelGGL(candidates_batch_kernel<0>, dim3(ntiles), dim3(CAND_THREADS), 0, st, bp, g, k.hist, ntiles);
+    hipLaunchKernelGGL(candidates_batch_kernel<1>, dim3(ntiles), dim3(CAND_THREADS), 0, st, bp, g, k.hist, ntiles);
+  } else {
+    (void)hipMemsetAsync(k.count, 0, sizeof(int), st);
+    (void)hipMemsetAsync(bw.seg_off, 0, sizeof(int) * (DET_MAX_IMAGES + 1), st);
+  }
+  // stable descending by score over all candidates: -> key1/order -> key0/val0 -> key1/order; then stable by image: -> key0/val0
+  const int tiles = sort_tiles(cap);
+  const int shifts[3] = {0, 11, 22}, bits[3] = {11, 11, 10};
+  for (int ps = 0; ps < 3; ++ps) {
+    const bool even = (ps & 1) == 0;
+    SortPass sp{k.c_score, even ? k.key0 : k.key1, even ? k.val0 : k.order, even ? k.key1 : k.key0,
+                even ? k.order : k.val0, k.hist, k.count, tiles, shifts[ps], bits[ps], ps == 0};
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  }
+  hipLaunchKernelGGL(image_key_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, k.order, k.count, bw.seg_off, n_images,
+                     k.key1);
+  {
+    SortPass sp{nullptr, k.key1, k.order, k.key0, k.val0, k.hist, k.count, tiles, 0, 4, 0};  // 4 bits: DET_MAX_IMAGES = 16
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  }
+  NmsParams np{k.c_box, k.c_score, k.c_cls, k.val0, k.count, bw.maxcoord, nms_thresh, topk, 40000, bw.keep, bw.n_keep};
+  hipLaunchKernelGGL(nms_topk_batch_kernel, dim3(n_images), dim3(64), 0, st, np, (const int*)bw.seg_off);
+  PostParams pp{k.c_box, k.c_score, k.c_row, k.c_cls, bw.keep, bw.n_keep, topk, postprocess ? 1 : 0, out_boxes, out_scores,
+                out_classes, out_rows, out_count};
+  hipLaunchKernelGGL(gather_post_kernel, dim3(n_images), dim3(64), 0, st, pp, g);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// n_blocks padded blocks of topk slots -> the live slots packed in block order then slot order; offsets [n_blocks + 1] is scratch
+int drn_detect_compact(const float* boxes, const float* scores, const int* classes, const int* count, const int* image_index,
+                       int n_blocks, int topk, int* offsets, float* out_boxes, float* out_scores, int* out_classes,
+                       int* out_images, int* out_n, void* stream) {
+  if (!out_n || !offsets || n_blocks < 0 || topk < 1) return DRN_ERR_ARG;
+  if (n_blocks > 0 && (!boxes || !scores || !classes || !count || !image_index || !out_boxes || !out_scores ||
+                       !out_classes || !out_images))
+    return DRN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(compact_offsets_kernel, dim3(1), dim3(1024), 0, st, count, n_blocks, topk, offsets, out_n);
+  if (n_blocks > 0)
+    hipLaunchKernelGGL(compact_gather_kernel, dim3(n_blocks), dim3(64), 0, st, boxes, scores, classes, image_index,
+                       (const int*)offsets, topk, out_boxes, out_scores, out_classes, out_images);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

@@ -16,6 +16,7 @@ COCO box AP: `COCOEvaluator` (detectron2/evaluation/coco_evaluation.py:33-306, b
 (detectron2/layers/csrc/cocoeval/cocoeval.cpp); here both run on the device (ops.coco_match / ops.coco_accumulate,
 csrc/cocoeval.hip) and the predictions never leave it before the three result arrays are read back.  Pinned by
 tests/golden/coco_eval.npz (the unmodified C++ on synthetic, tie-heavy annotation sets)."""
+import contextlib
 import json
 import os
 import xml.etree.ElementTree as ET
@@ -24,7 +25,134 @@ from collections import OrderedDict, defaultdict
 import numpy as np
 
 __all__ = ["PascalVOCDetectionEvaluator", "parse_rec", "voc_ap", "voc_eval", "voc_eval_corloc", "format_prediction",
-           "COCOEvaluator", "instances_to_coco_json", "coco_params", "coco_summarize", "derive_coco_results"]
+           "COCOEvaluator", "instances_to_coco_json", "coco_params", "coco_summarize", "derive_coco_results",
+           "inference_on_dataset", "inference_context", "DatasetEvaluators"]
+
+
+# ---- the dataset loop (detectron2/evaluation/evaluator.py:64-200) ------------------------------------------------------
+
+class DatasetEvaluators:
+    """Several evaluators behind one reset() / process() / evaluate(): every call goes to each of them in turn; evaluate()
+    merges their result dicts (a key that two of them return is an error; a None result - not the main process - adds
+    nothing)."""
+
+    def __init__(self, evaluators):
+        self._evaluators = list(evaluators)
+
+    def reset(self):
+        for ev in self._evaluators:
+            ev.reset()
+
+    def process(self, inputs, outputs):
+        for ev in self._evaluators:
+            ev.process(inputs, outputs)
+
+    def evaluate(self):
+        merged = OrderedDict()
+        for ev in self._evaluators:
+            res = ev.evaluate()
+            for key, val in (res or {}).items():
+                assert key not in merged, "Different evaluators produce results with the same key {}".format(key)
+                merged[key] = val
+        return merged
+
+
+@contextlib.contextmanager
+def inference_context(model):
+    """The model in eval mode inside the block, its previous mode afterwards - also when the block raises."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def inference_on_dataset(model, data_loader, evaluator):
+    """evaluator.reset(); evaluator.process(inputs, model(inputs)) for every element of data_loader with the model in eval mode
+    and without autograd; the result of evaluator.evaluate(), {} where that is None (not the main process).  evaluator=None
+    only runs the model.  The reference's timing / ETA log lines are not rebuilt - they synchronise after every image.
+    Whatever the model returns goes to process() as it is: a padded model (GeneralizedRCNNWithTTAAVG(padded=True), or a wrapper
+    around model.inference(padded=True)) with a device evaluator makes a loop in which nothing between reset() and evaluate()
+    reads the device, so the host prepares image i+1 while image i's kernels run."""
+    import torch
+
+    if evaluator is None:
+        evaluator = DatasetEvaluators([])
+    evaluator.reset()
+    with inference_context(model), torch.no_grad():
+        for inputs in data_loader:
+            evaluator.process(inputs, model(inputs))
+    results = evaluator.evaluate()
+    return {} if results is None else results
+
+
+def _is_padded(outputs):
+    return hasattr(outputs, "to_outputs") and hasattr(outputs, "count")
+
+
+def _padded_block(index, inputs, outputs):
+    """process() of a DetectionBatch on the device path: the blocks are kept as they are (no read of the count)"""
+    import torch
+
+    if len(inputs) != len(outputs):
+        raise ValueError("%d inputs for a DetectionBatch of %d images" % (len(inputs), len(outputs)))
+    if outputs.boxes.dtype != torch.float32 or outputs.scores.dtype != torch.float32:
+        raise TypeError("DetectionBatch blocks are float32, got %s / %s" % (outputs.boxes.dtype, outputs.scores.dtype))
+    return ("padded", outputs.boxes, outputs.scores, outputs.classes, outputs.count, list(index))
+
+
+def _entries_in_order(ev):
+    """the per-image entries and the padded blocks of an evaluator, interleaved in processing order"""
+    out, at = [], 0
+    for pos, block in ev._padded:
+        out += [("list", ev._boxes[k], ev._scores[k], ev._classes[k], ev._images[k]) for k in range(at, pos)]
+        out.append(block)
+        at = pos
+    out += [("list", ev._boxes[k], ev._scores[k], ev._classes[k], ev._images[k]) for k in range(at, len(ev._boxes))]
+    return out
+
+
+def _pack_entries(entries, device):
+    """The processed predictions in processing order, packed on the device: boxes [n, 4] f32, scores [n] f32, classes [n] i32,
+    image index [n] i32.  `entries` mixes ("list", boxes, scores, classes, image) of one image each and padded blocks
+    ("padded", boxes, scores, classes, count, images); each run of consecutive padded blocks is packed by ONE
+    ops.detections_compact and costs one 4-byte read of its n."""
+    import torch
+
+    from . import ops
+
+    parts, i = [], 0
+    while i < len(entries):
+        j = i
+        while j < len(entries) and entries[j][0] == entries[i][0]:
+            j += 1
+        run = entries[i:j]
+        if run[0][0] == "list":
+            counts = torch.tensor([e[1].shape[0] for e in run])
+            img = torch.repeat_interleave(torch.tensor([e[4] for e in run], dtype=torch.int32), counts).to(device)
+            parts.append((torch.cat([e[1].float().reshape(-1, 4) for e in run]), torch.cat([e[2].float() for e in run]),
+                          torch.cat([e[3] for e in run]).to(torch.int32), img))
+        else:
+            topk = max(e[2].shape[1] for e in run)
+
+            def pad(t, fill):  # blocks of different capacity (evaluations that mix models): widen to the largest
+                if t.shape[1] == topk:
+                    return t
+                wide = t.new_full((t.shape[0], topk) + tuple(t.shape[2:]), fill)
+                wide[:, : t.shape[1]] = t
+                return wide
+
+            images = torch.tensor([v for e in run for v in e[5]], dtype=torch.int32).to(device, non_blocking=True)
+            ob, os_, oc, oi, n = ops.detections_compact(torch.cat([pad(e[1], 0) for e in run]), torch.cat([pad(e[2], 0) for e in run]),
+                                                        torch.cat([pad(e[3], -1) for e in run]).to(torch.int32),
+                                                        torch.cat([e[4] for e in run]).to(torch.int32), images)
+            n = int(n.item())  # the one extra read of evaluate()
+            parts.append((ob[:n], os_[:n], oc[:n], oi[:n]))
+        i = j
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(torch.cat([p[k] for p in parts]) for k in range(4))
 
 
 def parse_rec(filename):
@@ -193,10 +321,17 @@ class PascalVOCDetectionEvaluator:
     def reset(self):
         self._predictions = defaultdict(list)
         self._boxes, self._scores, self._classes, self._images = [], [], [], []
+        self._padded = []  # (number of per-image entries in front of it, padded block): DetectionBatch outputs, device path
 
     def process(self, inputs, outputs):
+        """outputs: a list of {"instances": Instances} or a structures.DetectionBatch (both may be mixed in one evaluation;
+        processing order defines the tie order either way).  On the device path a DetectionBatch is kept as padded blocks
+        without a read of its count; evaluate() packs them with ops.detections_compact, which costs one extra 4-byte read
+        of n per run of consecutive padded blocks.  The host path converts it with to_outputs()."""
         if self._device is not None:
             return self._process_device(inputs, outputs)
+        if _is_padded(outputs):
+            outputs = outputs.to_outputs()
         for inp, out in zip(inputs, outputs):
             inst = out["instances"]
             boxes = inst.pred_boxes.tensor.detach().cpu().numpy()
@@ -207,6 +342,13 @@ class PascalVOCDetectionEvaluator:
         import torch
 
         narrow = (torch.float32, torch.float16, torch.bfloat16)
+        if _is_padded(outputs):
+            for inp in inputs:
+                if inp["image_id"] not in self._img_index:
+                    raise ValueError("image_id %r is not in the annotations" % (inp["image_id"],))
+            self._padded.append((len(self._boxes), _padded_block([self._img_index[inp["image_id"]] for inp in inputs],
+                                                                 inputs, outputs)))
+            return
         for inp, out in zip(inputs, outputs):
             if inp["image_id"] not in self._img_index:
                 raise ValueError("image_id %r is not in the annotations" % (inp["image_id"],))
@@ -253,6 +395,8 @@ class PascalVOCDetectionEvaluator:
         (both widened exactly), classes, image index"""
         import torch
 
+        if self._padded:
+            return _pack_entries(_entries_in_order(self), self._padded[0][1][1].device)
         dev = self._boxes[0].device if self._boxes else torch.device(self._device)
         if not self._boxes:
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
@@ -402,8 +546,19 @@ class COCOEvaluator:
 
     def reset(self):
         self._boxes, self._scores, self._classes, self._images = [], [], [], []
+        self._padded = []  # (number of per-image entries in front of it, padded block): DetectionBatch outputs
 
     def process(self, inputs, outputs):
+        """outputs: a list of {"instances": Instances} or a structures.DetectionBatch, which is kept as padded blocks without
+        a read of its count (both may be mixed; evaluate() packs the blocks with ops.detections_compact at the price of one
+        extra 4-byte read of n per run of consecutive padded blocks)."""
+        if _is_padded(outputs):
+            for inp in inputs:
+                if int(inp["image_id"]) not in self._img_index:
+                    raise ValueError("image_id %r is not in the annotation file" % (inp["image_id"],))
+            self._padded.append((len(self._boxes), _padded_block([self._img_index[int(inp["image_id"])] for inp in inputs],
+                                                                 inputs, outputs)))
+            return
         for inp, out in zip(inputs, outputs):
             iid = int(inp["image_id"])
             if iid not in self._img_index:
@@ -418,6 +573,8 @@ class COCOEvaluator:
         """this rank's predictions, concatenated on the device: boxes [n, 4] f32 XYXY, scores [n] f32, classes, image index"""
         import torch
 
+        if self._padded:
+            return _pack_entries(_entries_in_order(self), self._padded[0][1][1].device)
         dev = self._boxes[0].device if self._boxes else torch.device(self._device)
         if not self._boxes:
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)

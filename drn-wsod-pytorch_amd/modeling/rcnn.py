@@ -1,6 +1,7 @@
 """GeneralizedRCNNWSL (projects/WSL/wsl/modeling/meta_arch/rcnn.py:23-325) — same registry name, constructor
 and call contract: `model(batched_inputs) -> dict[str, Tensor]` when training, `list[{"instances": Instances}]`
-in eval, `model.inference(batched_inputs, detected_instances=None, do_postprocess=True)`."""
+in eval, `model.inference(batched_inputs, detected_instances=None, do_postprocess=True, padded=False)` (`padded=True`: a
+`structures.DetectionBatch` from the batched, sync-free inference tail instead of the list)."""
 from typing import Optional, Tuple
 
 import torch
@@ -173,13 +174,26 @@ class GeneralizedRCNNWSL(nn.Module):
         losses.update(detector_losses)
         return losses
 
-    def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
+    def inference(self, batched_inputs, detected_instances=None, do_postprocess=True, padded=False):
+        """padded=True: the heads run the batched inference tail once for all images and the first return value is a
+        DetectionBatch - in output coordinates with do_postprocess (detector_postprocess runs inside the tail's last kernel),
+        raw otherwise - and nothing between the inputs and the result reads the device."""
         assert not self.training
         assert detected_instances is None, "forward_with_given_boxes is off this path"
         with torch.no_grad():
             images = self.preprocess_image(batched_inputs)
             features = self.backbone(images.tensor)
             proposals = self._proposals(batched_inputs)
+            if padded:
+                sizes = None
+                if do_postprocess:
+                    sizes = [(inp.get("height", s[0]), inp.get("width", s[1])) for inp, s in zip(batched_inputs, images.image_sizes)]
+                prev, self.roi_heads.padded_tail = self.roi_heads.padded_tail, {"output_sizes": sizes}
+                try:
+                    results, _, all_scores, all_boxes = self.roi_heads(images, features, proposals, None)
+                finally:
+                    self.roi_heads.padded_tail = prev
+                return results if do_postprocess else (results, all_scores, all_boxes)
             results, _, all_scores, all_boxes = self.roi_heads(images, features, proposals, None)
         if do_postprocess:
             return GeneralizedRCNNWSL._postprocess(results, batched_inputs, images.image_sizes)

@@ -29,9 +29,36 @@ from ..config import configurable
 from ..events import get_event_storage, has_event_storage
 from ..layers import Linear, ROIAlign, RoIPool, ShapeSpec, to_nhwc
 from ..registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
-from ..structures import Boxes, Instances
+from ..structures import Boxes, DetectionBatch, Instances
 # (re-exported: roi_heads._HeadEngine / _TrainFn and the dropout-seed rule still resolve here)
 from .head_engine import DROP_COUNTER_STEP, FC7_SEED_OFFSET, _HeadEngine, _TrainFn, dropout_seeds  # noqa: F401
+
+
+def padded_detections(boxes, scores, nper, image_sizes, output_sizes, score_thresh, nms_thresh, topk):
+    """The batched inference tail (ops.detect_topk_batch) on the rows of len(nper) images, as a DetectionBatch: raw (in
+    `image_sizes` coordinates) when output_sizes is None, else after detector_postprocess to `output_sizes`.  Batches beyond
+    the entry's limits are chunked here: the launch count then depends on the number of chunks alone.  No host read."""
+    K = scores.shape[1] - 1
+    chunks, lo, n_img = [], 0, len(nper)
+    while lo < n_img:
+        hi = lo + 1
+        while (hi < n_img and hi - lo < ops.DETECT_MAX_IMAGES
+               and sum(nper[lo: hi + 1]) * K <= ops.DETECT_BATCH_MAX_ENTRIES):
+            hi += 1
+        chunks.append((lo, hi))
+        lo = hi
+    parts, r0 = [], 0
+    for lo, hi in chunks:
+        rows = sum(nper[lo:hi])
+        off = [0]
+        for n in nper[lo:hi]:
+            off.append(off[-1] + n)
+        parts.append(ops.detect_topk_batch(boxes[r0: r0 + rows], scores[r0: r0 + rows], off, image_sizes[lo:hi],
+                                           None if output_sizes is None else output_sizes[lo:hi],
+                                           score_thresh=score_thresh, nms_thresh=nms_thresh, topk=topk))
+        r0 += rows
+    ob, os_, oc, orow, cnt = parts[0] if len(parts) == 1 else (torch.cat(t) for t in zip(*parts))
+    return DetectionBatch(ob, os_, oc, cnt, image_sizes if output_sizes is None else output_sizes, topk, rows=orow)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -413,6 +440,7 @@ class OICRROIHeads(ROIHeads):
         self._zero_oh = None     # cached zero label matrix of the WSDDN inference scores
         self._prefetched = None  # what prefetch_pooled() returned for the batch of this forward
         self.scores_only = False  # GeneralizedRCNNWithTTAAVG: inference returns all_scores / all_boxes alone
+        self.padded_tail = None   # GeneralizedRCNNWSL.inference(padded=True): a dict while the batched tail is asked for
         self._engine = _HeadEngine(self)
 
     @classmethod
@@ -623,6 +651,16 @@ class OICRROIHeads(ROIHeads):
                 all_scores.append(s.unsqueeze(0))
                 all_boxes.append(b.unsqueeze(0))
             return None, all_scores, all_boxes
+        if self.padded_tail is not None:
+            # GeneralizedRCNNWSL.inference(padded=True): ONE launch chain for all images, no host read; the value holds the
+            # output sizes of detector_postprocess (applied on the device) or None for the raw tail
+            results = padded_detections(boxes, probs, nper, [p.image_size for p in proposals],
+                                        self.padded_tail.get("output_sizes"), last.test_score_thresh, last.test_nms_thresh,
+                                        last.test_topk_per_image)
+            for s, b in zip(probs.split(nper), boxes.split(nper)):
+                all_scores.append(s.unsqueeze(0))
+                all_boxes.append(b.unsqueeze(0))
+            return results, all_scores, all_boxes
         for p, s, b in zip(proposals, probs.split(nper), boxes.split(nper)):
             ob, os_, oc, _ = ops.detect_topk(b, s, p.image_size, last.test_score_thresh, last.test_nms_thresh,
                                              last.test_topk_per_image)

@@ -17,7 +17,8 @@ from torch import nn
 
 from .. import ops
 from .._cabi import DrnError
-from ..structures import Boxes, Instances
+from ..structures import Boxes, DetectionBatch, Instances
+from .roi_heads import padded_detections
 
 __all__ = ["DatasetMapperTTAAVG", "GeneralizedRCNNWithTTAAVG", "resize_shortest_edge_shape"]
 
@@ -205,7 +206,9 @@ class DatasetMapperTTAAVG:
 class GeneralizedRCNNWithTTAAVG(nn.Module):
     """test_time_augmentation_avg.py:139-321 (box branch; masks / keypoints are off the WSL path)."""
 
-    def __init__(self, cfg, model, tta_mapper=None, batch_size=1):
+    def __init__(self, cfg, model, tta_mapper=None, batch_size=1, padded=False):
+        """padded=True: __call__ returns a DetectionBatch (one image per input, the merge through the batched tail with N = 1)
+        instead of a list of dicts, and reads nothing back from the device."""
         super().__init__()
         from .rcnn import GeneralizedRCNNWSL
 
@@ -221,6 +224,7 @@ class GeneralizedRCNNWithTTAAVG(nn.Module):
         self.model = model
         self.tta_mapper = tta_mapper if tta_mapper is not None else DatasetMapperTTAAVG(cfg, device=model.device)
         self.batch_size = batch_size
+        self.padded = bool(padded)
 
     def __call__(self, batched_inputs):
         out = []
@@ -231,6 +235,12 @@ class GeneralizedRCNNWithTTAAVG(nn.Module):
             if "height" not in ret and "width" not in ret:
                 ret["height"], ret["width"] = x["image"].shape[1], x["image"].shape[2]
             out.append(self._inference_one_image(ret))
+        if self.padded:
+            if len(out) == 1:
+                return out[0]
+            cat = lambda name: torch.cat([getattr(b, name) for b in out])
+            return DetectionBatch(cat("boxes"), cat("scores"), cat("classes"), cat("count"),
+                                  [b.image_sizes[0] for b in out], out[0].topk, rows=cat("rows"))
         return out
 
     def _get_augmented_boxes(self, augmented_inputs):
@@ -270,6 +280,10 @@ class GeneralizedRCNNWithTTAAVG(nn.Module):
             augmented_inputs = self.tta_mapper(input)
             all_boxes, all_scores = self._get_augmented_boxes(augmented_inputs)
             # _merge_detections (:296-309) = fast_rcnn_inference_single_image on the averages
+            if self.padded:  # the same tail, padded and without the read of the count (merged instances are not postprocessed)
+                return padded_detections(all_boxes, all_scores, [all_scores.shape[0]], [orig_shape], None,
+                                         self.cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST, self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST,
+                                         self.cfg.TEST.DETECTIONS_PER_IMAGE)
             ob, os_, oc, _ = ops.detect_topk(all_boxes, all_scores, orig_shape, self.cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST,
                                              self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST, self.cfg.TEST.DETECTIONS_PER_IMAGE)
         r = Instances(orig_shape)

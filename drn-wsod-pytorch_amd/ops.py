@@ -1371,6 +1371,82 @@ def detect_topk(boxes, scores, image_shape, score_thresh, nms_thresh, topk):
     return ob[:n], os_[:n], oc[:n].long(), orow[:n].long()
 
 
+DETECT_MAX_IMAGES, DETECT_BATCH_MAX_ENTRIES = 16, 4194304  # include/drn_wsod.h DRN_DETECT_MAX_IMAGES / _BATCH_MAX_ENTRIES
+
+
+def detect_topk_batch(boxes, scores, img_off, image_sizes, output_sizes=None, *, score_thresh, nms_thresh, topk):
+    """The inference tail of all images of a call in one launch chain, without a host read (drn_detect_topk_batch).
+    boxes [M, 4*nreg] f32, scores [M, K+1] f32 with the rows of image i contiguous; img_off: N+1 HOST ints; image_sizes: N (h, w) to
+    clip to; output_sizes: N (h, w) - detector_postprocess to that size is applied on the device - or None for the raw tail.
+    Returns padded device tensors (boxes [N, topk, 4] f32, scores [N, topk] f32, classes [N, topk] i32, rows [N, topk] i32,
+    count [N] i32): image i's first count[i] slots are detect_topk (+ detector_postprocess) on its rows, bit for bit; the slots
+    beyond hold 0 / 0 / -1 / -1.  More than DETECT_MAX_IMAGES images or DETECT_BATCH_MAX_ENTRIES = M * K entries raise DrnError
+    before any launch: callers chunk."""
+    if torch.is_tensor(img_off):
+        if img_off.is_cuda:
+            raise C.DrnError("detect_topk_batch: img_off is known on the host; a device tensor would have to be read back")
+        img_off = img_off.tolist()
+    off = [int(v) for v in img_off]
+    n_img = len(off) - 1
+    M, K = scores.shape[0], scores.shape[1] - 1
+    nreg = boxes.shape[1] // 4
+    if not 1 <= n_img <= DETECT_MAX_IMAGES:
+        raise C.DrnError("detect_topk_batch: %d images, 1 .. %d per call are built (chunk the batch)" % (n_img, DETECT_MAX_IMAGES))
+    if M * K > DETECT_BATCH_MAX_ENTRIES:
+        raise C.DrnError("detect_topk_batch: %d x %d entries, at most %d per call are built (chunk the batch)"
+                         % (M, K, DETECT_BATCH_MAX_ENTRIES))
+    if not 1 <= int(topk) <= 1024:
+        raise C.DrnError("detect_topk_batch: topk = %d, 1 .. 1024 are built" % topk)
+    if off[0] != 0 or off[-1] != M or any(b < a for a, b in zip(off[:-1], off[1:])) or boxes.shape[0] != M or K < 1:
+        raise C.DrnError("detect_topk_batch: img_off %s does not split %d rows into %d images" % (off, M, n_img))
+    if len(image_sizes) != n_img or (output_sizes is not None and len(output_sizes) != n_img):
+        raise C.DrnError("detect_topk_batch: one (h, w) per image")
+    geom = []
+    for i, (h, w) in enumerate(image_sizes):
+        oh, ow = output_sizes[i] if output_sizes is not None else (h, w)
+        # detector_postprocess forms the scales in double; Boxes.scale rounds them to fp32 once (ctypes does the same here)
+        geom += [h, w, oh, ow, ow / w, oh / h]
+    dev = boxes.device
+    cap = max(M * K, 1)
+    nbytes = C.lib().drn_detect_batch_workspace_bytes(cap, n_img)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    boxes = boxes.contiguous().float()
+    scores = scores.contiguous().float()
+    ob = torch.empty((n_img, topk, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((n_img, topk), dtype=torch.float32, device=dev)
+    oc = torch.empty((n_img, topk), dtype=torch.int32, device=dev)
+    orow = torch.empty((n_img, topk), dtype=torch.int32, device=dev)
+    cnt = torch.empty((n_img,), dtype=torch.int32, device=dev)
+    C.call("drn_detect_topk_batch", C.ptr(boxes), C.ptr(scores), ctypes.cast(C.host_ints(off), ctypes.c_void_p), n_img, K, nreg,
+           ctypes.cast(C.host_floats(geom), ctypes.c_void_p), int(output_sizes is not None), float(score_thresh),
+           float(nms_thresh), int(topk), C.ptr(ws), nbytes, cap, C.ptr(ob), C.ptr(os_), C.ptr(oc), C.ptr(orow), C.ptr(cnt),
+           C.stream())
+    return ob, os_, oc, orow, cnt
+
+
+def detections_compact(boxes, scores, classes, count, image_index):
+    """Padded blocks -> packed detections on the device (drn_detect_compact): boxes [B, topk, 4] f32, scores [B, topk] f32,
+    classes [B, topk] i32, count [B] i32, image_index [B] i32 -> (boxes [B*topk, 4], scores, classes, images [B*topk], n [1] i32):
+    the first n rows are the live slots in block order then slot order, the rows beyond are zero.  No host read: n stays on the
+    device."""
+    B, topk = scores.shape[0], scores.shape[1]
+    dev = scores.device
+    assert boxes.shape == (B, topk, 4) and classes.shape == (B, topk) and count.shape == (B,) and image_index.shape == (B,)
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32
+    assert classes.dtype == torch.int32 and count.dtype == torch.int32 and image_index.dtype == torch.int32
+    boxes, scores, classes = boxes.contiguous(), scores.contiguous(), classes.contiguous()
+    count, image_index = count.contiguous(), image_index.contiguous()
+    ob = torch.zeros((B * topk, 4), dtype=torch.float32, device=dev)
+    os_ = torch.zeros((B * topk,), dtype=torch.float32, device=dev)
+    oc = torch.zeros((B * topk,), dtype=torch.int32, device=dev)
+    oi = torch.zeros((B * topk,), dtype=torch.int32, device=dev)
+    offs = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    n = torch.empty((1,), dtype=torch.int32, device=dev)
+    C.call("drn_detect_compact", C.ptr(boxes), C.ptr(scores), C.ptr(classes), C.ptr(count), C.ptr(image_index), B, max(topk, 1),
+           C.ptr(offs), C.ptr(ob), C.ptr(os_), C.ptr(oc), C.ptr(oi), C.ptr(n), C.stream())
+    return ob, os_, oc, oi, n
+
+
 def tta_accumulate(boxes, scores, acc_boxes, acc_scores, sx, sy, flip_w, first, n_final):
     """fold one augmentation's [R, 4K] boxes / [R, K+1] scores into the running TTA averages (see the header)"""
     assert boxes.is_contiguous() and scores.is_contiguous() and boxes.dtype == torch.float32 and scores.dtype == torch.float32

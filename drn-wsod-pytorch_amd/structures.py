@@ -200,3 +200,38 @@ class ImageList:
     @property
     def device(self):
         return self.tensor.device
+
+
+class DetectionBatch:
+    """The detections of N images as padded, fixed-capacity device blocks with a device-side count - what the batched
+    inference tail (ops.detect_topk_batch) leaves and what the device evaluators keep until evaluate(): boxes [N, topk, 4] f32,
+    scores [N, topk] f32, classes [N, topk] i32, rows [N, topk] i32 (row of the detection within its image, or None), count [N] i32;
+    image i's detections are its first count[i] slots.  `image_sizes` are the (h, w) the boxes are expressed in (the output
+    sizes after the postprocess).  A plain holder: to_instances() / to_outputs() are the only readers of `count`, one read for
+    the whole batch each."""
+
+    def __init__(self, boxes, scores, classes, count, image_sizes, topk=None, rows=None):
+        self.boxes, self.scores, self.classes, self.rows, self.count = boxes, scores, classes, rows, count
+        self.image_sizes = [tuple(s) for s in image_sizes]
+        self.topk = int(scores.shape[1]) if topk is None else int(topk)
+        assert boxes.shape == (len(self.image_sizes), self.topk, 4) and scores.shape == (len(self.image_sizes), self.topk)
+        assert classes.shape == scores.shape and count.shape == (len(self.image_sizes),)
+
+    def __len__(self):
+        return len(self.image_sizes)
+
+    def to_instances(self) -> List["Instances"]:
+        out = []
+        for i, n in enumerate(self.count.tolist()):  # the one read
+            r = Instances(self.image_sizes[i])
+            r.pred_boxes = Boxes(self.boxes[i, :n])
+            r.scores = self.scores[i, :n]
+            r.pred_classes = self.classes[i, :n].long()
+            out.append(r)
+        return out
+
+    def to_outputs(self) -> List[Dict[str, "Instances"]]:
+        return [{"instances": r} for r in self.to_instances()]
+
+    def __repr__(self):
+        return "DetectionBatch(num_images={}, topk={}, image_sizes={})".format(len(self), self.topk, self.image_sizes)

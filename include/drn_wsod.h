@@ -746,6 +746,37 @@ int drn_detect_topk(const float* boxes, const float* scores, int R, int K, int n
 int drn_detect_gather(const void* workspace, long workspace_bytes, int cap, const int* keep_ids, const int* n_keep,
                       int topk, float* out_boxes, float* out_scores, int* out_classes, int* out_rows, void* stream);
 
+/* The batched, sync-free inference tail: all images of a call through ONE launch chain whose length does not depend on
+ * n_images, and nothing is read back by the host.
+ * boxes [M][4*nreg], scores [M][K+1] with the rows of image b contiguous: img_off_host [n_images + 1] (HOST, ascending from 0
+ * to M).  geom_host [n_images][6] (HOST) = per image (h, w, out_h, out_w, sx, sy): the candidates are clipped to (h, w) as the
+ * single-image entry clips them; with postprocess != 0 the kept boxes then go through detector_postprocess
+ * (projects/WSL/wsl/modeling/postprocessing.py) - x * sx, y * sy in fp32 (sx = out_w / w, sy = out_h / h formed in double and
+ * rounded once by the caller, what Boxes.scale does with a Python float on an fp32 tensor), clip to (out_h, out_w), boxes with
+ * w <= 0 or h <= 0 dropped keeping the order.  With postprocess == 0 the raw tail is delivered (out_h, out_w, sx, sy unused).
+ * Outputs are padded blocks: out_boxes [n_images][topk][4], out_scores / out_classes / out_rows [n_images][topk], out_count
+ * [n_images].  Image b's first out_count[b] slots equal, bit for bit, the single-image entries on that image's rows (followed by
+ * the postprocess); out_rows are row indices WITHIN the image, after its own finite-row filter.  Slots at and beyond the count
+ * hold boxes / scores 0 and classes / rows -1: the buffers are a function of the inputs alone.  Per image, as in the reference:
+ * the finite-row filter, the boxes.max() + 1 class offset (integer-bits atomic max), the >= 40000 candidates switch to per-class
+ * NMS decided by the image's own candidate count, the clip, the early exit at topk <= 1024.
+ * Limits (DRN_ERR_UNSUPPORTED before any launch; callers chunk): 1 <= n_images <= DRN_DETECT_MAX_IMAGES,
+ * M * K <= DRN_DETECT_BATCH_MAX_ENTRIES (the sort's tile table).  total_cap >= M * K sizes the workspace. */
+#define DRN_DETECT_MAX_IMAGES 16
+#define DRN_DETECT_BATCH_MAX_ENTRIES 4194304
+long drn_detect_batch_workspace_bytes(int total_cap, int n_images);
+int drn_detect_topk_batch(const float* boxes, const float* scores, const int* img_off_host, int n_images, int K, int nreg,
+                          const float* geom_host, int postprocess, float score_thresh, float nms_thresh, int topk,
+                          void* workspace, long workspace_bytes, int total_cap, float* out_boxes, float* out_scores,
+                          int* out_classes, int* out_rows, int* out_count, void* stream);
+/* Padded blocks -> packed detections: n_blocks blocks of topk slots, concatenated (boxes [n_blocks][topk][4], scores / classes
+ * [n_blocks][topk]), count [n_blocks] (held to 0 .. topk) and image_index [n_blocks].  The live slots are packed in block order
+ * then slot order into out_boxes [n][4], out_scores / out_classes / out_images [n] (capacity n_blocks * topk), and n is written
+ * to out_n [1] on the device.  offsets [n_blocks + 1] is scratch.  Two launches: a prefix over count, a gather. */
+int drn_detect_compact(const float* boxes, const float* scores, const int* classes, const int* count, const int* image_index,
+                       int n_blocks, int topk, int* offsets, float* out_boxes, float* out_scores, int* out_classes,
+                       int* out_images, int* out_n, void* stream);
+
 /* ---- test-time augmentation ------------------------------------------- */
 
 /* GeneralizedRCNNWithTTAAVG._get_augmented_boxes (projects/WSL/wsl/modeling/test_time_augmentation_avg.py:269-294):
