@@ -10,7 +10,6 @@
 //   softmax_ce         OICROutputs.softmax_cross_entropy_loss fast_rcnn.py:1087-1096,1128-1144,
 //                      predict_probs :1561-1575 and its backward
 //   apply_deltas       Box2BoxTransform.apply_deltas box_regression.py:73-110
-//   sgd_step           torch.optim.SGD as built by detectron2/solver/build.py:93-137
 #include "drn_common.h"
 #include "box_shared.h"
 #include "tune.h"
@@ -1085,259 +1084,16 @@ __global__ void apply_deltas_kernel(const float* deltas, long ld_d, const float*
                       out + (long)r * 4 * K + 4 * k);
 }
 
-// p -= lr * (buf = mom*buf + (g + wd*p)); first step: buf = g + wd*p.  One launch over the flat parameter
-// arena (blockIdx.y walks the segments, float4 lanes when the segment offset is 16-B aligned); the bf16
-// compute shadow (same flat layout) is refreshed in the same pass, so the weights are read once per step.
-// w / momentum / gradient are streamed once per step: non-temporal accesses keep them from evicting the GEMM operands
-// (and the freshly written bf16 shadow, which the next fc6 forward reads) from L2 / Infinity Cache (+1.4 % step rate).
-// CLIP (SOLVER.CLIP_GRADIENTS, detectron2/solver/build.py:19-90: each parameter = each segment on its own, on the gradient
-// as SGD.step sees it = g * grad_scale): CLIP_NONE is the kernel's arithmetic as it was (the two clip arguments are passed,
-// never read); CLIP_VALUE clamps to +-clip_value (torch.nn.utils.clip_grad_value_); CLIP_NORM scales by min(clip_value * (1 / (norm + 1e-6)), 1) with the segment's norm read from
-// seg_norms (drn_grad_norms; torch.nn.utils.clip_grad_norm_ on one tensor).  NaNs pass through both as through torch.clamp.
-enum { CLIP_NONE = 0, CLIP_VALUE = 1, CLIP_NORM = 2 };
-template <int CLIP>
-__device__ __forceinline__ float clip_coef(float clip_value, const float* seg_norms, int s) {
-  if constexpr (CLIP == CLIP_NORM) {
-    // torch forms `max_norm / (total_norm + 1e-6)` as reciprocal(total_norm + 1e-6) * max_norm (Tensor.__rtruediv__): two roundings,
-    // restated as such - a true division differs in the last bit for a quarter of the norms
-    const float coef = (1.f / (seg_norms[s] + 1e-6f)) * clip_value;
-    return coef > 1.f ? 1.f : coef;
-  }
-  return 1.f;
-}
-template <int CLIP>
-__device__ __forceinline__ float clip_grad(float d, float clip_value, float coef) {
-  if constexpr (CLIP == CLIP_VALUE) return d > clip_value ? clip_value : (d < -clip_value ? -clip_value : d);
-  if constexpr (CLIP == CLIP_NORM) return d * coef;
-  return d;
-}
-
-// GUARD (the anomaly guard): guard -> state[0] of drn_loss_guard; non-zero = the step's loss was not finite, and the whole
-// launch leaves w / mom / shadow as they are (a wave-uniform early exit: no load, no store).
-template <bool SHADOW, int GDT, bool NT = true, int CLIP = CLIP_NONE, bool GUARD = false>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, float* __restrict__ mom,
-                                                  const void* __restrict__ gv, long goff, bf16_t* __restrict__ shadow,
-                                                  const SgdSeg* segs, int nseg, float momentum, int first_step,
-                                                  float grad_scale, float clip_value, const float* seg_norms,
-                                                  const int* guard) {
-  if constexpr (GUARD) {
-    if (guard[0] != 0) return;
-  }
-  using GT = typename ElemOf<GDT>::type;
-  const GT* g = (const GT*)gv - goff;  // arena element j <-> g[j]
-  for (int s = blockIdx.y; s < nseg; s += gridDim.y) {
-    const SgdSeg sg = segs[s];
-    const float coef = clip_coef<CLIP>(clip_value, seg_norms, s);
-    const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
-    long done = 0;
-    if ((sg.off & 3) == 0 && ((sg.off - goff) & 3) == 0) {
-      const long nvec = sg.cnt >> 2;
-      for (long i = tid; i < nvec; i += nthr) {
-        const long j = sg.off + 4 * i;
-        const f32x4_t pw = NT ? __builtin_nontemporal_load((const f32x4_t*)(w + j)) : *(const f32x4_t*)(w + j);
-        f32x4_t gg;
-        if constexpr (GDT == DRN_BF16) {
-          typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-          const u32x2_t x = NT ? __builtin_nontemporal_load((const u32x2_t*)(g + j)) : *(const u32x2_t*)(g + j);
-          gg = f32x4_t{__builtin_bit_cast(float, x.x << 16), __builtin_bit_cast(float, x.x & 0xffff0000u),
-                       __builtin_bit_cast(float, x.y << 16), __builtin_bit_cast(float, x.y & 0xffff0000u)};
-        } else {
-          gg = NT ? __builtin_nontemporal_load((const f32x4_t*)(g + j)) : *(const f32x4_t*)(g + j);
-        }
-        f32x4_t mm = {0.f, 0.f, 0.f, 0.f};
-        if (!first_step) mm = NT ? __builtin_nontemporal_load((const f32x4_t*)(mom + j)) : *(const f32x4_t*)(mom + j);
-        f32x4_t nb, nw;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float d = clip_grad<CLIP>(gg[e] * grad_scale, clip_value, coef);
-          if (sg.wd != 0.f) d = d + sg.wd * pw[e];
-          nb[e] = first_step ? d : momentum * mm[e] + d;
-          nw[e] = pw[e] - sg.lr * nb[e];
-        }
-        if (NT) {
-          __builtin_nontemporal_store(nb, (f32x4_t*)(mom + j));
-          __builtin_nontemporal_store(nw, (f32x4_t*)(w + j));
-        } else {
-          *(f32x4_t*)(mom + j) = nb;
-          *(f32x4_t*)(w + j) = nw;
-        }
-        if (SHADOW) {
-          uint2 o;
-          o.x = (uint32_t)f32_to_bf16(nw[0]) | ((uint32_t)f32_to_bf16(nw[1]) << 16);
-          o.y = (uint32_t)f32_to_bf16(nw[2]) | ((uint32_t)f32_to_bf16(nw[3]) << 16);
-          *(uint2*)(shadow + j) = o;
-        }
-      }
-      done = nvec << 2;
-    }
-    for (long i = done + tid; i < sg.cnt; i += nthr) {
-      const long j = sg.off + i;
-      const float pw = w[j];
-      float d = clip_grad<CLIP>(ElemOf<GDT>::ld(g + j) * grad_scale, clip_value, coef);
-      if (sg.wd != 0.f) d = d + sg.wd * pw;
-      const float b = first_step ? d : momentum * mom[j] + d;
-      mom[j] = b;
-      const float nw = pw - sg.lr * b;
-      w[j] = nw;
-      if (SHADOW) shadow[j] = f32_to_bf16(nw);
-    }
-  }
-}
-
-// The same update on a rectangular BLOCK of one 2-D parameter (rows r0..r1, columns c0..c1 of a [.., ld] tensor that starts at
-// arena element sg.off): the fc6 weight gradient leaves its GEMM in COLUMN slabs (one exact round of the persistent
-// kernel each, run_fc1_tail), and each slab's update starts the moment its GEMM is queued.  Arithmetic, access width
-// and cache policy are sgd_kernel's; only the index map differs (a row of the block is a contiguous run of cols / 4
-// 16-byte vectors).  c0, cols, ld, sg.off and goff are multiples of 4 (launcher).
-template <bool SHADOW, int GDT, int CLIP = CLIP_NONE, bool GUARD = false>
-__global__ __launch_bounds__(256) void sgd_block_kernel(float* __restrict__ w, float* __restrict__ mom,
-                                                        const void* __restrict__ gv, long goff, bf16_t* __restrict__ shadow,
-                                                        const SgdSeg* seg, int r0, int rows, int c0, int cols, long ld,
-                                                        float momentum, int first_step, float grad_scale, float clip_value,
-                                                        const float* seg_norms, const int* guard) {
-  if constexpr (GUARD) {
-    if (guard[0] != 0) return;  // (as sgd_kernel)
-  }
-  using GT = typename ElemOf<GDT>::type;
-  const GT* g = (const GT*)gv - goff;
-  const SgdSeg sg = seg[0];
-  const float coef = clip_coef<CLIP>(clip_value, seg_norms, 0);  // the norm of the ONE tensor seg[0] describes
-  const unsigned cv = (unsigned)cols >> 2, nvec = (unsigned)rows * cv;
-  const unsigned nthr = gridDim.x * blockDim.x;
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += nthr) {
-    const unsigned r = i / cv, c = i - r * cv;
-    const long j = sg.off + (long)(r0 + (int)r) * ld + c0 + 4 * (long)c;
-    const f32x4_t pw = __builtin_nontemporal_load((const f32x4_t*)(w + j));
-    f32x4_t gg;
-    if constexpr (GDT == DRN_BF16) {
-      typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-      const u32x2_t x = __builtin_nontemporal_load((const u32x2_t*)(g + j));
-      gg = f32x4_t{__builtin_bit_cast(float, x.x << 16), __builtin_bit_cast(float, x.x & 0xffff0000u),
-                   __builtin_bit_cast(float, x.y << 16), __builtin_bit_cast(float, x.y & 0xffff0000u)};
-    } else {
-      gg = __builtin_nontemporal_load((const f32x4_t*)(g + j));
-    }
-    f32x4_t mm = {0.f, 0.f, 0.f, 0.f};
-    if (!first_step) mm = __builtin_nontemporal_load((const f32x4_t*)(mom + j));
-    f32x4_t nb, nw;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float d = clip_grad<CLIP>(gg[e] * grad_scale, clip_value, coef);
-      if (sg.wd != 0.f) d = d + sg.wd * pw[e];
-      nb[e] = first_step ? d : momentum * mm[e] + d;
-      nw[e] = pw[e] - sg.lr * nb[e];
-    }
-    __builtin_nontemporal_store(nb, (f32x4_t*)(mom + j));
-    __builtin_nontemporal_store(nw, (f32x4_t*)(w + j));
-    if (SHADOW) {
-      uint2 o;
-      o.x = (uint32_t)f32_to_bf16(nw[0]) | ((uint32_t)f32_to_bf16(nw[1]) << 16);
-      o.y = (uint32_t)f32_to_bf16(nw[2]) | ((uint32_t)f32_to_bf16(nw[3]) << 16);
-      *(uint2*)(shadow + j) = o;
-    }
-  }
-}
-
-// Per-segment gradient norms for CLIP_NORM (torch.nn.utils.clip_grad_norm_ on ONE tensor: ||g * grad_scale||_p, p = 1 / 2 / inf, in
-// fp32).  HBM-bound (fc6.weight: 411 MB fp32 / 205 MB as the bf16 bucket), so every segment is spread over the whole x grid like
-// sgd_kernel's; NO float atomics and a FIXED order of addition (set_deterministic rests on the RoI backward being the package's only
-// float-atomic kernel): thread -> wave butterfly -> LDS tree over the 4 waves -> partial[s][blockIdx.x] in the caller's workspace
-// (grad_norm_partial_kernel), then ONE workgroup per segment adds the NORM_GX partials in a fixed order and takes the root
-// (grad_norm_final_kernel).  The x grid is a constant, not a tuning knob: the same input gives the same bits on every run.
-constexpr int NORM_GX = 512;  // 2 workgroups per CU x 4 x 16-byte loads per thread in flight = 32 KiB of HBM reads per CU
-enum { NORM_INF = 0, NORM_L1 = 1, NORM_L2 = 2 };
-
-template <int P>
-__device__ __forceinline__ float norm_term(float x, float grad_scale) {
-  const float d = x * grad_scale;
-  if constexpr (P == NORM_L2) return d * d;
-  return fabsf(d);
-}
-// sum for p = 1 / 2; for inf a maximum that keeps a NaN (torch's abs().max() does)
-template <int P>
-__device__ __forceinline__ float norm_join(float a, float b) {
-  if constexpr (P == NORM_INF) return (a >= b || a != a) ? a : b;
-  return a + b;
-}
-template <int P>
-__device__ __forceinline__ float norm_block_join(float v, float* lds4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = norm_join<P>(v, __shfl_xor(v, o, 64));
-  __syncthreads();  // (lds4 is reused by the next segment of the caller's loop)
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return norm_join<P>(norm_join<P>(lds4[0], lds4[1]), norm_join<P>(lds4[2], lds4[3]));
-}
-
-template <int GDT, int P>
-__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const void* __restrict__ gv, long goff, const SgdSeg* segs, int nseg,
-                                                                float grad_scale, float* __restrict__ partial) {
-  using GT = typename ElemOf<GDT>::type;
-  constexpr int VE = 16 / (int)sizeof(GT);  // elements of one 16-byte load
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  __shared__ float lds4[4];
-  const GT* g = (const GT*)gv - goff;  // arena element j <-> g[j]
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
-  for (int s = blockIdx.y; s < nseg; s += gridDim.y) {
-    const SgdSeg sg = segs[s];
-    float acc[VE];
-#pragma unroll
-    for (int e = 0; e < VE; ++e) acc[e] = 0.f;
-    auto add_vec = [&](const u32x4_t x) {
-      if constexpr (GDT == DRN_BF16) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc[2 * e] = norm_join<P>(acc[2 * e], norm_term<P>(__builtin_bit_cast(float, x[e] << 16), grad_scale));
-          acc[2 * e + 1] = norm_join<P>(acc[2 * e + 1], norm_term<P>(__builtin_bit_cast(float, x[e] & 0xffff0000u), grad_scale));
-        }
-      } else {
-        const f32x4_t f = __builtin_bit_cast(f32x4_t, x);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = norm_join<P>(acc[e], norm_term<P>(f[e], grad_scale));
-      }
-    };
-    long done = 0;
-    if ((reinterpret_cast<uintptr_t>(g + sg.off) & 15) == 0) {
-      const u32x4_t* g4 = (const u32x4_t*)(g + sg.off);
-      const long nvec = sg.cnt / VE;
-      long i = tid;
-      for (; i + 3 * nthr < nvec; i += 4 * nthr) {  // four independent loads in flight, added in index order
-        const u32x4_t x0 = __builtin_nontemporal_load(g4 + i), x1 = __builtin_nontemporal_load(g4 + i + nthr);
-        const u32x4_t x2 = __builtin_nontemporal_load(g4 + i + 2 * nthr), x3 = __builtin_nontemporal_load(g4 + i + 3 * nthr);
-        add_vec(x0); add_vec(x1); add_vec(x2); add_vec(x3);
-      }
-      for (; i < nvec; i += nthr) add_vec(__builtin_nontemporal_load(g4 + i));
-      done = nvec * VE;
-    }
-    float v;
-    if constexpr (VE == 8) {
-      v = norm_join<P>(norm_join<P>(norm_join<P>(acc[0], acc[1]), norm_join<P>(acc[2], acc[3])),
-                       norm_join<P>(norm_join<P>(acc[4], acc[5]), norm_join<P>(acc[6], acc[7])));
-    } else {
-      v = norm_join<P>(norm_join<P>(acc[0], acc[1]), norm_join<P>(acc[2], acc[3]));
-    }
-    for (long i = done + tid; i < sg.cnt; i += nthr) v = norm_join<P>(v, norm_term<P>(ElemOf<GDT>::ld(g + sg.off + i), grad_scale));
-    v = norm_block_join<P>(v, lds4);
-    if (threadIdx.x == 0) partial[(long)s * gridDim.x + blockIdx.x] = v;
-  }
-}
-
-template <int P>
-__global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __restrict__ partial, int npart, float* __restrict__ norms) {
-  __shared__ float lds4[4];
-  const float* p = partial + (long)blockIdx.x * npart;
-  float v = 0.f;
-  for (int i = threadIdx.x; i < npart; i += 256) v = norm_join<P>(v, p[i]);
-  v = norm_block_join<P>(v, lds4);
-  if (threadIdx.x == 0) norms[blockIdx.x] = P == NORM_L2 ? sqrtf(v) : v;
-}
-
 __global__ void sum_small_kernel(const float* in, int n, float scale, float* out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     float s = 0.f;
     for (int i = 0; i < n; ++i) s += in[i];
     out[0] = s * scale;
   }
+}
+
+__global__ void counter_add_kernel(unsigned long long* c, unsigned long long inc) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += inc;
 }
 
 }  // namespace
@@ -1673,218 +1429,6 @@ int drn_apply_deltas(const float* deltas, long ld_d, const float* boxes, float* 
   const long tot = (long)M * K;
   hipLaunchKernelGGL(apply_deltas_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      deltas, ld_d, boxes, out, M, K, w4[0], w4[1], w4[2], w4[3], scale_clamp);
-  DRN_CHECK_LAUNCH();
-  return DRN_OK;
-}
-
-// g_tune.sgd_grid workgroups (x) of the optimizer kernel; each runs a grid-stride loop, i.e. lives for the whole launch.  At most two
-// 256-thread workgroups (34 VGPRs) fit on a CU beside a resident 256x256 GEMM workgroup.
-// segs_dev: device array of {int64 off, int64 cnt, float lr, float wd} (24 bytes each).  shadow (optional):
-// bf16 array with the arena's flat layout, refreshed in the same pass.
-static int sgd_step_launch(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                           int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
-                           int clip_mode, float clip_value, const float* seg_norms, const int* guard, void* stream) {
-  if (!weights || !momentum_buf || !grads || !segs_dev || nseg < 1) return DRN_ERR_ARG;
-  if (shadow && shadow_dtype != DRN_BF16) return DRN_ERR_ARG;
-  if (grad_dtype != DRN_F32 && grad_dtype != DRN_BF16) return DRN_ERR_ARG;
-  if (clip_mode < CLIP_NONE || clip_mode > CLIP_NORM || (clip_mode == CLIP_NORM && !seg_norms)) return DRN_ERR_ARG;
-  if (clip_mode != CLIP_NONE && !(clip_value >= 0.f)) return DRN_ERR_ARG;
-  dim3 grid(g_tune.sgd_grid, nseg < 32 ? nseg : 32), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define SGD_LAUNCH_G(SH, GD, CL, GU)                                                                                 \
-  hipLaunchKernelGGL((sgd_kernel<SH, GD, true, CL, GU>), grid, block, 0, st, weights, momentum_buf, grads, grad_off, \
-                     (bf16_t*)shadow, (const SgdSeg*)segs_dev, nseg, momentum, first_step, grad_scale, clip_value,   \
-                     seg_norms, guard)
-#define SGD_LAUNCH(SH, GD, CL)                                                         \
-  do {                                                                                 \
-    if (guard) SGD_LAUNCH_G(SH, GD, CL, true); else SGD_LAUNCH_G(SH, GD, CL, false);   \
-  } while (0)
-#define SGD_LAUNCH_CL(SH, GD)                                        \
-  do {                                                               \
-    if (clip_mode == CLIP_VALUE) SGD_LAUNCH(SH, GD, CLIP_VALUE);     \
-    else if (clip_mode == CLIP_NORM) SGD_LAUNCH(SH, GD, CLIP_NORM);  \
-    else SGD_LAUNCH(SH, GD, CLIP_NONE);                              \
-  } while (0)
-  if (shadow) { if (grad_dtype == DRN_BF16) SGD_LAUNCH_CL(true, DRN_BF16); else SGD_LAUNCH_CL(true, DRN_F32); }
-  else { if (grad_dtype == DRN_BF16) SGD_LAUNCH_CL(false, DRN_BF16); else SGD_LAUNCH_CL(false, DRN_F32); }
-#undef SGD_LAUNCH_CL
-#undef SGD_LAUNCH
-#undef SGD_LAUNCH_G
-  DRN_CHECK_LAUNCH();
-  return DRN_OK;
-}
-
-int drn_sgd_step(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                 int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
-                 void* stream) {
-  return sgd_step_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, segs_dev, nseg, momentum,
-                         first_step, grad_scale, CLIP_NONE, 0.f, nullptr, nullptr, stream);
-}
-
-// drn_sgd_step with SOLVER.CLIP_GRADIENTS applied to g * grad_scale, per segment (sgd_kernel's CLIP parameter): clip_mode 0 = none
-// (drn_sgd_step's bits), 1 = value, 2 = norm with seg_norms[nseg] from drn_grad_norms (device memory, read by the kernel)
-int drn_sgd_step_clip(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                      int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
-                      int clip_mode, float clip_value, const float* seg_norms, void* stream) {
-  return sgd_step_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, segs_dev, nseg, momentum,
-                         first_step, grad_scale, clip_mode, clip_value, seg_norms, nullptr, stream);
-}
-
-// drn_sgd_step_clip under the anomaly guard: guard -> state[0] of drn_loss_guard (device memory).  guard[0] == 0:
-// drn_sgd_step_clip's bits; guard[0] != 0: weights, momentum_buf and shadow keep their bits.  A skipped FIRST step leaves
-// momentum_buf untouched - the caller creates it as zeros, and a later first_step = 0 update on zeros computes what a first step would.
-int drn_sgd_step_guard(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                       int shadow_dtype, const void* segs_dev, int nseg, float momentum, int first_step, float grad_scale,
-                       int clip_mode, float clip_value, const float* seg_norms, const int* guard, void* stream) {
-  if (!guard) return DRN_ERR_ARG;
-  return sgd_step_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, segs_dev, nseg, momentum,
-                         first_step, grad_scale, clip_mode, clip_value, seg_norms, guard, stream);
-}
-
-// workspace of drn_grad_norms: one fp32 partial per (segment, x workgroup).  Host-only.
-long drn_grad_norms_ws_bytes(int nseg) { return nseg < 1 ? 0 : (long)nseg * NORM_GX * (long)sizeof(float); }
-
-// norms[s] = || grads[segment s] * grad_scale ||_p (norm_type 1, 2, or 0 = inf), grads read as drn_sgd_step reads them: two
-// launches, no host synchronisation (capturable), no atomics
-int drn_grad_norms(const void* grads, int grad_dtype, long grad_off, const void* segs_dev, int nseg, int norm_type,
-                   float grad_scale, float* norms, void* workspace, long workspace_bytes, void* stream) {
-  if (!grads || !segs_dev || !norms || !workspace || nseg < 1) return DRN_ERR_ARG;
-  if (grad_dtype != DRN_F32 && grad_dtype != DRN_BF16) return DRN_ERR_ARG;
-  if (norm_type != NORM_L1 && norm_type != NORM_L2 && norm_type != NORM_INF) return DRN_ERR_UNSUPPORTED;
-  if (workspace_bytes < drn_grad_norms_ws_bytes(nseg)) return DRN_ERR_ARG;
-  dim3 grid(NORM_GX, nseg < 32 ? nseg : 32), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace;
-#define NORM_LAUNCH(GD, P)                                                                                              \
-  do {                                                                                                                  \
-    hipLaunchKernelGGL((grad_norm_partial_kernel<GD, P>), grid, block, 0, st, grads, grad_off, (const SgdSeg*)segs_dev, \
-                       nseg, grad_scale, partial);                                                                      \
-    hipLaunchKernelGGL((grad_norm_final_kernel<P>), dim3(nseg), block, 0, st, (const float*)partial, NORM_GX, norms);   \
-  } while (0)
-#define NORM_LAUNCH_P(GD)                                     \
-  do {                                                        \
-    if (norm_type == NORM_L1) NORM_LAUNCH(GD, NORM_L1);       \
-    else if (norm_type == NORM_L2) NORM_LAUNCH(GD, NORM_L2);  \
-    else NORM_LAUNCH(GD, NORM_INF);                           \
-  } while (0)
-  if (grad_dtype == DRN_BF16) NORM_LAUNCH_P(DRN_BF16); else NORM_LAUNCH_P(DRN_F32);
-#undef NORM_LAUNCH_P
-#undef NORM_LAUNCH
-  DRN_CHECK_LAUNCH();
-  return DRN_OK;
-}
-
-// drn_sgd_step on a rectangular block of ONE 2-D tensor: seg_dev = that tensor's {offset, count, lr, wd} entry (lr / wd are
-// read on the device: a captured launch follows the schedule), the block = rows r0 .. r0+rows, columns c0 .. c0+cols of
-// its [count / ld][ld] view.
-static int sgd_step_block_launch(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off,
-                                 void* shadow, int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld,
-                                 float momentum, int first_step, float grad_scale, int clip_mode, float clip_value,
-                                 const float* seg_norms, const int* guard, void* stream) {
-  if (!weights || !momentum_buf || !grads || !seg_dev || r0 < 0 || rows < 0 || c0 < 0 || cols < 0 || ld < c0 + cols)
-    return DRN_ERR_ARG;
-  if (shadow && shadow_dtype != DRN_BF16) return DRN_ERR_ARG;
-  if (grad_dtype != DRN_F32 && grad_dtype != DRN_BF16) return DRN_ERR_ARG;
-  if (clip_mode < CLIP_NONE || clip_mode > CLIP_NORM || (clip_mode == CLIP_NORM && !seg_norms)) return DRN_ERR_ARG;
-  if (clip_mode != CLIP_NONE && !(clip_value >= 0.f)) return DRN_ERR_ARG;
-  if ((c0 & 3) || (cols & 3) || (ld & 3) || (grad_off & 3)) return DRN_ERR_UNSUPPORTED;  // (the tensor's offset: checked by the caller's table)
-  if ((long)rows * (cols >> 2) >= (1L << 32)) return DRN_ERR_UNSUPPORTED;
-  if (rows == 0 || cols == 0) return DRN_OK;
-  dim3 grid(g_tune.sgd_grid), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define SGD_LAUNCH_G(SH, GD, CL, GU)                                                                                    \
-  hipLaunchKernelGGL((sgd_block_kernel<SH, GD, CL, GU>), grid, block, 0, st, weights, momentum_buf, grads, grad_off,    \
-                     (bf16_t*)shadow, (const SgdSeg*)seg_dev, r0, rows, c0, cols, ld, momentum, first_step, grad_scale, \
-                     clip_value, seg_norms, guard)
-#define SGD_LAUNCH(SH, GD, CL)                                                         \
-  do {                                                                                 \
-    if (guard) SGD_LAUNCH_G(SH, GD, CL, true); else SGD_LAUNCH_G(SH, GD, CL, false);   \
-  } while (0)
-#define SGD_LAUNCH_CL(SH, GD)                                        \
-  do {                                                               \
-    if (clip_mode == CLIP_VALUE) SGD_LAUNCH(SH, GD, CLIP_VALUE);     \
-    else if (clip_mode == CLIP_NORM) SGD_LAUNCH(SH, GD, CLIP_NORM);  \
-    else SGD_LAUNCH(SH, GD, CLIP_NONE);                              \
-  } while (0)
-  if (shadow) { if (grad_dtype == DRN_BF16) SGD_LAUNCH_CL(true, DRN_BF16); else SGD_LAUNCH_CL(true, DRN_F32); }
-  else { if (grad_dtype == DRN_BF16) SGD_LAUNCH_CL(false, DRN_BF16); else SGD_LAUNCH_CL(false, DRN_F32); }
-#undef SGD_LAUNCH_CL
-#undef SGD_LAUNCH
-#undef SGD_LAUNCH_G
-  DRN_CHECK_LAUNCH();
-  return DRN_OK;
-}
-
-int drn_sgd_step_block(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                       int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
-                       int first_step, float grad_scale, void* stream) {
-  return sgd_step_block_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, seg_dev, r0, rows, c0,
-                               cols, ld, momentum, first_step, grad_scale, CLIP_NONE, 0.f, nullptr, nullptr, stream);
-}
-
-// drn_sgd_step_block with the clipping of drn_sgd_step_clip; seg_norms -> the norm of the ONE tensor seg_dev describes
-int drn_sgd_step_block_clip(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                            int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
-                            int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
-                            void* stream) {
-  return sgd_step_block_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, seg_dev, r0, rows, c0,
-                               cols, ld, momentum, first_step, grad_scale, clip_mode, clip_value, seg_norms, nullptr, stream);
-}
-
-// drn_sgd_step_block_clip under the anomaly guard (as drn_sgd_step_guard)
-int drn_sgd_step_block_guard(float* weights, float* momentum_buf, const void* grads, int grad_dtype, long grad_off, void* shadow,
-                             int shadow_dtype, const void* seg_dev, int r0, int rows, int c0, int cols, long ld, float momentum,
-                             int first_step, float grad_scale, int clip_mode, float clip_value, const float* seg_norms,
-                             const int* guard, void* stream) {
-  if (!guard) return DRN_ERR_ARG;
-  return sgd_step_block_launch(weights, momentum_buf, grads, grad_dtype, grad_off, shadow, shadow_dtype, seg_dev, r0, rows, c0,
-                               cols, ld, momentum, first_step, grad_scale, clip_mode, clip_value, seg_norms, guard, stream);
-}
-
-__global__ void counter_add_kernel(unsigned long long* c, unsigned long long inc) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += inc;
-}
-
-// The anomaly guard's check (detectron2/engine/train_loop.py:252-258: `losses = sum(loss_dict.values())`, then
-// `if not torch.isfinite(losses).all(): raise FloatingPointError`): one wave forms the fp32 sum of the step's loss scalars in
-// list order and tests isfinite(sum) - +inf + -inf and an overflowing sum of finite terms are bad, as there.  The pointers
-// travel in the kernel arguments (no device table to keep alive or to re-upload).  state[0] = skip flag (read by the guarded
-// update kernels), [1] = calls seen, [2] = index of the first bad call or -1, [3] = bad calls; written by lane 0 alone.
-enum { GUARD_RAISE = 1, GUARD_SKIP = 2, GUARD_MAX_LOSSES = 16 };
-struct LossPtrs { const float* p[GUARD_MAX_LOSSES]; };
-__global__ __launch_bounds__(64) void loss_guard_kernel(LossPtrs lp, int n, int mode, int window_first, int* state) {
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < GUARD_MAX_LOSSES; ++i)  // (unrolled: static indices into the argument block)
-    if (i < n) sum = sum + lp.p[i][0];
-  const bool bad = (__builtin_bit_cast(unsigned, sum) & 0x7f800000u) == 0x7f800000u;  // !isfinite: inf or NaN
-  if (threadIdx.x == 0) {
-    const int flag = state[0], calls = state[1], first_bad = state[2];
-    // raise: sticky for ever.  skip: a bad micro-step discards its whole accumulation window and nothing more
-    const bool keep = mode == GUARD_RAISE ? flag != 0 : (flag != 0 && !window_first);
-    state[0] = (bad || keep) ? 1 : 0;
-    state[1] = calls + 1;
-    if (bad) {
-      if (first_bad < 0) state[2] = calls;
-      state[3] = state[3] + 1;
-    }
-  }
-}
-
-}  // extern "C"  (kernels above need C++ linkage)
-extern "C" {
-
-// The device-side anomaly guard: losses = HOST array of n <= 16 device pointers to the step's fp32 loss scalars (copied into the
-// launch's arguments); mode 1 = raise (the flag is sticky), 2 = skip (flag = bad_now || (flag && !window_first)); state =
-// int32[4] in device memory, initialised by the caller to {0, 0, -1, 0}.  One launch of one wave; no sync, no allocation.
-int drn_loss_guard(const void* const* losses, int n, int mode, int window_first, int* state, void* stream) {
-  if (!losses || !state || n < 1 || n > GUARD_MAX_LOSSES || (mode != GUARD_RAISE && mode != GUARD_SKIP)) return DRN_ERR_ARG;
-  LossPtrs lp;
-  for (int i = 0; i < GUARD_MAX_LOSSES; ++i) {
-    lp.p[i] = (const float*)losses[i < n ? i : 0];
-    if (!lp.p[i]) return DRN_ERR_ARG;
-  }
-  hipLaunchKernelGGL(loss_guard_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lp, n, mode, window_first ? 1 : 0, state);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

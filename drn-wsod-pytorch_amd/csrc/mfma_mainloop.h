@@ -12,6 +12,7 @@
 // swizzle slot ^= (row>>1)&7 (rows are 128 B, a 256-B bank row holds two).
 #pragma once
 #include "drn_common.h"
+#include "sgd_rule.h"
 
 namespace {
 
@@ -301,7 +302,7 @@ __device__ __forceinline__ void pp_issue_first(char* smem, __amdgpu_buffer_rsrc_
 // retire in order, and every wait below is the old count plus the optimizer operations issued behind the piece it guards:
 //   phase 1 / 2: vmcnt(4) -> vmcnt(7)   (3 loads of this slab's phase 1)      phase 4: vmcnt(4) -> vmcnt(7) from slab 1 on
 //   (3 stores of phase 3);  chunk i - 1's loads have 18 (slab 1: 15) younger operations when phase 3 of slab i needs them.
-// Same arithmetic, element for element, as sgd_kernel on the bf16 bucket (bit-identical: tests).
+// Same arithmetic, element for element, as sgd_kernel on the bf16 bucket: both run sgd_rule.h (bit-identical: tests).
 // GUARD (the anomaly guard, drn_loss_guard): a skipped step keeps ALL SIX memory operations of a chunk and selects the stored
 // VALUES - w_old, m_old and the shadow word of w_old (the shadow is bf16(w) by construction) - so every count above holds
 // unchanged; a predicated store would change what each wait guards.  The flag is wave-uniform (SgdPipe::skip).
@@ -327,17 +328,13 @@ __device__ __forceinline__ void sgdp_load(const SgdPipe& sp, SgdRegs& r, unsigne
 template <bool GUARD = false>
 __device__ __forceinline__ void sgdp_apply_store(const SgdPipe& sp, const SgdRegs& r, unsigned off) {
 #pragma clang fp contract(off)
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  const u32x2_t x = __builtin_bit_cast(u32x2_t, r.g);
-  const f32x4_t gg = {__builtin_bit_cast(float, x.x << 16), __builtin_bit_cast(float, x.x & 0xffff0000u),
-                      __builtin_bit_cast(float, x.y << 16), __builtin_bit_cast(float, x.y & 0xffff0000u)};
+  const f32x4_t gg = sgd_unpack_bf16x4(__builtin_bit_cast(u32x2_t, r.g));
   f32x4_t nb, nw;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float d = gg[e] * sp.gs;
-    if (sp.wd != 0.f) d = d + sp.wd * r.w[e];
-    nb[e] = sp.first ? d : sp.mom * r.m[e] + d;
-    nw[e] = r.w[e] - sp.lr * nb[e];
+    const SgdNew u = sgd_rule(r.w[e], r.m[e], gg[e] * sp.gs, sp.lr, sp.wd, sp.mom, sp.first);
+    nb[e] = u.b;
+    nw[e] = u.w;
   }
   if constexpr (GUARD) {
 #pragma unroll
@@ -346,9 +343,7 @@ __device__ __forceinline__ void sgdp_apply_store(const SgdPipe& sp, const SgdReg
       nw[e] = sp.skip ? r.w[e] : nw[e];
     }
   }
-  u32x2_t o;
-  o.x = (uint32_t)f32_to_bf16(nw[0]) | ((uint32_t)f32_to_bf16(nw[1]) << 16);
-  o.y = (uint32_t)f32_to_bf16(nw[2]) | ((uint32_t)f32_to_bf16(nw[3]) << 16);
+  const u32x2_t o = sgd_pack_shadow<u32x2_t>(nw);
   __builtin_nontemporal_store(nb, (f32x4_t*)((char*)sp.m + off));
   __builtin_nontemporal_store(nw, (f32x4_t*)((char*)sp.w + off));
   *(u32x2_t*)((char*)sp.s + (off >> 1)) = o;

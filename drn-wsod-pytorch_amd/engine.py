@@ -17,8 +17,6 @@ import bisect
 import collections
 import math
 
-import numpy as np
-
 import torch
 import torch.distributed as dist
 
@@ -176,14 +174,8 @@ class FusedSGD:
         bb = self._bb
         key = tuple((g["lr"], g["weight_decay"]) for g in bb["groups"])
         if key != bb["segs_key"]:
-            arr = np.zeros(len(bb["groups"]), dtype=[("off", "<i8"), ("cnt", "<i8"), ("lr", "<f4"), ("wd", "<f4")])
-            for i, g in enumerate(bb["groups"]):
-                arr[i] = (g["off"], g["cnt"], g["lr"], g["weight_decay"])
-            host = torch.from_numpy(arr.view(np.uint8).copy())
-            if bb["segs_dev"] is None:
-                bb["segs_dev"] = host.to(bb["w"].device)
-            else:
-                bb["segs_dev"].copy_(host)
+            bb["segs_dev"] = ops.sgd_segments(((g["off"], g["cnt"], g["lr"], g["weight_decay"]) for g in bb["groups"]),
+                                              out=bb["segs_dev"], device=bb["w"].device)
             bb["segs_key"] = key
         return bb["segs_dev"], len(bb["groups"])
 
@@ -230,14 +222,9 @@ class FusedSGD:
         groups = [g for g in self.param_groups if g["used"] and not g.get("bb")]
         key = tuple((g["lr"], g["weight_decay"]) for g in groups)
         if key != self._segs_key:
-            arr = np.zeros(len(groups), dtype=[("off", "<i8"), ("cnt", "<i8"), ("lr", "<f4"), ("wd", "<f4")])
-            for i, g in enumerate(groups):
-                arr[i] = (g["off"], g["cnt"], g["lr"], g["weight_decay"])
-            host = torch.from_numpy(arr.view(np.uint8).copy())
-            if self._segs_dev is None:
-                self._segs_dev = host.to(self.engine.arena_w.device)
-            else:
-                self._segs_dev.copy_(host)  # in place: a captured hipGraph keeps reading this table
+            # (out=: in place from the second time on - a captured hipGraph keeps reading this table)
+            self._segs_dev = ops.sgd_segments(((g["off"], g["cnt"], g["lr"], g["weight_decay"]) for g in groups),
+                                              out=self._segs_dev, device=self.engine.arena_w.device)
             self._segs_key, self._nseg = key, len(groups)
         return self._segs_dev, self._nseg
 
@@ -505,15 +492,8 @@ class FusedSGD:
                 r0, r1 = what[1], what[2]
                 k1 = self.model.roi_heads.box_head.fc1.weight.shape[1]
                 rows.append((g["off"] + r0 * k1, (r1 - r0) * k1, g["lr"], g["weight_decay"]))
-        arr = np.zeros(len(rows), dtype=[("off", "<i8"), ("cnt", "<i8"), ("lr", "<f4"), ("wd", "<f4")])
-        for i, r in enumerate(rows):
-            arr[i] = r
-        host = torch.from_numpy(arr.view(np.uint8).copy())
-        if hit is not None:
-            hit[1].copy_(host)  # in place: captured graphs keep reading this table
-            dev = hit[1]
-        else:
-            dev = host.to(self.engine.arena_w.device)
+        # (out=: in place from the second time on - captured graphs keep reading this table)
+        dev = ops.sgd_segments(rows, out=hit[1] if hit is not None else None, device=self.engine.arena_w.device)
         self._bucket_segs[what] = (key, dev, len(rows))
         return dev, len(rows)
 

@@ -6,6 +6,7 @@ import ctypes
 import functools
 import math
 
+import numpy as np
 import torch
 
 from . import _cabi as C
@@ -1289,6 +1290,36 @@ def _clip_args(clip):
     return mode, float(value), C.ptr(norms) if mode == CLIP_NORM else None
 
 
+def _sgd_call(entry, common, clip, guard):
+    """entry(common..., stream), entry_clip(common..., clip..., stream) or entry_guard(common..., clip..., guard, stream); a guard
+    without clipping passes clip_mode CLIP_NONE"""
+    if guard is not None:
+        C.call(entry + "_guard", *common, *_clip_args(clip if clip is not None else (CLIP_NONE, 0.0, None)), _guard_ptr(guard),
+               C.stream())
+    elif clip is not None:
+        C.call(entry + "_clip", *common, *_clip_args(clip), C.stream())
+    else:
+        C.call(entry, *common, C.stream())
+
+
+_SGD_SEG = np.dtype([("off", "<i8"), ("cnt", "<i8"), ("lr", "<f4"), ("wd", "<f4")])  # struct SgdSeg (csrc/drn_common.h)
+
+
+def sgd_segments(rows, out=None, device="cuda"):
+    """The device segment table of sgd_step / sgd_step_block / grad_norms / gemm_tn_sgd: rows = iterable of (off, cnt, lr, wd), one
+    struct SgdSeg each, as a uint8 tensor.  out: the table to overwrite IN PLACE instead (same number of rows; a captured graph
+    keeps reading it) - returned; device: where a new table goes."""
+    rows = list(rows)
+    arr = np.zeros(len(rows), dtype=_SGD_SEG)
+    for i, r in enumerate(rows):
+        arr[i] = tuple(r)
+    host = torch.from_numpy(arr.view(np.uint8))
+    if out is None:
+        return host.to(device)
+    out.copy_(host)
+    return out
+
+
 def sgd_step(weights, momentum_buf, grads, segs_dev, nseg, momentum, first_step, grad_scale=1.0, shadow=None,
              grad_off=0, clip=None, guard=None):
     """grads: the fp32 gradient arena, or (grad_off > 0) a bucket buffer - fp32 or bf16 - whose element 0 is arena
@@ -1298,19 +1329,9 @@ def sgd_step(weights, momentum_buf, grads, segs_dev, nseg, momentum, first_step,
     if HBM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    if guard is not None:
-        C.call("drn_sgd_step_guard", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
-               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
-               int(first_step), float(grad_scale), *_clip_args(clip if clip is not None else (CLIP_NONE, 0.0, None)),
-               _guard_ptr(guard), C.stream())
-    elif clip is None:
-        C.call("drn_sgd_step", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
-               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
-               int(first_step), float(grad_scale), C.stream())
-    else:
-        C.call("drn_sgd_step_clip", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
-               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
-               int(first_step), float(grad_scale), *_clip_args(clip), C.stream())
+    _sgd_call("drn_sgd_step", (C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off), C.ptr(shadow),
+                               C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(segs_dev), nseg, float(momentum),
+                               int(first_step), float(grad_scale)), clip, guard)
     if HBM_TIMING is not None:
         e1.record()
         # bytes are the caller's to know (the segment table lives on the device): keyed by (segments, bucket offset)
@@ -1326,20 +1347,10 @@ def sgd_step_block(weights, momentum_buf, grads, seg_dev, r0, rows, c0, cols, ld
     if HBM_TIMING is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    if guard is not None:
-        C.call("drn_sgd_step_block_guard", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype),
-               int(grad_off), C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0),
-               int(rows), int(c0), int(cols), int(ld), float(momentum), int(first_step), float(grad_scale),
-               *_clip_args(clip if clip is not None else (CLIP_NONE, 0.0, None)), _guard_ptr(guard), C.stream())
-    elif clip is None:
-        C.call("drn_sgd_step_block", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
-               C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0), int(rows), int(c0),
-               int(cols), int(ld), float(momentum), int(first_step), float(grad_scale), C.stream())
-    else:
-        C.call("drn_sgd_step_block_clip", C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype),
-               int(grad_off), C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0),
-               int(rows), int(c0), int(cols), int(ld), float(momentum), int(first_step), float(grad_scale),
-               *_clip_args(clip), C.stream())
+    _sgd_call("drn_sgd_step_block", (C.ptr(weights), C.ptr(momentum_buf), C.ptr(grads), C.dt(grads.dtype), int(grad_off),
+                                     C.ptr(shadow), C.dt(shadow.dtype) if shadow is not None else 0, C.ptr(seg_dev), int(r0),
+                                     int(rows), int(c0), int(cols), int(ld), float(momentum), int(first_step),
+                                     float(grad_scale)), clip, guard)
     if HBM_TIMING is not None:
         e1.record()
         HBM_TIMING.append((e0, e1, int(rows) * int(cols), ("sgd_block", int(r0), int(rows), int(c0), int(cols),

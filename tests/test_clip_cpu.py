@@ -121,7 +121,7 @@ def test_clip_entry_points_declared_and_exported():
 
 
 def test_the_coefficient_is_formed_as_torch_forms_it():
-    """csrc/head.hip forms the norm-clipping coefficient as (1.f / (norm + 1e-6f)) * CLIP_VALUE, not as CLIP_VALUE / (norm + 1e-6f):
+    """csrc/sgd_rule.h forms the norm-clipping coefficient as (1.f / (norm + 1e-6f)) * CLIP_VALUE, not as CLIP_VALUE / (norm + 1e-6f):
     torch.nn.utils.clip_grad_norm_ writes `max_norm / (total_norm + 1e-6)` with a Python float on the left, which Tensor.__rtruediv__
     evaluates as reciprocal * max_norm.  Pinned to torch itself: on fp32 gradients, clip_grad_norm_'s result equals g * coef bit for
     bit with coef restated in numpy fp32 as the kernel computes it, and a true division gives other bits for some of the norms."""

@@ -6,7 +6,7 @@
   5. through the model: a Trainer step with the key set in the config clips both arenas (FAILS where the key is ignored);
   6. the graphed, pipelined step with value clipping equals the plain clipped Trainer; norm clipping is refused there.
 
-The summation order of drn_grad_norms (csrc/head.hip), for the chain depth D used below: a thread adds its 16-byte vectors lane by
+The summation order of drn_grad_norms (csrc/optim.hip), for the chain depth D used below: a thread adds its 16-byte vectors lane by
 lane (segment of 1 500 003 fp32 elements over 512 x 256 threads: at most 3 vectors per thread -> 3 additions; as a bf16 bucket: 2),
 joins the 4 (bf16: 8) lanes in a tree (2; bf16: 3), adds its scalar tail element (1), then the 6 levels of the wave butterfly, the 2
 levels of the LDS tree over the 4 waves; the second launch adds 512 partials as 2 per thread + 6 + 2.  D = 3 + 2 + 1 + 6 + 2 + 2 + 6 + 2

@@ -1415,6 +1415,70 @@ def test_sgd_step_bf16_bucket(drn):
     assert torch.equal(wa[:n0], w[:n0]) and not torch.equal(wa[n0:], w[n0:])
 
 
+@pytest.mark.parametrize("shadowed", [True, False])
+@pytest.mark.parametrize("gdt,grad_off", [(torch.float32, 0),     # the fp32 gradient arena
+                                          (torch.bfloat16, 8),    # a bf16 bucket that keeps the arena's 16-byte phase
+                                          (torch.bfloat16, 6)])   # one that does not: (off - grad_off) & 3 != 0 where off & 3 == 0
+def test_sgd_step_ragged_segments(drn, gdt, grad_off, shadowed):
+    """The flat update on what whole-model runs alone exercised: 35 segments (more than the 32 rows of the grid's y dimension:
+    the s += gridDim.y wrap) of 1 .. 260 elements with gaps of 0 .. 3 between them, so that off & 3 takes all four values - the
+    16-byte body with its scalar tail, and the scalar loop alone where the segment or the bucket is off phase - with mixed lr and
+    wd = 0 on some.  Reference: the rule as separate fp32 torch operations in the kernel's order (as oracle.SGDState, plus
+    grad_scale).  Weights, momentum and shadow bit for bit over a first step and two momentum steps; nothing outside the segments
+    moves.  drn_sgd_step_clip with CLIP_NONE and drn_sgd_step_guard with a clear flag give the same bits; a set flag none."""
+    rs = np.random.RandomState(45)  # (a seed whose layout has the properties asserted below)
+    sizes = [1, 2, 3, 4, 5, 7, 8, 9, 37, 260]
+    counts = rs.permutation(sizes * 3 + sizes[:5])
+    rows, pos = [], 8
+    for i, cnt in enumerate(counts):
+        pos += int(rs.randint(0, 4))
+        rows.append((pos, int(cnt), float(rs.choice([0.01, 0.02, 0.001])), 0.0 if i % 3 == 0 else float(rs.choice([5e-4, 1e-4]))))
+        pos += int(cnt)
+    tot = pos + 5
+    assert len(rows) == 35 and tot < 10000 and {r[0] & 3 for r in rows} == {0, 1, 2, 3}
+    # every size starts on a 16-byte phase somewhere (bodies with and without a tail), the two large ones also off it
+    assert {r[1] for r in rows if r[0] & 3 == 0} == set(sizes) and {37, 260} <= {r[1] for r in rows if r[0] & 3}
+    segs = np.zeros(len(rows), dtype=[("off", "<i8"), ("cnt", "<i8"), ("lr", "<f4"), ("wd", "<f4")])
+    for i, r in enumerate(rows):
+        segs[i] = r
+    segs_dev = torch.from_numpy(segs.view(np.uint8)).to(DEV)
+    inside = torch.zeros(tot, dtype=torch.bool)
+    for off, cnt, _, _ in rows:
+        inside[off: off + cnt] = True
+    momentum, grad_scale = 0.9, 0.37
+    w0 = torch.from_numpy(rs.standard_normal(tot).astype(np.float32))
+    s0 = torch.from_numpy(rs.standard_normal(tot).astype(np.float32)).to(torch.bfloat16)  # (not bf16(w0): a stale word shows)
+    rw, rm, rsh = w0.clone(), torch.zeros(tot), s0.clone()
+    w, m, sh = w0.to(DEV), torch.zeros(tot, device=DEV), s0.to(DEV) if shadowed else None
+    state = lambda: (w.clone(), m.clone(), sh.clone() if shadowed else None)
+    bits = lambda t: t.cpu().view(torch.int32 if t.dtype == torch.float32 else torch.int16)  # (equal bits, not equal values)
+    same = lambda a, b: all(torch.equal(bits(x), bits(y)) for x, y in zip(a, b) if x is not None)
+    clear, flagged = drn.loss_guard_state(DEV), torch.tensor([1, 0, -1, 0], dtype=torch.int32, device=DEV)
+    for step in range(3):
+        g = torch.from_numpy(rs.standard_normal(tot).astype(np.float32)).to(gdt)  # arena-shaped; the bucket starts at grad_off
+        g_dev = g[grad_off:].contiguous().to(DEV)
+        before = state()
+        variants = []
+        for kw in ({"clip": (drn.CLIP_NONE, 0, None)}, {"guard": clear}, {"guard": flagged}):
+            v = state()
+            drn.sgd_step(v[0], v[1], g_dev, segs_dev, len(rows), momentum, step == 0, grad_scale, shadow=v[2], grad_off=grad_off, **kw)
+            variants.append(v)
+        drn.sgd_step(w, m, g_dev, segs_dev, len(rows), momentum, step == 0, grad_scale, shadow=sh, grad_off=grad_off)
+        for off, cnt, lr, wd in rows:
+            sl = slice(off, off + cnt)
+            d = g[sl].float() * grad_scale
+            if wd != 0:
+                d = d + wd * rw[sl]
+            rm[sl] = d if step == 0 else rm[sl] * momentum + d
+            rw[sl] = rw[sl] - lr * rm[sl]
+            rsh[sl] = rw[sl].to(torch.bfloat16)
+        assert same((w, m, sh), (rw, rm, rsh)), step
+        out = ~inside  # (implied by the reference, which touches the segments alone; spelled out)
+        assert same((w.cpu()[out], m.cpu()[out], sh.cpu()[out] if shadowed else None), (w0[out], torch.zeros(tot)[out], s0[out])), step
+        assert same(variants[0], state()) and same(variants[1], state()) and same(variants[2], before), step
+    assert int(clear[0]) == 0 and not torch.equal(w.cpu()[inside], w0[inside])
+
+
 @pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
 def test_sgd_step_block_equals_flat(drn, gdt):
     """drn_sgd_step_block over a 2-D partition of one tensor (column slabs + a trailing block, the fc6 dW schedule of round
