@@ -699,6 +699,15 @@ __device__ __forceinline__ void oicr_targets_body(const TargetParams& p) {
   const int r0 = p.img_off[img], r1 = p.img_off[img + 1];
   const int G = p.gt_count[img];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (r0 == r1) {
+    // an image without proposals has no row to mine and none to label: its first G slots are defined as index 0 and an
+    // all-zero box, and nothing is read (row r0 belongs to the next image, or lies past the tensor for the last one)
+    if ((int)threadIdx.x < G) {
+      p.pgt_idx[img * p.gmax + threadIdx.x] = 0;
+      for (int e = 0; e < 4; ++e) p.pgt_boxes[((long)img * p.gmax + threadIdx.x) * 4 + e] = 0.f;
+    }
+    return;
+  }
   // this thread's first two proposals (all of them for images of <= 2048 proposals): fetched now, used by the labelling
   // pass at the end - they depend on nothing that is computed here
   float pb[2][4];
@@ -782,7 +791,9 @@ __device__ __forceinline__ void oicr_targets_body(const TargetParams& p) {
       if (iou > best) { best = iou; bg = g; }
     }
     int ml = 1;  // Matcher: labels default 1, then per-interval assignment over [-inf, thr.., +inf]
-    if (G == 0) { ml = p.lab[0]; best = 0.f; }
+    // no ground truth: background whatever labels[0] is (roi_heads.py:243, the has_gt == False branch never looks at
+    // the Matcher's labels), weight 0
+    if (G == 0) { ml = 0; best = 0.f; }
     else {
       for (int q = 0; q <= p.nthr; ++q) {
         const float lo = q == 0 ? -INFINITY : p.thr[q - 1];

@@ -912,16 +912,19 @@ def csc_stats(scores, W, img_off, n_img, onehot, slots, table, scratch=None):
 
 
 def oicr_targets(prev_scores, prev_boxes, props, img_off, n_img, gt_classes, gt_count, img_scores, K,
-                 thresholds=(0.5,), labels=(0, 1), zero_delta_decode=False):
+                 thresholds=(0.5,), labels=(0, 1), zero_delta_decode=False, out=None):
+    """`out`: the six output tensors, given by the caller (contiguous, at least the shapes below); allocated if None."""
     M = props.shape[0]
     dev = props.device
     gmax = gt_classes.shape[1]
-    out = dict(labels=torch.empty((M,), dtype=torch.int32, device=dev),
-               weights=torch.empty((M,), dtype=torch.float32, device=dev),
-               matched=torch.empty((M,), dtype=torch.int32, device=dev),
-               gt_boxes=torch.empty((M, 4), dtype=torch.float32, device=dev),
-               pgt_idx=torch.empty((n_img, gmax), dtype=torch.int32, device=dev),
-               pgt_boxes=torch.empty((n_img, gmax, 4), dtype=torch.float32, device=dev))
+    shapes = dict(labels=((M,), torch.int32), weights=((M,), torch.float32), matched=((M,), torch.int32),
+                  gt_boxes=((M, 4), torch.float32), pgt_idx=((n_img, gmax), torch.int32),
+                  pgt_boxes=((n_img, gmax, 4), torch.float32))
+    if out is None:
+        out = {k: torch.empty(s, dtype=dt, device=dev) for k, (s, dt) in shapes.items()}
+    for k, (s, dt) in shapes.items():
+        t = out[k]
+        assert t.dtype == dt and t.is_contiguous() and t.dim() == len(s) and t.shape[0] >= s[0] and t.shape[1:] == s[1:], k
     th, lb = C.host_floats(thresholds), C.host_ints(labels)
     C.call("drn_oicr_targets", C.ptr(prev_scores), _2d(prev_scores), C.ptr(prev_boxes), prev_boxes.shape[1],
            int(zero_delta_decode), C.ptr(props),

@@ -439,7 +439,12 @@ int drn_wsddn_fwd_bwd(const float* logits, long ld, int c_cls, int c_det, int K,
 /* OICRROIHeads.get_pgt (roi_heads_oicr.py:491-567) + ROIHeads.label_and_sample_proposals
  * (roi_heads.py:255-353; pairwise_iou structures/boxes.py:329-361; Matcher modeling/matcher.py:61-103).
  * prev_boxes [M][box_cols] with box_cols = 4 (Boxes path) or 4K (class-specific decoded boxes);
- * zero_delta_decode = 1 applies apply_deltas(0, .) to the selected box (what a non-regressing head passes on). */
+ * zero_delta_decode = 1 applies apply_deltas(0, .) to the selected box (what a non-regressing head passes on).
+ * gt_classes [n_img][gmax] (unique per image, any order; 1 <= gmax <= 128), of which the first gt_count[i] are used;
+ * pgt_idx / pgt_boxes slots from gt_count[i] on are not written.  1 <= nthr <= 3; anything else is refused.
+ * An image without ground truth (gt_count[i] == 0): labels K, weights 0, matched 0, gt_boxes 0 - the has_gt == False
+ * branch of label_and_sample_proposals, whatever thr_labels[0] is.  An image without proposals
+ * (img_off[i] == img_off[i+1]): no row is read or written; its first gt_count[i] slots are pgt_idx 0, pgt_boxes 0. */
 int drn_oicr_targets(const float* prev_scores, long ld_s, const float* prev_boxes, int box_cols, int zero_delta_decode,
                      const float* props,
                      const int* img_off, int n_img, const int* gt_classes, const int* gt_count, int gmax,

@@ -1258,7 +1258,8 @@ def test_mil_oicr_losses_without_bias(drn, K, M_per, nh, splits):
     _mil_equals_separate(drn, K, M_per, nh, splits, False)
 
 
-def _mil_equals_separate(drn, K, M_per, nh, splits, with_bias):
+def _mil_equals_separate(drn, K, M_per, nh, splits, with_bias, gmax=4, draws=3):
+    """gmax / draws: class slots per image and how many classes are drawn for it (test_oicr_targets_gpu.py raises both)"""
     M, n_img = sum(M_per), len(M_per)
     rs = np.random.RandomState(91)
     C_ = K + 1
@@ -1270,12 +1271,11 @@ def _mil_equals_separate(drn, K, M_per, nh, splits, with_bias):
     if not with_bias:
         bias = None
     props = _boxes(M, 35).to(DEV)
-    gmax = 4
     gcl = torch.zeros((n_img, gmax), dtype=torch.int32)
     gcn = torch.zeros((n_img,), dtype=torch.int32)
     oh = torch.zeros((n_img, K))
     for i in range(n_img):
-        g = torch.unique(torch.from_numpy(rs.randint(0, K, 3)))
+        g = torch.unique(torch.from_numpy(rs.randint(0, K, draws)))
         gcl[i, : len(g)] = g.int()
         gcn[i] = len(g)
         oh[i, g.long()] = 1
