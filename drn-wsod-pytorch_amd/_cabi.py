@@ -88,6 +88,7 @@ _SIGS = {
     "drn_detect_gather": "plippippppp",
     "drn_detect_topk_batch": "pppiiipi" + "ffi" + "pli" + "ppppp" + "p",
     "drn_detect_compact": "pppppii" + "p" + "ppppp" + "p",
+    "drn_detect_union_batch": "pppp" + "ii" + "pi" + "pp" + "i" + "ffi" + "pli" + "ppppp" + "p",
     "drn_coco_match": "pppi" + "pppp" + "iii" + "pi" + "pi" + "i" + "pli" + "pppppppp" + "p",
     "drn_coco_accumulate": "pppppi" + "piiii" + "pi" + "pi" + "pli" + "ppp" + "p",
     "drn_voc_match": "pppi" + "ppp" + "iii" + "pi" + "pli" + "pppppppp" + "p",
@@ -140,6 +141,8 @@ def lib():
         _lib.drn_detect_workspace_bytes.restype = ctypes.c_long
         _lib.drn_detect_batch_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         _lib.drn_detect_batch_workspace_bytes.restype = ctypes.c_long
+        _lib.drn_detect_union_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        _lib.drn_detect_union_workspace_bytes.restype = ctypes.c_long
         _lib.drn_gemm_nt_main_cols.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         _lib.drn_gemm_nt_main_cols.restype = ctypes.c_long
         _lib.drn_roi_pool_workspace_bytes.argtypes = [ctypes.c_int] * 10
@@ -157,7 +160,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_detect_batch_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
+    return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_detect_batch_workspace_bytes", "drn_detect_union_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
                                   "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes", "drn_grad_norms_ws_bytes"])
 
 

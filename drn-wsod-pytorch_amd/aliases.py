@@ -5,7 +5,7 @@ registry / key names + a thin alias layer").
     from detectron2.config import get_cfg                    # projects/WSL/tools/train_net.py:26
     from detectron2.checkpoint import DetectionCheckpointer   # :25
     from wsl.config import add_wsl_config                      # :45
-    from wsl.modeling import GeneralizedRCNNWithTTAAVG         # :46
+    from wsl.modeling import GeneralizedRCNNWithTTAAVG, GeneralizedRCNNWithTTAUNION   # :46
     from detectron2.layers import Conv2d, FrozenBatchNorm2d, ROIAlign, ShapeSpec, cat
     from detectron2.modeling import build_model, META_ARCH_REGISTRY, ROI_HEADS_REGISTRY
 
@@ -70,7 +70,8 @@ def _table():
         "detectron2.modeling.box_regression": pick(roi_heads, "Box2BoxTransform"),
         "wsl": {},
         "wsl.config": pick(config, "add_wsl_config"),
-        "wsl.modeling": dict(pick(tta, "GeneralizedRCNNWithTTAAVG", "DatasetMapperTTAAVG"),
+        "wsl.modeling": dict(pick(tta, "GeneralizedRCNNWithTTAAVG", "DatasetMapperTTAAVG", "GeneralizedRCNNWithTTAUNION",
+                                  "DatasetMapperTTAUNION"),
                              GeneralizedRCNNWSL=rcnn.GeneralizedRCNNWSL),
         "wsl.modeling.meta_arch": {"GeneralizedRCNNWSL": rcnn.GeneralizedRCNNWSL},
         "wsl.modeling.backbone": pick(backbone, "build_ws_resnet_backbone", "build_vgg_backbone", "ResNet", "VGG16", "BasicStem",

@@ -14,6 +14,16 @@
 
 namespace {
 
+// TransformList([ResizeTransform, HFlipTransform?]).inverse().apply_box on one box, in float32 op for op like the numpy code the
+// reference runs on the host: HFlipTransform.inverse (x -> W' - x, flip_w < 0 = not flipped), ResizeTransform.inverse (x * sx,
+// y * sy) on the four corners, then their bounding box.  Shared by the AVG accumulation and the UNION candidates.
+__device__ __forceinline__ void tta_inverse_box(const float* __restrict__ b, float sx, float sy, float flip_w, float o[4]) {
+  float x0 = b[0], y0 = b[1], x1 = b[2], y1 = b[3];
+  if (flip_w >= 0.f) { x0 = flip_w - x0; x1 = flip_w - x1; }
+  x0 = x0 * sx; x1 = x1 * sx; y0 = y0 * sy; y1 = y1 * sy;
+  o[0] = fminf(x0, x1); o[1] = fminf(y0, y1); o[2] = fmaxf(x0, x1); o[3] = fmaxf(y0, y1);
+}
+
 struct CandParams {
   const float* boxes;   // [R][4*nreg]
   const float* scores;  // [R][K+1]
@@ -483,6 +493,167 @@ inline BatchWs carve_batch(void* workspace, int cap) {
   return BatchWs{(int*)w, (float*)(w + 128), (int*)(w + 256), (int*)(w + BATCH_WS_HEAD)};
 }
 
+// ---- the tail shared by the batched entries: everything behind the candidates -----------------------------------------
+// On entry c_box / c_score / c_row / c_cls hold the candidates of all images in image-major order, count[0] their number (held
+// to cap), seg_off[b] the candidates in front of image b and maxcoord[b] the image's largest clipped coordinate (-inf: none).
+// Stable descending by score over all candidates: -> key1/order -> key0/val0 -> key1/order; then stable by image: -> key0/val0;
+// the NMS and the gather / postprocess run one wave per image.  15 launches whatever n_images is.
+void launch_sorted_tail(const Ws& k, const BatchWs& bw, const BatchGeom& g, int cap, int n_images, int postprocess,
+                        float nms_thresh, int topk, float* out_boxes, float* out_scores, int* out_classes, int* out_rows,
+                        int* out_count, hipStream_t st) {
+  const int tiles = sort_tiles(cap);
+  const int shifts[3] = {0, 11, 22}, bits[3] = {11, 11, 10};
+  for (int ps = 0; ps < 3; ++ps) {
+    const bool even = (ps & 1) == 0;
+    SortPass sp{k.c_score, even ? k.key0 : k.key1, even ? k.val0 : k.order, even ? k.key1 : k.key0,
+                even ? k.order : k.val0, k.hist, k.count, tiles, shifts[ps], bits[ps], ps == 0};
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  }
+  hipLaunchKernelGGL(image_key_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, k.order, k.count, bw.seg_off, n_images,
+                     k.key1);
+  {
+    SortPass sp{nullptr, k.key1, k.order, k.key0, k.val0, k.hist, k.count, tiles, 0, 4, 0};  // 4 bits: DET_MAX_IMAGES = 16
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  }
+  NmsParams np{k.c_box, k.c_score, k.c_cls, k.val0, k.count, bw.maxcoord, nms_thresh, topk, 40000, bw.keep, bw.n_keep};
+  hipLaunchKernelGGL(nms_topk_batch_kernel, dim3(n_images), dim3(64), 0, st, np, (const int*)bw.seg_off);
+  PostParams pp{k.c_box, k.c_score, k.c_row, k.c_cls, bw.keep, bw.n_keep, topk, postprocess ? 1 : 0, out_boxes, out_scores,
+                out_classes, out_rows, out_count};
+  hipLaunchKernelGGL(gather_post_kernel, dim3(n_images), dim3(64), 0, st, pp, g);
+}
+
+// ---- union of per-pass detections (wsl/modeling/test_time_augmentation_union.py:228-264) ---------------------------------
+// The candidates of the merge come from padded detection blocks instead of an [M][K+1] score matrix: slot s of block b is a
+// union row iff s < min(count[b], blk_topk); the blocks of image i are img_off[i] .. img_off[i+1].  Its box is mapped back
+// to the original image with the block's own (sx, sy, flip_w) and the row is dropped BEFORE numbering when the mapped box or the
+// score is not finite (detectron2 fast_rcnn.py:95-98); it is a candidate iff score > thresh and 0 <= class < K (the one non-zero
+// entry of its row of the reference's one-hot [n, K+1] matrix), with the box clipped to the original (h, w).  Candidates are
+// written in (block, slot) order = the row-major nonzero() order of that matrix.  One wave per block, two launches: pass 0
+// leaves every block's finite-row and candidate counts (and keeps the per-block transforms, which arrive as kernel arguments,
+// for pass 1), pass 1 places a block behind the sums of the counts in front of it.  Nothing beyond a block's count is read.
+constexpr int UNION_MAX_BLOCKS = 256;  // include/drn_wsod.h DRN_DETECT_UNION_MAX_BLOCKS
+
+// Per block (sx, sy, flip_w): 3 KiB of kernel arguments, which the runtime copies at the launch - so the host array is free when
+// the entry returns, without a staging buffer or a copy engine in the chain.  Only pass 0 takes the table and leaves it in the
+// workspace (three 4-byte stores per block) for pass 1: pass 1 already carries BatchGeom, and UnionParams + BatchGeom + this table
+// would come to ~3.6 KiB of the 4 KiB a launch may pass - too close to the limit to grow either struct later.
+// Both passes evaluate union_slot in full (load, back-transform, finite / candidate test): that is the price of two passes;
+// keeping pass 0's verdicts and boxes instead would cost a 20-byte store and load per slot to save ~10 VALU operations.
+struct UnionTfm { float v[UNION_MAX_BLOCKS][3]; };
+
+struct UnionParams {
+  const float* blk_boxes; const float* blk_scores; const int* blk_classes; const int* blk_count;
+  int n_blocks, blk_topk, K;
+  float thresh;
+  float* c_box; float* c_score; int* c_row; int* c_cls;
+  int* count;       // [1] candidates of all images
+  int* seg_off;     // [n_img + 1]
+  float* maxcoord;  // [n_img]
+  int cap;
+  int* blk_fin;     // [n_blocks] finite rows of the block
+  int* blk_cand;    // [n_blocks] candidates of the block
+  float* tfm;       // [n_blocks][3]
+};
+
+struct UnionWs { int* blk_fin; int* blk_cand; float* tfm; };
+constexpr long UNION_WS_BYTES = (long)UNION_MAX_BLOCKS * (4 + 4 + 12);
+inline UnionWs carve_union(void* workspace, int cap, int n_img) {
+  char* w = (char*)workspace + batch_ws_bytes(cap, n_img);
+  return UnionWs{(int*)w, (int*)(w + UNION_MAX_BLOCKS * 4), (float*)(w + UNION_MAX_BLOCKS * 8)};
+}
+
+// what slot s of block b is: bit 0 = a union row (finite), bit 1 = a candidate; o = the box on the original image, unclipped
+__device__ __forceinline__ int union_slot(const UnionParams& p, int b, int s, float sx, float sy, float flip_w, float o[4],
+                                          float* score, int* cls) {
+  const long i = (long)b * p.blk_topk + s;
+  const float* raw = p.blk_boxes + 4 * i;
+  tta_inverse_box(raw, sx, sy, flip_w, o);
+  *score = p.blk_scores[i];
+  *cls = p.blk_classes[i];
+  // (numpy's min / max hand a NaN corner on, fminf / fmaxf drop it: the raw coordinates are looked at as well)
+  const bool finite = isfinite(raw[0]) && isfinite(raw[1]) && isfinite(raw[2]) && isfinite(raw[3]) && isfinite(o[0]) &&
+                      isfinite(o[1]) && isfinite(o[2]) && isfinite(o[3]) && isfinite(*score);
+  const bool cand = finite && *score > p.thresh && *cls >= 0 && *cls < p.K;
+  return (finite ? 1 : 0) | (cand ? 2 : 0);
+}
+
+__global__ __launch_bounds__(64) void union_count_kernel(UnionParams p, UnionTfm t, int n_img) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float sx = t.v[b][0], sy = t.v[b][1], flip_w = t.v[b][2];
+  if (b == 0 && lane < n_img) p.maxcoord[lane] = -INFINITY;
+  if (lane < 3) p.tfm[3 * b + lane] = t.v[b][lane];
+  const int n = min(max(p.blk_count[b], 0), p.blk_topk);
+  int nfin = 0, ncand = 0;
+  for (int start = 0; start < n; start += 64) {
+    const int s = start + lane;
+    int what = 0;
+    if (s < n) {
+      float o[4], score;
+      int cls;
+      what = union_slot(p, b, s, sx, sy, flip_w, o, &score, &cls);
+    }
+    nfin += __popcll(__ballot(what & 1));
+    ncand += __popcll(__ballot(what & 2));
+  }
+  if (lane == 0) { p.blk_fin[b] = nfin; p.blk_cand[b] = ncand; }
+}
+
+__global__ __launch_bounds__(64) void union_place_kernel(UnionParams p, BatchGeom g) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int img = image_of(g.img_off, g.n_img, b);
+  // candidates of all blocks in front of this one; finite rows of this image's blocks in front of this one
+  int cbase = 0, rbase = 0;
+  for (int q = lane; q < b; q += 64) {
+    cbase += p.blk_cand[q];
+    if (q >= g.img_off[img]) rbase += p.blk_fin[q];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cbase += __shfl_xor(cbase, o, 64);
+    rbase += __shfl_xor(rbase, o, 64);
+  }
+  if (lane == 0)  // the first block of image i (an image without blocks shares it with its successor)
+    for (int i = 0; i < g.n_img; ++i)
+      if (g.img_off[i] == b) p.seg_off[i] = cbase;
+  const float sx = p.tfm[3 * b], sy = p.tfm[3 * b + 1], flip_w = p.tfm[3 * b + 2];
+  const float iw = g.w[img], ih = g.h[img];
+  const int n = min(max(p.blk_count[b], 0), p.blk_topk);
+  int pos0 = cbase, row0 = rbase;
+  float mymax = -INFINITY;
+  for (int start = 0; start < n; start += 64) {
+    const int s = start + lane;
+    int what = 0, cls = -1;
+    float o[4] = {0.f, 0.f, 0.f, 0.f}, score = 0.f;
+    if (s < n) what = union_slot(p, b, s, sx, sy, flip_w, o, &score, &cls);
+    const unsigned long long fbal = __ballot(what & 1), cbal = __ballot(what & 2);
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+    if (what & 2) {
+      const int pos = pos0 + __popcll(cbal & below);
+      if (pos < p.cap) {
+        const float x1 = fminf(fmaxf(o[0], 0.f), iw), y1 = fminf(fmaxf(o[1], 0.f), ih);
+        const float x2 = fminf(fmaxf(o[2], 0.f), iw), y2 = fminf(fmaxf(o[3], 0.f), ih);
+        p.c_box[4 * (long)pos] = x1; p.c_box[4 * (long)pos + 1] = y1; p.c_box[4 * (long)pos + 2] = x2; p.c_box[4 * (long)pos + 3] = y2;
+        p.c_score[pos] = score; p.c_row[pos] = row0 + __popcll(fbal & below); p.c_cls[pos] = cls;
+        mymax = fmaxf(mymax, fmaxf(fmaxf(x1, y1), fmaxf(x2, y2)));
+      }
+    }
+    pos0 += __popcll(cbal);
+    row0 += __popcll(fbal);
+  }
+  mymax = wave_max(mymax);
+  // (clipped coordinates are >= 0 and finite: their bit patterns order like the values; -inf stays for "none")
+  if (lane == 0 && mymax >= 0.f) atomicMax((int*)p.maxcoord + img, __builtin_bit_cast(int, mymax));
+  if (b == p.n_blocks - 1 && lane == 0) {
+    p.count[0] = pos0 < p.cap ? pos0 : p.cap;
+    for (int i = 0; i <= g.n_img; ++i)  // images without blocks at the end, and the end itself
+      if (g.img_off[i] >= p.n_blocks) p.seg_off[i] = pos0;
+  }
+}
+
 // ---- padded blocks -> packed detections -------------------------------------------------------------------------------
 // off[b] = sum of the counts (held to 0 .. topk) in front of block b, off[B] = n: one workgroup
 __global__ __launch_bounds__(1024) void compact_offsets_kernel(const int* __restrict__ count, int B, int topk, int* __restrict__ off,
@@ -539,11 +710,8 @@ __global__ void tta_accumulate_kernel(const float* __restrict__ boxes, const flo
                                       float sx, float sy, float flip_w, int first, int n_final) {
   const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (i < nbox) {
-    const float* b = boxes + 4 * i;
-    float x0 = b[0], y0 = b[1], x1 = b[2], y1 = b[3];
-    if (flip_w >= 0.f) { x0 = flip_w - x0; x1 = flip_w - x1; }
-    x0 = x0 * sx; x1 = x1 * sx; y0 = y0 * sy; y1 = y1 * sy;
-    const float o[4] = {fminf(x0, x1), fminf(y0, y1), fmaxf(x0, x1), fmaxf(y0, y1)};
+    float o[4];
+    tta_inverse_box(boxes + 4 * i, sx, sy, flip_w, o);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float v = first ? o[e] : acc_boxes[4 * i + e] + o[e];
@@ -666,30 +834,58 @@ int drn_detect_topk_batch(const float* boxes, const float* scores, const int* im
     (void)hipMemsetAsync(k.count, 0, sizeof(int), st);
     (void)hipMemsetAsync(bw.seg_off, 0, sizeof(int) * (DET_MAX_IMAGES + 1), st);
   }
-  // stable descending by score over all candidates: -> key1/order -> key0/val0 -> key1/order; then stable by image: -> key0/val0
-  const int tiles = sort_tiles(cap);
-  const int shifts[3] = {0, 11, 22}, bits[3] = {11, 11, 10};
-  for (int ps = 0; ps < 3; ++ps) {
-    const bool even = (ps & 1) == 0;
-    SortPass sp{k.c_score, even ? k.key0 : k.key1, even ? k.val0 : k.order, even ? k.key1 : k.key0,
-                even ? k.order : k.val0, k.hist, k.count, tiles, shifts[ps], bits[ps], ps == 0};
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  launch_sorted_tail(k, bw, g, cap, n_images, postprocess, nms_thresh, topk, out_boxes, out_scores, out_classes, out_rows,
+                     out_count, st);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// bytes of scratch drn_detect_union_batch needs for n_images images with total_cap >= n_blocks * blk_topk slots in all
+long drn_detect_union_workspace_bytes(int total_cap, int n_images) {
+  return batch_ws_bytes(total_cap < 1 ? 1 : total_cap, n_images < 1 ? 1 : n_images) + UNION_WS_BYTES + 256;
+}
+
+// The union merge of per-pass detections (see include/drn_wsod.h).  img_off_host [n_images + 1] (in blocks), tfm_host
+// [n_blocks][3] and geom_host [n_images][2] are HOST arrays, read before the call returns.  Nothing is read back from the device.
+int drn_detect_union_batch(const float* blk_boxes, const float* blk_scores, const int* blk_classes, const int* blk_count,
+                           int n_blocks, int blk_topk, const int* img_off_host, int n_images, const float* tfm_host,
+                           const float* geom_host, int K, float score_thresh, float nms_thresh, int topk, void* workspace,
+                           long workspace_bytes, int total_cap, float* out_boxes, float* out_scores, int* out_classes,
+                           int* out_rows, int* out_count, void* stream) {
+  if (!blk_boxes || !blk_scores || !blk_classes || !blk_count || !img_off_host || !tfm_host || !geom_host || !workspace ||
+      !out_boxes || !out_scores || !out_classes || !out_rows || !out_count || total_cap < 1 || K < 1)
+    return DRN_ERR_ARG;
+  if (n_images < 1 || n_images > DET_MAX_IMAGES || n_blocks < 1 || n_blocks > UNION_MAX_BLOCKS || blk_topk < 1 ||
+      blk_topk > NMS_MAXK || topk < 1 || topk > NMS_MAXK)
+    return DRN_ERR_UNSUPPORTED;
+  BatchGeom g{};
+  g.n_img = n_images;
+  if (img_off_host[0] != 0 || img_off_host[n_images] != n_blocks) return DRN_ERR_ARG;
+  for (int b = 0; b <= n_images; ++b) {
+    g.img_off[b] = img_off_host[b];
+    if (b > 0 && img_off_host[b] < img_off_host[b - 1]) return DRN_ERR_ARG;
   }
-  hipLaunchKernelGGL(image_key_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, k.order, k.count, bw.seg_off, n_images,
-                     k.key1);
-  {
-    SortPass sp{nullptr, k.key1, k.order, k.key0, k.val0, k.hist, k.count, tiles, 0, 4, 0};  // 4 bits: DET_MAX_IMAGES = 16
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  for (int b = n_images + 1; b <= DET_MAX_IMAGES; ++b) g.img_off[b] = n_blocks;
+  for (int b = 0; b < n_images; ++b) {  // merged instances are not postprocessed: (oh, ow, sx, sy) only mirror (h, w, 1, 1)
+    g.h[b] = g.oh[b] = geom_host[2 * b]; g.w[b] = g.ow[b] = geom_host[2 * b + 1];
+    g.sx[b] = g.sy[b] = 1.f;
   }
-  NmsParams np{k.c_box, k.c_score, k.c_cls, k.val0, k.count, bw.maxcoord, nms_thresh, topk, 40000, bw.keep, bw.n_keep};
-  hipLaunchKernelGGL(nms_topk_batch_kernel, dim3(n_images), dim3(64), 0, st, np, (const int*)bw.seg_off);
-  PostParams pp{k.c_box, k.c_score, k.c_row, k.c_cls, bw.keep, bw.n_keep, topk, postprocess ? 1 : 0, out_boxes, out_scores,
-                out_classes, out_rows, out_count};
-  hipLaunchKernelGGL(gather_post_kernel, dim3(n_images), dim3(64), 0, st, pp, g);
+  const long slots = (long)n_blocks * blk_topk;
+  if ((long)total_cap < slots || total_cap > DET_MAX_ENTRIES) return DRN_ERR_ARG;
+  const int cap = total_cap;
+  if (workspace_bytes < drn_detect_union_workspace_bytes(cap, n_images)) return DRN_ERR_ARG;
+  UnionTfm t{};
+  for (int b = 0; b < n_blocks; ++b)
+    for (int e = 0; e < 3; ++e) t.v[b][e] = tfm_host[3 * b + e];
+  hipStream_t st = (hipStream_t)stream;
+  Ws k = carve(workspace, workspace_bytes, cap);
+  BatchWs bw = carve_batch(workspace, cap);
+  UnionWs uw = carve_union(workspace, cap, n_images);
+  UnionParams up{blk_boxes, blk_scores, blk_classes, blk_count, n_blocks, blk_topk, K, score_thresh, k.c_box, k.c_score,
+                 k.c_row, k.c_cls, k.count, bw.seg_off, bw.maxcoord, cap, uw.blk_fin, uw.blk_cand, uw.tfm};
+  hipLaunchKernelGGL(union_count_kernel, dim3(n_blocks), dim3(64), 0, st, up, t, n_images);
+  hipLaunchKernelGGL(union_place_kernel, dim3(n_blocks), dim3(64), 0, st, up, g);
+  launch_sorted_tail(k, bw, g, cap, n_images, 0, nms_thresh, topk, out_boxes, out_scores, out_classes, out_rows, out_count, st);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }

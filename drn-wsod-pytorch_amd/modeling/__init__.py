@@ -4,5 +4,5 @@ from .backbone import (Backbone, BasicBlock, BasicStem, BottleneckBlock, PlainBl
 from .rcnn import GeneralizedRCNNWSL, build_model, detector_postprocess
 from .roi_heads import (Box2BoxTransform, DiscriminativeAdaptionNeck, FastRCNNConvFCHead, Matcher, OICROutputLayers, OICRROIHeads, ROIHeads,
                         PCLROIHeads, ROIPooler, WSDDNOutputLayers, WSDDNROIHeads, build_box_head, build_roi_heads)
-from .tta import DatasetMapperTTAAVG, GeneralizedRCNNWithTTAAVG
+from .tta import DatasetMapperTTAAVG, DatasetMapperTTAUNION, GeneralizedRCNNWithTTAAVG, GeneralizedRCNNWithTTAUNION
 from ..registry import BACKBONE_REGISTRY, META_ARCH_REGISTRY, ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY

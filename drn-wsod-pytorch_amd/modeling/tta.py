@@ -9,6 +9,7 @@ stays on the GPU: one `model.inference` per augmentation, `drn_tta_accumulate` m
 predictions back to the original image and folds them into the running box / score averages (the reference copies
 them to the host and back for this), and `drn_detect_topk` runs the final score-threshold / NMS / top-k."""
 import copy
+import logging
 
 import numpy as np
 import torch
@@ -20,7 +21,8 @@ from .._cabi import DrnError
 from ..structures import Boxes, DetectionBatch, Instances
 from .roi_heads import padded_detections
 
-__all__ = ["DatasetMapperTTAAVG", "GeneralizedRCNNWithTTAAVG", "resize_shortest_edge_shape"]
+__all__ = ["DatasetMapperTTAAVG", "GeneralizedRCNNWithTTAAVG", "DatasetMapperTTAUNION", "GeneralizedRCNNWithTTAUNION",
+           "resize_shortest_edge_shape"]
 
 VECTORISED_MAPPER = True  # tools: False = the per-augmentation mapper (its proposals are uploaded inside each pass)
 
@@ -203,6 +205,35 @@ class DatasetMapperTTAAVG:
                 yield dic
 
 
+class DatasetMapperTTAUNION(DatasetMapperTTAAVG):
+    """test_time_augmentation_union.py:27-82: the AVG mapper's augmented images (the same code path: host PIL, or
+    drn_resize_bilinear_u8 on `device`) and the same "tta" = (sx, sy, flip_w) key - but, restated as the reference has it,
+    dataset_dict["proposals"] is NOT transformed: with MODEL.LOAD_PROPOSALS every augmentation gets the ORIGINAL image's
+    proposals unchanged (the object itself, untouched), whatever the size or flip of its image (the reference's constructor
+    assertion against it is disabled, :109-111).  That is the reference's default for GeneralizedRCNNWithTTAUNION and is kept as
+    the default here; it is warned about once.  GeneralizedRCNNWithTTAUNION(cfg, model, tta_mapper=DatasetMapperTTAAVG(cfg,
+    device=...)) is the combination whose proposals follow their images."""
+
+    _warned = False
+
+    def __init__(self, cfg, device=None):
+        super().__init__(cfg, device=device)
+        self.load_proposals = bool(cfg.MODEL.LOAD_PROPOSALS)
+        self.proposal_topk = None  # the AVG code path then leaves "proposals" out: they are passed through below
+
+    def __call__(self, dataset_dict):
+        out = super().__call__(dataset_dict)
+        if "proposals" in dataset_dict:
+            if self.load_proposals and not DatasetMapperTTAUNION._warned:
+                DatasetMapperTTAUNION._warned = True
+                logging.warning("DatasetMapperTTAUNION leaves precomputed proposals in the ORIGINAL image's coordinates for every "
+                                "augmentation, as the reference does (test_time_augmentation_union.py:27-82); pass "
+                                "tta_mapper=DatasetMapperTTAAVG(cfg, device=...) for proposals that follow their images")
+            for dic in out:
+                dic["proposals"] = dataset_dict["proposals"]
+        return out
+
+
 class GeneralizedRCNNWithTTAAVG(nn.Module):
     """test_time_augmentation_avg.py:139-321 (box branch; masks / keypoints are off the WSL path)."""
 
@@ -291,3 +322,68 @@ class GeneralizedRCNNWithTTAAVG(nn.Module):
         r.scores = os_
         r.pred_classes = oc
         return {"instances": r}
+
+
+class GeneralizedRCNNWithTTAUNION(GeneralizedRCNNWithTTAAVG):
+    """test_time_augmentation_union.py:85-264 (box branch): every augmentation's OWN detections (threshold / NMS / top-k per pass),
+    mapped back to the original image, concatenated in augmentation order then detection order, and merged by one more
+    threshold (1e-8) / NMS / top-k over the union.  Unlike the AVG form the augmentations may keep different numbers of
+    proposals.  On the device this is two launch chains per image whatever the number of augmentations: ONE batched tail over
+    the passes as "images" (padded_detections) and ONE drn_detect_union_batch; the reference runs a tail per pass, moves every
+    pass's boxes to the host and back, and fills its [n, K+1] score matrix one element at a time.
+
+    tta_mapper defaults to DatasetMapperTTAUNION as in the reference - which leaves precomputed proposals untransformed, see its
+    docstring; DatasetMapperTTAAVG is accepted as well.  padded=True: __call__ returns a DetectionBatch on the original image
+    sizes and reads nothing back; otherwise the reference's list of {"instances": ...}, at one read of the count per image."""
+
+    MERGE_SCORE_THRESH = 1e-8  # :259
+
+    def __init__(self, cfg, model, tta_mapper=None, batch_size=1, padded=False):
+        inner = getattr(model, "module", model)
+        if tta_mapper is None:
+            tta_mapper = DatasetMapperTTAUNION(cfg, device=getattr(inner, "device", None))
+        super().__init__(cfg, model, tta_mapper=tta_mapper, batch_size=batch_size, padded=padded)
+
+    def _get_augmented_detections(self, augmented_inputs):
+        """_batch_inference + the per-pass tails (:146-170, :228-230): a DetectionBatch with one block per augmentation, in the
+        augmented images' coordinates, and the passes' (sx, sy, flip_w)"""
+        heads = self.model.roi_heads
+        all_b, all_s, nper, sizes = [], [], [], []
+        # the passes deliver scores / boxes alone; their tails then run in ONE chain instead of one per pass
+        prev, heads.scores_only = heads.scores_only, True
+        try:
+            for g0 in range(0, len(augmented_inputs), self.batch_size):
+                group = augmented_inputs[g0: g0 + self.batch_size]
+                _, scores, boxes = self.model.inference([{k: v for k, v in inp.items() if k != "tta"} for inp in group],
+                                                        do_postprocess=False)
+                for j, inp in enumerate(group):
+                    all_b.append(boxes[j][0])
+                    all_s.append(scores[j][0])
+                    nper.append(int(scores[j][0].shape[0]))
+                    # a pass clips to its proposals' image size (fast_rcnn.py: image_shapes = [x.image_size for x in proposals]):
+                    # the augmented image's under DatasetMapperTTAAVG, the original image's under DatasetMapperTTAUNION
+                    sizes.append(tuple(inp["proposals"].image_size) if "proposals" in inp else tuple(inp["image"].shape[1:]))
+        finally:
+            heads.scores_only = prev
+        det = padded_detections(torch.cat(all_b).contiguous(), torch.cat(all_s).contiguous(), nper, sizes, None,
+                                self.cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST, self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST,
+                                self.cfg.TEST.DETECTIONS_PER_IMAGE)
+        return det, [inp["tta"] for inp in augmented_inputs]
+
+    def _merge_detections(self, det, tfms, orig_shape):
+        """:246-264 with the back-transform of :236-239 inside: ops.detect_union_batch on the passes' blocks"""
+        return ops.detect_union_batch(det.boxes, det.scores, det.classes, det.count, [0, len(det)], tfms, [orig_shape],
+                                      num_classes=self.cfg.MODEL.ROI_HEADS.NUM_CLASSES, score_thresh=self.MERGE_SCORE_THRESH,
+                                      nms_thresh=self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST,
+                                      topk=self.cfg.TEST.DETECTIONS_PER_IMAGE)
+
+    def _inference_one_image(self, input):
+        orig_shape = (input["height"], input["width"])
+        with torch.no_grad():
+            augmented_inputs = self.tta_mapper(input)
+            det, tfms = self._get_augmented_detections(augmented_inputs)
+            ob, os_, oc, orow, cnt = self._merge_detections(det, tfms, orig_shape)
+        merged = DetectionBatch(ob, os_, oc, cnt, [orig_shape], self.cfg.TEST.DETECTIONS_PER_IMAGE, rows=orow)
+        if self.padded:
+            return merged
+        return merged.to_outputs()[0]  # (merged instances are not postprocessed, :220-221)

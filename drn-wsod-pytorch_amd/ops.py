@@ -1438,6 +1438,69 @@ def detect_topk_batch(boxes, scores, img_off, image_sizes, output_sizes=None, *,
     return ob, os_, oc, orow, cnt
 
 
+DETECT_UNION_MAX_BLOCKS = 256  # include/drn_wsod.h DRN_DETECT_UNION_MAX_BLOCKS
+
+
+def detect_union_batch(boxes, scores, classes, count, img_off, tfms, image_sizes, *, num_classes, score_thresh=1e-8, nms_thresh,
+                       topk):
+    """GeneralizedRCNNWithTTAUNION's merge for all images of a call in one launch chain, without a host read
+    (drn_detect_union_batch).  boxes [B, blk_topk, 4] f32, scores [B, blk_topk] f32, classes [B, blk_topk] i32, count [B] i32: the
+    padded blocks of detect_topk_batch, one per augmentation pass; the blocks of image i are img_off[i] .. img_off[i + 1] (N + 1 HOST
+    ints); tfms: B (sx, sy, flip_w) of the inverse box transform (sx, sy rounded to float32 like the reference's numpy code);
+    image_sizes: N (h, w) of the original images.  Returns the padded tensors of detect_topk_batch (boxes [N, topk, 4], scores,
+    classes, rows [N, topk], count [N]); rows index the image's finite union rows in (block, slot) order.  The limits (N <= 16,
+    B <= 256, blk_topk and topk <= 1024) raise DrnError before the library is touched."""
+    if torch.is_tensor(img_off):
+        if img_off.is_cuda:
+            raise C.DrnError("detect_union_batch: img_off is known on the host; a device tensor would have to be read back")
+        img_off = img_off.tolist()
+    off = [int(v) for v in img_off]
+    n_img = len(off) - 1
+    if scores.dim() != 2:
+        raise C.DrnError("detect_union_batch: scores are padded blocks [B, blk_topk]")
+    B, blk_topk = scores.shape
+    if not 1 <= n_img <= DETECT_MAX_IMAGES:
+        raise C.DrnError("detect_union_batch: %d images, 1 .. %d per call are built" % (n_img, DETECT_MAX_IMAGES))
+    if not 1 <= B <= DETECT_UNION_MAX_BLOCKS:
+        raise C.DrnError("detect_union_batch: %d blocks, 1 .. %d per call are built" % (B, DETECT_UNION_MAX_BLOCKS))
+    if not 1 <= blk_topk <= 1024:
+        raise C.DrnError("detect_union_batch: blocks of %d slots, 1 .. 1024 are built" % blk_topk)
+    if not 1 <= int(topk) <= 1024:
+        raise C.DrnError("detect_union_batch: topk = %d, 1 .. 1024 are built" % topk)
+    if int(num_classes) < 1:
+        raise C.DrnError("detect_union_batch: num_classes = %d" % num_classes)
+    if off[0] != 0 or off[-1] != B or any(b < a for a, b in zip(off[:-1], off[1:])):
+        raise C.DrnError("detect_union_batch: img_off %s does not split %d blocks into %d images" % (off, B, n_img))
+    if tuple(boxes.shape) != (B, blk_topk, 4) or tuple(classes.shape) != (B, blk_topk) or tuple(count.shape) != (B,):
+        raise C.DrnError("detect_union_batch: boxes %s / classes %s / count %s do not match scores %s"
+                         % (tuple(boxes.shape), tuple(classes.shape), tuple(count.shape), tuple(scores.shape)))
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or classes.dtype != torch.int32 or count.dtype != torch.int32:
+        raise C.DrnError("detect_union_batch: boxes / scores are float32, classes / count int32")
+    if len(tfms) != B or len(image_sizes) != n_img:
+        raise C.DrnError("detect_union_batch: one (sx, sy, flip_w) per block and one (h, w) per image")
+    tfm = []
+    for sx, sy, flip_w in tfms:
+        tfm += [np.float32(sx), np.float32(sy), flip_w]
+    geom = []
+    for h, w in image_sizes:
+        geom += [h, w]
+    dev = scores.device
+    cap = B * blk_topk
+    nbytes = C.lib().drn_detect_union_workspace_bytes(cap, n_img)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    boxes, scores, classes, count = boxes.contiguous(), scores.contiguous(), classes.contiguous(), count.contiguous()
+    ob = torch.empty((n_img, topk, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((n_img, topk), dtype=torch.float32, device=dev)
+    oc = torch.empty((n_img, topk), dtype=torch.int32, device=dev)
+    orow = torch.empty((n_img, topk), dtype=torch.int32, device=dev)
+    cnt = torch.empty((n_img,), dtype=torch.int32, device=dev)
+    C.call("drn_detect_union_batch", C.ptr(boxes), C.ptr(scores), C.ptr(classes), C.ptr(count), B, blk_topk,
+           ctypes.cast(C.host_ints(off), ctypes.c_void_p), n_img, ctypes.cast(C.host_floats(tfm), ctypes.c_void_p),
+           ctypes.cast(C.host_floats(geom), ctypes.c_void_p), int(num_classes), float(score_thresh), float(nms_thresh), int(topk),
+           C.ptr(ws), nbytes, cap, C.ptr(ob), C.ptr(os_), C.ptr(oc), C.ptr(orow), C.ptr(cnt), C.stream())
+    return ob, os_, oc, orow, cnt
+
+
 def detections_compact(boxes, scores, classes, count, image_index):
     """Padded blocks -> packed detections on the device (drn_detect_compact): boxes [B, topk, 4] f32, scores [B, topk] f32,
     classes [B, topk] i32, count [B] i32, image_index [B] i32 -> (boxes [B*topk, 4], scores, classes, images [B*topk], n [1] i32):

@@ -793,6 +793,31 @@ int drn_detect_compact(const float* boxes, const float* scores, const int* class
 int drn_tta_accumulate(const float* boxes, const float* scores, float* acc_boxes, float* acc_scores, long n_boxes,
                        long n_scores, float sx, float sy, float flip_w, int first, int n_final, void* stream);
 
+/* GeneralizedRCNNWithTTAUNION._get_augmented_boxes + _merge_detections (projects/WSL/wsl/modeling/
+ * test_time_augmentation_union.py:228-264): the detections of every augmentation's own inference tail, mapped back to the
+ * original image and merged by ONE more threshold / NMS / top-k over their union, for all images of a call in one launch chain
+ * (2 launches that build the candidates + the tail drn_detect_topk_batch runs behind its own candidates); nothing is read back.
+ * Inputs are the padded blocks drn_detect_topk_batch leaves: blk_boxes [n_blocks][blk_topk][4], blk_scores / blk_classes
+ * [n_blocks][blk_topk], blk_count [n_blocks] on the device.  The blocks of image i are img_off_host[i] .. img_off_host[i + 1]
+ * (HOST, ascending from 0 to n_blocks).  tfm_host [n_blocks][3] (HOST) = per block (sx, sy, flip_w) of drn_tta_accumulate;
+ * geom_host [n_images][2] (HOST) = (h, w) of the original image.
+ * Slot s of block b is a union row iff s < min(blk_count[b], blk_topk); nothing beyond a block's count is read.  Its box goes
+ * through the float32 inverse transform of drn_tta_accumulate; a row whose mapped box or score is not finite is dropped before
+ * numbering (detectron2 fast_rcnn.py:95-98), and out_rows index the image's remaining union rows in (block, slot) order.  A row
+ * is a candidate iff score > score_thresh (the reference passes 1e-8) and 0 <= class < K; its box is clipped to (h, w).
+ * Candidate order = (block, slot) = the row-major nonzero() order of the reference's one-hot [n, K + 1] score matrix, so the
+ * stable sort keeps score ties in union order.  Outputs: padded blocks [n_images][topk] with the layout and fill rule of
+ * drn_detect_topk_batch (no postprocess: merged instances stay on the original image's (h, w)).
+ * Limits (DRN_ERR_UNSUPPORTED before any launch): 1 <= n_images <= DRN_DETECT_MAX_IMAGES, 1 <= n_blocks <=
+ * DRN_DETECT_UNION_MAX_BLOCKS, 1 <= blk_topk <= 1024, 1 <= topk <= 1024.  total_cap >= n_blocks * blk_topk sizes the workspace. */
+#define DRN_DETECT_UNION_MAX_BLOCKS 256
+long drn_detect_union_workspace_bytes(int total_cap, int n_images);
+int drn_detect_union_batch(const float* blk_boxes, const float* blk_scores, const int* blk_classes, const int* blk_count,
+                           int n_blocks, int blk_topk, const int* img_off_host, int n_images, const float* tfm_host,
+                           const float* geom_host, int K, float score_thresh, float nms_thresh, int topk, void* workspace,
+                           long workspace_bytes, int total_cap, float* out_boxes, float* out_scores, int* out_classes,
+                           int* out_rows, int* out_count, void* stream);
+
 /* ---- COCO box-AP evaluation (COCOEvaluator -> COCOeval_opt; detectron2/layers/csrc/cocoeval/cocoeval.cpp) -----------
  * The two native stages of the reference's evaluator, EvaluateImages (:141-198) and Accumulate (:371-497), on the device
  * and bit-identical to the C++: integer counts and single IEEE fp64 operations in its order.  The IoU is pycocotools'
