@@ -91,6 +91,7 @@ _SIGS = {
     "drn_detect_union_batch": "pppp" + "ii" + "pi" + "pp" + "i" + "ffi" + "pli" + "ppppp" + "p",
     "drn_coco_match": "pppi" + "pppp" + "iii" + "pi" + "pi" + "i" + "pli" + "pppppppp" + "p",
     "drn_coco_accumulate": "pppppi" + "piiii" + "pi" + "pi" + "pli" + "ppp" + "p",
+    "drn_proposal_recall": "pppi" + "pppi" + "iii" + "pi" + "pi" + "pi" + "pli" + "ppp" + "p",
     "drn_voc_match": "pppi" + "ppp" + "iii" + "pi" + "pli" + "pppppppp" + "p",
     "drn_voc_accumulate": "ppi" + "pppp" + "iii" + "pi" + "ii" + "pppp" + "p",
     "drn_csc_cpg": "piiiiippp",
@@ -151,6 +152,8 @@ def lib():
         _lib.drn_roi_backward_det_ws_bytes.restype = ctypes.c_long
         _lib.drn_grad_norms_ws_bytes.argtypes = [ctypes.c_int]
         _lib.drn_grad_norms_ws_bytes.restype = ctypes.c_long
+        _lib.drn_proposal_recall_workspace_bytes.argtypes = [ctypes.c_int]
+        _lib.drn_proposal_recall_workspace_bytes.restype = ctypes.c_long
         _lib.drn_augment_lds_bytes.argtypes = [ctypes.c_int] * 7
         _lib.drn_augment_lds_bytes.restype = ctypes.c_long
         for kv in filter(None, os.environ.get("DRN_TUNE", "").split(",")):  # A/B runs: DRN_TUNE="5=0,4=1024" (drn_tune knobs)
@@ -161,7 +164,7 @@ def lib():
 
 def exported_symbols():
     return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_detect_batch_workspace_bytes", "drn_detect_union_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
-                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes", "drn_grad_norms_ws_bytes"])
+                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes", "drn_grad_norms_ws_bytes", "drn_proposal_recall_workspace_bytes"])
 
 
 _ERR = {-1: "invalid argument", -2: "kernel launch failure", -3: "unsupported"}

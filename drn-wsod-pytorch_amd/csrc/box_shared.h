@@ -57,6 +57,16 @@ __device__ __forceinline__ int label_row(const AnnotLds& s, int G, float x1, flo
   return cls;
 }
 
+// pairwise_iou (boxes.py:329-361) of ONE pair, the arithmetic of label_row's loop body: g = the staged box with its corner area,
+// (x1, y1, x2, y2) / a2 = the other box and its corner area.  Used by the proposal-recall matching (proprecall.hip).
+__device__ __forceinline__ float pair_iou(float gx1, float gy1, float gx2, float gy2, float garea, float x1, float y1, float x2,
+                                          float y2, float a2) {
+  const float iw = fmaxf(fminf(gx2, x2) - fmaxf(gx1, x1), 0.f);
+  const float ih = fmaxf(fminf(gy2, y2) - fmaxf(gy1, y1), 0.f);
+  const float inter = iw * ih;
+  return inter > 0.f ? inter / (garea + a2 - inter) : 0.f;
+}
+
 // host side: thresholds / labels -> MatcherArgs; false = a label outside {-1, 0, 1}
 inline bool matcher_args(const float* thresholds, const int* match_labels, int nthr, MatcherArgs& a) {
   a = MatcherArgs{};

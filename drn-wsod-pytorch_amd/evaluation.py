@@ -15,7 +15,11 @@ COCO box AP: `COCOEvaluator` (detectron2/evaluation/coco_evaluation.py:33-306, b
 (:308-367).  The reference hands its predictions to COCOeval_opt, whose two expensive stages are native C++
 (detectron2/layers/csrc/cocoeval/cocoeval.cpp); here both run on the device (ops.coco_match / ops.coco_accumulate,
 csrc/cocoeval.hip) and the predictions never leave it before the three result arrays are read back.  Pinned by
-tests/golden/coco_eval.npz (the unmodified C++ on synthetic, tie-heavy annotation sets)."""
+tests/golden/coco_eval.npz (the unmodified C++ on synthetic, tie-heavy annotation sets).
+
+Box-proposal recall: `ProposalRecallEvaluator` / `evaluate_box_proposals`, the reference's box_proposals task
+(coco_evaluation.py:200-237, :372-480: AR@k by area), matched on the device (ops.proposal_recall, csrc/proprecall.hip;
+DESIGN 4.17); `COCOEvaluator` hands outputs that carry "proposals" to it.  Pinned by tests/golden/proposal_recall.npz."""
 import contextlib
 import json
 import os
@@ -26,7 +30,8 @@ import numpy as np
 
 __all__ = ["PascalVOCDetectionEvaluator", "parse_rec", "voc_ap", "voc_eval", "voc_eval_corloc", "format_prediction",
            "COCOEvaluator", "instances_to_coco_json", "coco_params", "coco_summarize", "derive_coco_results",
-           "inference_on_dataset", "inference_context", "DatasetEvaluators"]
+           "inference_on_dataset", "inference_context", "DatasetEvaluators", "ProposalRecallEvaluator",
+           "evaluate_box_proposals", "proposal_recall_key", "PROPOSAL_AREAS"]
 
 
 # ---- the dataset loop (detectron2/evaluation/evaluator.py:64-200) ------------------------------------------------------
@@ -540,6 +545,7 @@ class COCOEvaluator:
             crowd=np.array([1 if anns[j].get("iscrowd", 0) else 0 for j in o], np.uint8),
             off=np.concatenate([[0], np.cumsum(np.bincount(pair, minlength=I * K))]).astype(np.int32))
         self._gather, self._device = gather, device
+        self._annotations = annotations  # for the box_proposals task, indexed when the first such output arrives
         self.params = coco_params()
         self.stats, self.eval, self._mark = None, None, None
         self.reset()
@@ -547,6 +553,7 @@ class COCOEvaluator:
     def reset(self):
         self._boxes, self._scores, self._classes, self._images = [], [], [], []
         self._padded = []  # (number of per-image entries in front of it, padded block): DetectionBatch outputs
+        self._proposals = None  # the ProposalRecallEvaluator of outputs that carry "proposals"
 
     def process(self, inputs, outputs):
         """outputs: a list of {"instances": Instances} or a structures.DetectionBatch, which is kept as padded blocks without
@@ -563,6 +570,12 @@ class COCOEvaluator:
             iid = int(inp["image_id"])
             if iid not in self._img_index:
                 raise ValueError("image_id %r is not in the annotation file" % (inp["image_id"],))
+            if "proposals" in out:  # coco_evaluation.py:119-120: the box_proposals task
+                if self._proposals is None:
+                    self._proposals = ProposalRecallEvaluator(self._annotations, gather=self._gather, device=self._device)
+                self._proposals.process([inp], [out])
+                if "instances" not in out:
+                    continue
             inst = out["instances"]
             self._boxes.append(inst.pred_boxes.tensor.detach())
             self._scores.append(inst.scores.detach())
@@ -585,6 +598,18 @@ class COCOEvaluator:
                 torch.cat(self._classes).to(torch.int32), img)
 
     def evaluate(self):
+        """OrderedDict(bbox=...) as ever; when outputs with "proposals" were processed, box_proposals comes in front
+        (coco_evaluation.py:145-148) and bbox is there if any "instances" were processed too."""
+        if self._proposals is None:
+            return self._evaluate_instances()
+        res = self._proposals.evaluate()
+        if self._boxes or self._padded:
+            bbox = self._evaluate_instances()
+            if res is not None and bbox is not None:
+                res.update(bbox)
+        return res
+
+    def _evaluate_instances(self):
         import torch
 
         from . import ops
@@ -635,3 +660,247 @@ class COCOEvaluator:
                      "scores": scores}
         self.stats = coco_summarize(precision, recall, p)
         return OrderedDict(bbox=derive_coco_results(self.stats, precision, self._class_names))
+
+
+# ---- box-proposal recall (AR@k by area) -----------------------------------------------------------------------------------
+
+# coco_evaluation.py:380-399, to the letter
+PROPOSAL_AREAS = OrderedDict([("all", [0 ** 2, 1e5 ** 2]), ("small", [0 ** 2, 32 ** 2]), ("medium", [32 ** 2, 96 ** 2]),
+                              ("large", [96 ** 2, 1e5 ** 2]), ("96-128", [96 ** 2, 128 ** 2]), ("128-256", [128 ** 2, 256 ** 2]),
+                              ("256-512", [256 ** 2, 512 ** 2]), ("512-inf", [512 ** 2, 1e5 ** 2])])
+_AREA_SUFFIX = {"all": "", "small": "s", "medium": "m", "large": "l"}  # :230; the other four: "[name]"
+
+
+def proposal_recall_key(area, limit):
+    """the reference's result key (:234): AR@100, ARs@100, ...; AR[96-128]@100 for the areas it never reports; @all = no cut"""
+    return "AR%s@%s" % (_AREA_SUFFIX.get(area, "[%s]" % area), "all" if limit is None else "%d" % limit)
+
+
+def _xywh_to_xyxy_f32(bbox):
+    """BoxMode.convert of a python list (boxes.py:63,111-113): float32, one addition per far corner"""
+    b = np.asarray(bbox, np.float32).reshape(-1, 4)
+    return np.stack([b[:, 0], b[:, 1], b[:, 2] + b[:, 0], b[:, 3] + b[:, 1]], 1).astype(np.float32)
+
+
+def _id_key(v):
+    return v if isinstance(v, str) else int(v)
+
+
+class ProposalRecallEvaluator:
+    """The box_proposals task of the reference's COCOEvaluator (coco_evaluation.py:200-237 over _evaluate_box_proposals,
+    :372-480): average recall of the proposals an output carries, per (area range, limit) pair, matched on the device
+    (ops.proposal_recall, csrc/proprecall.hip).
+
+    `annotations`: a COCO-format dict or the path of a json file; `images[*].id` and `annotations[*].{image_id, bbox, area,
+    iscrowd}` are used (every category; crowd annotations are left out, :418).  `from_dataset_dicts` takes detectron2-format
+    dicts instead.  `limits`: cuts of the per-image proposal list (None = all), `areas`: names of PROPOSAL_AREAS.
+    `gather`: callable(per-rank dict of host arrays) -> list of such dicts on the main process, None elsewhere.
+
+    process() keeps `outputs[i]["proposals"]` (`proposal_boxes` / `objectness_logits`, on the device or on the host) and
+    never synchronises.  Only processed images take part, each as often as it was processed.  evaluate() uploads their
+    ground truth once, runs every pair in one launch chain and reads back once; it returns
+    OrderedDict(box_proposals={"AR@100": ..., "ARs@100": ..., ...}) with float(ar * 100) in the reference's key order, and
+    leaves the reference's dict of every pair (ar, recalls, thresholds, gt_overlaps sorted, num_pos; CPU tensors, formed from
+    the device's overlaps with the reference's torch expressions) in `self.results[(area, limit)]` and the device's integer
+    counts in `self.counts[(area, limit)]`.  This package's definitions: equal logits keep their input order; among equal
+    IoUs the first proposal and the first box win; a NaN logit is undefined.  An unknown image_id raises ValueError in
+    process(); more than ops.PROPOSAL_MAX_GT boxes in an image or more than ops.PROPOSAL_MAX_PER_IMAGE proposals after the
+    cut raise DrnError in evaluate() before anything is uploaded."""
+
+    def __init__(self, annotations, limits=(100, 1000), areas=("all", "small", "medium", "large"), gather=None, device="cuda",
+                 thresholds=None):
+        if not isinstance(annotations, dict):
+            with open(annotations) as f:
+                annotations = json.load(f)
+        per = OrderedDict((_id_key(im["id"]), []) for im in annotations["images"])
+        for a in annotations["annotations"]:
+            if a.get("iscrowd", 0) == 0 and _id_key(a["image_id"]) in per:
+                per[_id_key(a["image_id"])].append(a)
+        self._setup([(iid, _xywh_to_xyxy_f32([a["bbox"] for a in anns]), np.array([a["area"] for a in anns], np.float32))
+                     for iid, anns in per.items()], limits, areas, gather, device, thresholds)
+
+    @classmethod
+    def from_dataset_dicts(cls, dataset_dicts, limits=(100, 1000), areas=("all", "small", "medium", "large"), gather=None,
+                           device="cuda", thresholds=None):
+        """detectron2-format dicts ({"image_id", "annotations": [{"bbox", "bbox_mode", "iscrowd"?, "area"?}]}), so that VOC
+        works.  An annotation without "area" counts with w * h of its XYWH box in float32 (this package's definition)."""
+        from .data import BoxMode
+
+        records = []
+        for r in dataset_dicts:
+            boxes, areas_ = [], []
+            for a in r.get("annotations", []):
+                if a.get("iscrowd", 0) != 0:
+                    continue
+                mode = int(a.get("bbox_mode", BoxMode.XYXY_ABS))
+                b = np.asarray(a["bbox"], np.float32).reshape(4)
+                if mode == int(BoxMode.XYWH_ABS):
+                    xyxy, wh = _xywh_to_xyxy_f32(b)[0], (b[2], b[3])
+                elif mode == int(BoxMode.XYXY_ABS):
+                    xyxy, wh = b, (b[2] - b[0], b[3] - b[1])
+                else:
+                    raise ValueError("bbox_mode %r is not supported" % (a["bbox_mode"],))
+                boxes.append(xyxy)
+                areas_.append(np.float32(a["area"]) if "area" in a else np.float32(wh[0]) * np.float32(wh[1]))
+            records.append((_id_key(r["image_id"]), np.array(boxes, np.float32).reshape(-1, 4), np.array(areas_, np.float32)))
+        self = cls.__new__(cls)
+        self._setup(records, limits, areas, gather, device, thresholds)
+        return self
+
+    def _setup(self, records, limits, areas, gather, device, thresholds):
+        for a in areas:
+            assert a in PROPOSAL_AREAS, "Unknown area range: {}".format(a)
+        self._limits = [None if l is None else int(l) for l in limits]
+        assert self._limits and areas and all(l is None or l > 0 for l in self._limits)
+        self._areas = list(areas)
+        self._gt = {iid: (box, area) for iid, box, area in records}
+        self._gather, self._device, self._thresholds, self._mark = gather, device, thresholds, None
+        self.results, self.counts = None, None
+        self.reset()
+
+    def reset(self):
+        self._boxes, self._logits, self._images = [], [], []
+
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            iid = _id_key(inp["image_id"])
+            if iid not in self._gt:
+                raise ValueError("image_id %r is not in the annotations" % (inp["image_id"],))
+            prop = out["proposals"]
+            self._boxes.append(prop.proposal_boxes.tensor.detach())
+            self._logits.append(prop.objectness_logits.detach())
+            self._images.append(iid)
+
+    def process_proposal_file(self, proposal_file):
+        """Feeds in a proposal file in the format data.load_proposals_into_dataset reads (a pickle, or the dict it holds:
+        ids | indexes, boxes, objectness_logits | scores, bbox_mode?): the entries whose id is in the annotations, in file
+        order, as host tensors.  Returns how many were fed."""
+        import pickle
+
+        import torch
+
+        from .data import BoxMode
+
+        proposals = proposal_file
+        if not isinstance(proposals, dict):
+            with open(proposal_file, "rb") as f:
+                proposals = pickle.load(f, encoding="latin1")
+        ids = proposals["ids"] if "ids" in proposals else proposals["indexes"]
+        logits = proposals["objectness_logits"] if "objectness_logits" in proposals else proposals["scores"]
+        mode = int(proposals["bbox_mode"]) if "bbox_mode" in proposals else int(BoxMode.XYXY_ABS)
+        by_str = {str(k): k for k in self._gt}
+        fed = 0
+        for k, i in enumerate(ids):
+            if str(i) not in by_str:
+                continue
+            boxes = np.asarray(proposals["boxes"][k], np.float32).reshape(-1, 4)
+            if mode != int(BoxMode.XYXY_ABS):
+                boxes = np.asarray(BoxMode.convert(boxes, mode, BoxMode.XYXY_ABS), np.float32)
+            self._boxes.append(torch.from_numpy(np.ascontiguousarray(boxes)))
+            self._logits.append(torch.from_numpy(np.ascontiguousarray(np.asarray(logits[k], np.float32).reshape(-1))))
+            self._images.append(by_str[str(i)])
+            fed += 1
+        return fed
+
+    def _refuse_over_cap(self, images, counts):
+        from . import ops
+        from ._cabi import DrnError
+
+        for iid in images:
+            if len(self._gt[iid][1]) > ops.PROPOSAL_MAX_GT:
+                raise DrnError("ProposalRecallEvaluator: image %r has %d ground-truth boxes; the device matcher holds at most "
+                               "%d per image" % (iid, len(self._gt[iid][1]), ops.PROPOSAL_MAX_GT))
+        cut = None if None in self._limits else max(self._limits)
+        kept = [c if cut is None else min(c, cut) for c in counts]
+        if kept and max(kept) > ops.PROPOSAL_MAX_PER_IMAGE:
+            worst = int(np.argmax(kept))
+            raise DrnError("ProposalRecallEvaluator: image %r has %d proposals after the cut; the device matcher holds at most "
+                           "%d per image" % (images[worst], kept[worst], ops.PROPOSAL_MAX_PER_IMAGE))
+        return max(kept) if kept else 0
+
+    def evaluate(self):
+        import torch
+
+        images, counts = list(self._images), [int(b.shape[0]) for b in self._boxes]
+        if self._gather is None:
+            max_prop = self._refuse_over_cap(images, counts)  # before anything is uploaded
+        from . import ops
+
+        dev = torch.device(self._device)
+        mark = self._mark or (lambda name: None)  # tools/proposal_recall_bench.py records a HIP event per stage here
+        mark("start")
+        box = logit = None  # (an evaluation without a processed image touches no device)
+        if self._gather is not None:
+            host = lambda ts, shape: (torch.cat([t.float().reshape(shape).cpu() for t in ts]).numpy() if ts
+                                      else np.zeros((0,) + shape[1:], np.float32))
+            parts = self._gather({"boxes": host(self._boxes, (-1, 4)), "logits": host(self._logits, (-1,)),
+                                  "counts": np.array(counts, np.int64), "images": images})
+            if parts is None:
+                return None  # not the main process
+            images = [i for p in parts for i in p["images"]]
+            counts = [int(c) for p in parts for c in np.asarray(p["counts"])]
+            max_prop = self._refuse_over_cap(images, counts)
+            if images:
+                box = torch.from_numpy(np.concatenate([np.asarray(p["boxes"], np.float32).reshape(-1, 4) for p in parts])).to(dev)
+                logit = torch.from_numpy(np.concatenate([np.asarray(p["logits"], np.float32).reshape(-1) for p in parts])).to(dev)
+        elif self._boxes:
+            # host-resident proposals (a proposal file) go up in one copy, device-resident ones stay where they are
+            up = ((lambda t: t) if not any(b.is_cuda or s.is_cuda for b, s in zip(self._boxes, self._logits))
+                  else (lambda t: t.to(dev, non_blocking=True)))
+            box = torch.cat([up(b).float().reshape(-1, 4) for b in self._boxes]).to(dev).contiguous()
+            logit = torch.cat([up(s).float().reshape(-1) for s in self._logits]).to(dev).contiguous()
+        thr = (torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=torch.float32) if self._thresholds is None
+               else torch.as_tensor(self._thresholds, dtype=torch.float32).reshape(-1).cpu())  # :465-467
+        A, L, T, I = len(self._areas), len(self._limits), int(thr.shape[0]), len(images)
+        if I > 0:
+            gt_box = np.concatenate([self._gt[i][0] for i in images]).astype(np.float32).reshape(-1, 4)
+            gt_area = np.concatenate([self._gt[i][1] for i in images]).astype(np.float32)
+            ngt = [len(self._gt[i][1]) for i in images]
+            t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev, non_blocking=True)
+            off = lambda n: np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+            args = (box, logit, t(off(counts), torch.int32), t(gt_box, torch.float32), t(gt_area, torch.float32),
+                    t(off(ngt), torch.int32), t(np.array([PROPOSAL_AREAS[a] for a in self._areas], np.float32), torch.float32),
+                    t(np.array([0 if l is None else l for l in self._limits], np.int32), torch.int32), thr.to(dev),
+                    max(ngt), max_prop)
+            mark("upload")
+            m = ops.proposal_recall(*args, stages=1)
+            mark("order")
+            ops.proposal_recall(*args, stages=2, out=m)
+            mark("match")
+            G = gt_area.shape[0]
+            flat = torch.cat([m["counts"].reshape(-1).view(torch.int32), m["num_pos"].view(torch.int32),
+                              m["overlaps"].reshape(-1).view(torch.int32)]).cpu()  # one copy, the only sync
+            mark("read-back")
+            nc = 2 * A * L * T
+            cnt = flat[:nc].view(torch.int64).reshape(A, L, T)
+            num_pos = flat[nc: nc + 2 * A].view(torch.int64)
+            overlaps = flat[nc + 2 * A:].view(torch.float32).reshape(A, L, G)
+        else:
+            overlaps, cnt, num_pos = torch.zeros(A, L, 0), torch.zeros(A, L, T, dtype=torch.int64), torch.zeros(A, dtype=torch.int64)
+        self.results, self.counts, res = OrderedDict(), OrderedDict(), OrderedDict()
+        for l, limit in enumerate(self._limits):
+            for a, area in enumerate(self._areas):
+                ov = overlaps[a, l]
+                gt_overlaps, _ = torch.sort(ov[ov >= 0])  # :460-463 (-1 = not an entry)
+                n = int(num_pos[a])
+                recalls = torch.zeros_like(thr)
+                for i, tv in enumerate(thr):  # :468-473
+                    recalls[i] = (gt_overlaps >= tv).float().sum() / float(n)
+                ar = recalls.mean()
+                self.results[(area, limit)] = {"ar": ar, "recalls": recalls, "thresholds": thr, "gt_overlaps": gt_overlaps,
+                                               "num_pos": n}
+                self.counts[(area, limit)] = cnt[a, l].clone()
+                res[proposal_recall_key(area, limit)] = float(ar.item() * 100)
+        return OrderedDict(box_proposals=res)
+
+
+def evaluate_box_proposals(proposals, ground_truth, thresholds=None, area="all", limit=None, device="cuda"):
+    """_evaluate_box_proposals (coco_evaluation.py:372-480) on the device.  `proposals`: the reference's dataset_predictions,
+    [{"image_id", "proposals": Instances}]; `ground_truth`: a COCO-format dict or json path (in the place of coco_api), a list
+    of detectron2-format dataset dicts, or a ProposalRecallEvaluator's annotations in any form that class takes.  Returns the
+    reference's dict - ar, recalls, thresholds, gt_overlaps (sorted), num_pos - as CPU tensors (num_pos: int)."""
+    make = ProposalRecallEvaluator.from_dataset_dicts if isinstance(ground_truth, (list, tuple)) else ProposalRecallEvaluator
+    ev = make(ground_truth, limits=(limit,), areas=(area,), device=device, thresholds=thresholds)
+    ev.process(proposals, proposals)
+    ev.evaluate()
+    return ev.results[(area, limit)]

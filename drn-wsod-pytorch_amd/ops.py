@@ -1712,6 +1712,42 @@ def coco_accumulate(s_score, s_cat, s_rank, dm, di, npig, num_images, num_cats, 
     return out
 
 
+PROPOSAL_MAX_GT, PROPOSAL_MAX_PER_IMAGE = 256, 4096  # include/drn_wsod.h DRN_PROPOSAL_MAX_*
+
+
+def proposal_recall(prop_box, prop_logit, prop_off, gt_box, gt_area, gt_off, area_rng, limits, thresholds, max_gt, max_prop,
+                    stages=3, out=None):
+    """Box-proposal recall matching (see include/drn_wsod.h, drn_proposal_recall).  prop_box [P, 4] f32 XYXY, prop_logit
+    [P] f32, prop_off [I + 1] i32: the images' proposals, concatenated; gt_box [G, 4] f32 XYXY, gt_area [G] f32, gt_off
+    [I + 1] i32: the ground truth that is not crowd, in annotation order; area_rng [A, 2] f32, limits [L] i32 (<= 0: no
+    cut), thresholds [T] f32 - all on the device.  max_gt / max_prop = most boxes of one image / most proposals of one image
+    after the cut (host numbers).  Returns a dict: overlaps [A, L, G] f32 (-1 = not an entry), counts [A, L, T] and num_pos
+    [A] (int64).  stages = 1 / 2 with out = the dict of the stages = 1 call runs the ordering and the matching apart."""
+    dev = prop_box.device
+    P, G, I = prop_logit.shape[0], gt_area.shape[0], gt_off.shape[0] - 1
+    A, L, T = area_rng.shape[0], limits.shape[0], thresholds.shape[0]
+    assert prop_box.dtype == torch.float32 and prop_box.is_contiguous() and prop_box.shape == (P, 4)
+    assert prop_logit.dtype == torch.float32 and prop_logit.is_contiguous()
+    assert prop_off.dtype == torch.int32 and prop_off.shape == (I + 1,) and prop_off.is_contiguous()
+    assert gt_box.dtype == torch.float32 and gt_box.is_contiguous() and gt_box.shape == (G, 4)
+    assert gt_area.dtype == torch.float32 and gt_area.is_contiguous()
+    assert gt_off.dtype == torch.int32 and gt_off.is_contiguous() and I >= 1
+    assert area_rng.dtype == torch.float32 and area_rng.is_contiguous() and area_rng.shape == (A, 2)
+    assert limits.dtype == torch.int32 and limits.is_contiguous() and limits.dim() == 1
+    assert thresholds.dtype == torch.float32 and thresholds.is_contiguous() and thresholds.dim() == 1
+    if out is None:
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        nbytes = int(C.lib().drn_proposal_recall_workspace_bytes(P))
+        out = dict(ws=e((nbytes,), torch.uint8), overlaps=e((A, L, G), torch.float32), counts=e((A, L, T), torch.int64),
+                   num_pos=e((A,), torch.int64))
+    o = out
+    C.call("drn_proposal_recall", C.ptr(prop_box), C.ptr(prop_logit), C.ptr(prop_off), P, C.ptr(gt_box), C.ptr(gt_area),
+           C.ptr(gt_off), G, I, int(max_gt), int(max_prop), C.ptr(area_rng), A, C.ptr(limits), L, C.ptr(thresholds), T,
+           C.ptr(o["ws"]), o["ws"].numel(), int(stages), C.ptr(o["overlaps"]), C.ptr(o["counts"]), C.ptr(o["num_pos"]),
+           C.stream())
+    return out
+
+
 VOC_MAX_GT, VOC_MAX_REC = 128, 16  # include/drn_wsod.h DRN_VOC_MAX_*
 
 

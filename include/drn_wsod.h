@@ -863,6 +863,44 @@ int drn_coco_accumulate(const float* s_score, const int* s_cat, const int* s_ran
                         const int* max_dets, int M, const double* rec_thr, int R, void* workspace, long workspace_bytes,
                         int stages, double* precision, double* scores, double* recall, void* stream);
 
+/* ---- Box-proposal recall: AR@k by area (COCOEvaluator's box_proposals task; detectron2/evaluation/coco_evaluation.py) ---
+ * _evaluate_box_proposals (:372-480) for every (area range, limit) pair at once, on the device.  Per image that has at least
+ * one ground-truth box and one proposal (others are skipped before anything is counted, :424-425): the boxes with
+ * lo <= area <= hi (both ends inclusive, fp32; `area` is the annotation's field) are kept and counted into num_pos - also
+ * when none is left, and before the proposals are cut; the proposals are taken by descending objectness logit and cut to
+ * the limit; then min(P', G') rounds of greedy matching on pairwise_iou (fp32, detectron2/structures/boxes.py:329-361 in
+ * torch's operation order, uncontracted): every live box's best live proposal, the best-covered live box, its IoU recorded
+ * as entry j, box and proposal retired.  Entries past min(P', G') stay 0.
+ *
+ * Three rules the reference leaves open are this package's definition:
+ *   1. the objectness order is stable: equal logits keep their input order;
+ *   2. the first index wins, twice: among proposals of equal IoU for a box the lowest position in the sorted order, among
+ *      boxes of equal best IoU the lowest annotation index (what torch.max does on the CPU);
+ *   3. a NaN logit is undefined and stays undefined (nothing is read or written out of bounds).
+ *
+ * Caps: at most DRN_PROPOSAL_MAX_GT boxes per image and DRN_PROPOSAL_MAX_PER_IMAGE proposals per image after the cut;
+ * max_gt / max_prop are the largest such numbers, which the caller knows on the host; beyond a cap the entry answers
+ * DRN_ERR_UNSUPPORTED before anything is launched - nothing is truncated.
+ *
+ * Input, all on the device: the images' proposals concatenated, prop_box [P][4] fp32 XYXY (16-byte aligned), prop_logit
+ * [P], prop_off [I + 1] (ascending, 0 .. P); the ground truth that is not crowd, concatenated in annotation order, gt_box
+ * [G][4] fp32 XYXY, gt_area [G], gt_off [I + 1]; area_rng [A][2]; limits [L] int (<= 0: no cut); thresholds [T].
+ * Output: overlaps [A][L][G] fp32 - per (area range, limit) every image's segment holds its recorded entries first and -1
+ * (IoUs are >= 0) in the slots of boxes outside the range or of skipped images; counts [A][L][T] = entries >=
+ * thresholds[t]; num_pos [A].  P = 0: every slot -1, counts and num_pos 0.  One stream-ordered chain of launches whatever
+ * I is, no host read, capturable; integer atomics only, so the result is the same bits on every run.
+ * Workspace: 16-byte aligned, at least the bytes the workspace query answers for P.  stages: bit 0 = the ordering passes,
+ * bit 1 = the matching; 3 runs both, and a call with bit 1 alone continues from the workspace that a call with bit 0 alone
+ * left (used to time them apart). */
+#define DRN_PROPOSAL_MAX_GT 256
+#define DRN_PROPOSAL_MAX_PER_IMAGE 4096
+long drn_proposal_recall_workspace_bytes(int P);
+int drn_proposal_recall(const float* prop_box, const float* prop_logit, const int* prop_off, int P, const float* gt_box,
+                        const float* gt_area, const int* gt_off, int G, int I, int max_gt, int max_prop,
+                        const float* area_rng, int A, const int* limits, int L, const float* thresholds, int T,
+                        void* workspace, long workspace_bytes, int stages, float* overlaps, unsigned long long* counts,
+                        unsigned long long* num_pos, void* stream);
+
 /* ---- PASCAL VOC evaluation: AP and CorLoc (PascalVOCDetectionEvaluator; detectron2/evaluation/pascal_voc_evaluation.py) -
  * voc_eval (:237-350), voc_eval_corloc (:353-447) and voc_ap (:182-234) on the device, in fp64, operation for operation
  * (uncontracted), on the numbers the reference's text files hold: score "%.3f" = rint((double)s * 1000) / 1000, xmin / ymin
