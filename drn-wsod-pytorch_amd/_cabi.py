@@ -86,6 +86,11 @@ _SIGS = {
     "drn_gemm_tn_acc_sgd_guard": "pppp" + "iiii" + "llll" + "ppplp" + "fif" + "pp",
     "drn_detect_topk": "ppiii" + "ffff" + "i" + "pl" + "i" + "ppp",
     "drn_detect_gather": "plippippppp",
+    "drn_detect_all": "ppiii" + "ffff" + "i" + "pl" + "i" + "ppppp" + "p",
+    "drn_nms": "pp" + "lf" + "pl" + "pp" + "p",
+    "drn_batched_nms": "ppp" + "lf" + "pl" + "pp" + "p",
+    "drn_pairwise_iou": "pp" + "ll" + "p" + "p",
+    "drn_match": "pll" + "pip" + "pp" + "p",
     "drn_detect_topk_batch": "pppiiipi" + "ffi" + "pli" + "ppppp" + "p",
     "drn_detect_compact": "pppppii" + "p" + "ppppp" + "p",
     "drn_detect_union_batch": "pppp" + "ii" + "pi" + "pp" + "i" + "ffi" + "pli" + "ppppp" + "p",
@@ -144,6 +149,10 @@ def lib():
         _lib.drn_detect_batch_workspace_bytes.restype = ctypes.c_long
         _lib.drn_detect_union_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         _lib.drn_detect_union_workspace_bytes.restype = ctypes.c_long
+        _lib.drn_detect_all_workspace_bytes.argtypes = [ctypes.c_int]
+        _lib.drn_detect_all_workspace_bytes.restype = ctypes.c_long
+        _lib.drn_nms_workspace_bytes.argtypes = [ctypes.c_long]
+        _lib.drn_nms_workspace_bytes.restype = ctypes.c_long
         _lib.drn_gemm_nt_main_cols.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         _lib.drn_gemm_nt_main_cols.restype = ctypes.c_long
         _lib.drn_roi_pool_workspace_bytes.argtypes = [ctypes.c_int] * 10
@@ -164,7 +173,8 @@ def lib():
 
 def exported_symbols():
     return sorted(list(_SIGS) + ["drn_detect_workspace_bytes", "drn_detect_batch_workspace_bytes", "drn_detect_union_workspace_bytes", "drn_gemm_nt_main_cols", "drn_roi_pool_workspace_bytes",
-                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes", "drn_grad_norms_ws_bytes", "drn_proposal_recall_workspace_bytes"])
+                                  "drn_roi_backward_det_ws_bytes", "drn_augment_lds_bytes", "drn_grad_norms_ws_bytes", "drn_proposal_recall_workspace_bytes",
+                                  "drn_detect_all_workspace_bytes", "drn_nms_workspace_bytes"])
 
 
 _ERR = {-1: "invalid argument", -2: "kernel launch failure", -3: "unsupported"}

@@ -29,8 +29,8 @@ def _table():
     t = {
         "detectron2": {"__version__": "0.2"},  # detectron2/__init__.py:10 of the reference fork
         "detectron2.layers": pick(layers, "Conv2d", "Linear", "FrozenBatchNorm2d", "get_norm", "ROIAlign", "ShapeSpec", "cat",
-                                  "nonzero_tuple", "CNNBlockBase"),
-        "detectron2.structures": pick(structures, "Boxes", "Instances", "ImageList"),
+                                  "nonzero_tuple", "CNNBlockBase", "nms", "batched_nms"),
+        "detectron2.structures": pick(structures, "Boxes", "Instances", "ImageList", "pairwise_iou"),
         "detectron2.config": pick(config, "CfgNode", "get_cfg", "configurable"),
         "detectron2.checkpoint": pick(checkpoint, "DetectionCheckpointer"),
         "detectron2.checkpoint.c2_model_loading": pick(checkpoint, "convert_c2_detectron_names", "align_and_update_state_dicts"),

@@ -10,6 +10,7 @@
 // before it, so we walk the sorted list 64 candidates (one wave) at a time against the <= topk
 // survivors held in LDS and stop as soon as topk are kept - identical output, O(n*topk) work.
 #include "drn_common.h"
+#include "nms_shared.h"
 #include "radix_sort.h"
 
 namespace {
@@ -726,6 +727,45 @@ __global__ void tta_accumulate_kernel(const float* __restrict__ boxes, const flo
   }
 }
 
+namespace {
+
+// The single-image candidate stages, shared by drn_detect_topk and drn_detect_all: finite-row filter, threshold + ordered compaction
+// (background column dropped, boxes clipped), stable descending sort.  Leaves the candidates in k.c_*, their number in k.count,
+// the largest clipped coordinate in k.maxcoord and the sorted candidate ids in k.order.
+int launch_candidates_sorted(const Ws& k, const float* boxes, const float* scores, int R, int K, int nreg, float img_h, float img_w,
+                             float score_thresh, int cap, hipStream_t st) {
+  CandParams cp{boxes, scores, R, K, nreg, img_h, img_w, score_thresh, k.c_box, k.c_score, k.c_row, k.c_cls, k.count,
+                k.maxcoord, cap, (int*)k.key0};  // key0 doubles as the row map until the sort's second pass overwrites it
+  if (R > 0) hipLaunchKernelGGL(rows_finite_kernel, dim3((R + 3) / 4), dim3(256), 0, st, cp);
+  hipLaunchKernelGGL(rows_number_kernel, dim3(1), dim3(1024), 0, st, cp);
+  const long total = (long)R * K;
+  const int ntiles = (int)((total + CAND_TILE - 1) / CAND_TILE);
+  if (ntiles > SORT_BINS) return DRN_ERR_UNSUPPORTED;  // (8M scores per image; the tile counts live in the sort's histogram area)
+  if (ntiles > 0) {
+    hipLaunchKernelGGL(candidates_kernel<0>, dim3(ntiles), dim3(CAND_THREADS), 0, st, cp, k.hist, ntiles);
+    hipLaunchKernelGGL(candidates_kernel<1>, dim3(ntiles), dim3(CAND_THREADS), 0, st, cp, k.hist, ntiles);
+  } else {
+    (void)hipMemsetAsync(k.count, 0, sizeof(int), st);
+  }
+  // stable descending order of the live candidates: (score, index) -> key1/order -> key0/val0 -> key1/order
+  const int tiles = sort_tiles(cap);
+  const int shifts[3] = {0, 11, 22}, bits[3] = {11, 11, 10};
+  for (int ps = 0; ps < 3; ++ps) {
+    const bool even = (ps & 1) == 0;
+    SortPass sp{k.c_score, even ? k.key0 : k.key1, even ? k.val0 : k.order, even ? k.key1 : k.key0,
+                even ? k.order : k.val0, k.hist, k.count, tiles, shifts[ps], bits[ps], ps == 0};
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
+  }
+  return DRN_OK;
+}
+
+// drn_detect_all's workspace: drn_detect_topk's, then (64-byte aligned) the kept candidate ids and the suppression stage's share
+inline long all_keep_offset(int cap) { return (ws_fixed_bytes(cap) + 256 + 63) / 64 * 64; }
+
+}  // namespace
+
 extern "C" {
 
 // bytes of scratch drn_detect_topk needs for up to `cap` candidates (cap = R*K is always enough)
@@ -743,30 +783,8 @@ int drn_detect_topk(const float* boxes, const float* scores, int R, int K, int n
   if (workspace_bytes < drn_detect_workspace_bytes(cap)) return DRN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   Ws k = carve(workspace, workspace_bytes, cap);
-  CandParams cp{boxes, scores, R, K, nreg, img_h, img_w, score_thresh, k.c_box, k.c_score, k.c_row, k.c_cls, k.count,
-                k.maxcoord, cap, (int*)k.key0};  // key0 doubles as the row map until the sort's second pass overwrites it
-  if (R > 0) hipLaunchKernelGGL(rows_finite_kernel, dim3((R + 3) / 4), dim3(256), 0, st, cp);
-  hipLaunchKernelGGL(rows_number_kernel, dim3(1), dim3(1024), 0, st, cp);
-  const long total = (long)R * K;
-  const int ntiles = (int)((total + CAND_TILE - 1) / CAND_TILE);
-  if (ntiles > SORT_BINS) return DRN_ERR_UNSUPPORTED;  // (8M scores per image; the tile counts live in the sort's histogram area)
-  if (ntiles > 0) {
-    hipLaunchKernelGGL(candidates_kernel<0>, dim3(ntiles), dim3(CAND_THREADS), 0, st, cp, k.hist, ntiles);
-    hipLaunchKernelGGL(candidates_kernel<1>, dim3(ntiles), dim3(CAND_THREADS), 0, st, cp, k.hist, ntiles);
-  } else {
-    hipMemsetAsync(k.count, 0, sizeof(int), st);
-  }
-  // stable descending order of the live candidates: (score, index) -> key1/order -> key0/val0 -> key1/order
-  const int tiles = sort_tiles(cap);
-  const int shifts[3] = {0, 11, 22}, bits[3] = {11, 11, 10};
-  for (int ps = 0; ps < 3; ++ps) {
-    const bool even = (ps & 1) == 0;
-    SortPass sp{k.c_score, even ? k.key0 : k.key1, even ? k.val0 : k.order, even ? k.key1 : k.key0,
-                even ? k.order : k.val0, k.hist, k.count, tiles, shifts[ps], bits[ps], ps == 0};
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp);
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, sp);
-  }
+  const int rc = launch_candidates_sorted(k, boxes, scores, R, K, nreg, img_h, img_w, score_thresh, cap, st);
+  if (rc != DRN_OK) return rc;
   NmsParams np{k.c_box, k.c_score, k.c_cls, k.order, k.count, k.maxcoord, nms_thresh, topk, 40000, keep_ids, n_keep};
   hipLaunchKernelGGL(nms_topk_kernel, dim3(1), dim3(64), 0, st, np);
   DRN_CHECK_LAUNCH();
@@ -779,6 +797,40 @@ int drn_detect_gather(const void* workspace, long workspace_bytes, int cap, cons
   Ws k = carve((void*)workspace, workspace_bytes, cap);
   hipLaunchKernelGGL(gather_kernel, dim3((topk + 63) / 64), dim3(64), 0, (hipStream_t)stream, k.c_box, k.c_score,
                      k.c_row, k.c_cls, keep_ids, n_keep, out_boxes, out_scores, out_classes, out_rows);
+  DRN_CHECK_LAUNCH();
+  return DRN_OK;
+}
+
+// bytes of scratch drn_detect_all needs: the candidate stages' share, the kept ids, the suppression stage of nms.hip
+long drn_detect_all_workspace_bytes(int cap) {
+  const long c = cap < 1 ? 1 : cap;
+  return all_keep_offset((int)c) + (c * 4 + 63) / 64 * 64 + drn_supp::suppress_ws_bytes(c);
+}
+
+// The single-image tail without the 1024 cap (see include/drn_wsod.h): the candidate stages of drn_detect_topk, the panelled
+// NMS of nms.hip over all sorted candidates, the gather.  topk < 0 keeps every survivor, topk >= 1 the first topk.
+int drn_detect_all(const float* boxes, const float* scores, int R, int K, int nreg, float img_h, float img_w,
+                   float score_thresh, float nms_thresh, int topk, void* workspace, long workspace_bytes, int cap,
+                   float* out_boxes, float* out_scores, int* out_classes, int* out_rows, int* out_count, void* stream) {
+  if (!boxes || !scores || !workspace || !out_boxes || !out_scores || !out_classes || !out_rows || !out_count || topk == 0 ||
+      cap < 1 || R < 0 || K < 1)
+    return DRN_ERR_ARG;
+  if (nreg != 1 && nreg != K) return DRN_ERR_ARG;
+  if (cap < R) return DRN_ERR_ARG;
+  if ((long)R * K > drn_supp::MAX_N || cap > drn_supp::MAX_N) return DRN_ERR_UNSUPPORTED;
+  if (((uintptr_t)workspace & 15) || workspace_bytes < drn_detect_all_workspace_bytes(cap)) return DRN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Ws k = carve(workspace, workspace_bytes, cap);
+  const int rc = launch_candidates_sorted(k, boxes, scores, R, K, nreg, img_h, img_w, score_thresh, cap, st);
+  if (rc != DRN_OK) return rc;
+  char* w = (char*)workspace + all_keep_offset(cap);
+  int* keep = (int*)w;
+  w += ((long)cap * 4 + 63) / 64 * 64;
+  drn_supp::SuppressIn in{k.c_box, k.c_cls, k.order, k.count, k.maxcoord, nullptr, 40000, nms_thresh, topk < 0 ? 0x7fffffff : topk};
+  drn_supp::launch_suppress(in, cap, w, keep, nullptr, out_count, st);
+  const int slots = topk < 0 || topk > cap ? cap : topk;
+  hipLaunchKernelGGL(gather_kernel, dim3((slots + 63) / 64), dim3(64), 0, st, k.c_box, k.c_score, k.c_row, k.c_cls,
+                     (const int*)keep, (const int*)out_count, out_boxes, out_scores, out_classes, out_rows);
   DRN_CHECK_LAUNCH();
   return DRN_OK;
 }
@@ -831,7 +883,7 @@ int drn_detect_topk_batch(const float* boxes, const float* scores, const int* im
     hipLaunchKernelGGL(candidates_batch_kernel<0>, dim3(ntiles), dim3(CAND_THREADS), 0, st, bp, g, k.hist, ntiles);
     hipLaunchKernelGGL(candidates_batch_kernel<1>, dim3(ntiles), dim3(CAND_THREADS), 0, st, bp, g, k.hist, ntiles);
   } else {
-    (void)hipMemsetAsync(k.count, 0, sizeof(int), st);
+    (void)(void)hipMemsetAsync(k.count, 0, sizeof(int), st);
     (void)hipMemsetAsync(bw.seg_off, 0, sizeof(int) * (DET_MAX_IMAGES + 1), st);
   }
   launch_sorted_tail(k, bw, g, cap, n_images, postprocess, nms_thresh, topk, out_boxes, out_scores, out_classes, out_rows,

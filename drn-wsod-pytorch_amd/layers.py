@@ -1,6 +1,6 @@
 """The `detectron2.layers` operator surface this path uses (detectron2/layers/__init__.py:2-11):
 Conv2d (+norm +activation), FrozenBatchNorm2d, Linear, ROIAlign, ShapeSpec, CNNBlockBase, get_norm,
-cat, nonzero_tuple — same names, constructor arguments and state_dict keys, executing on the HIP
+cat, nonzero_tuple, nms, batched_nms — same names, constructor arguments and state_dict keys, executing on the HIP
 kernels.  Feature maps travel NHWC in the compute dtype; the [N,C,H,W] tensors handed across module
 boundaries are channels-last views of those buffers (shape-compatible with the reference)."""
 from collections import namedtuple
@@ -45,6 +45,18 @@ def nonzero_tuple(x):
     if x.dim() == 0:
         return x.unsqueeze(0).nonzero().unbind(1)
     return x.nonzero().unbind(1)
+
+
+def nms(boxes, scores, iou_threshold):
+    """torchvision.ops.nms as detectron2.layers exports it (detectron2/layers/nms.py:6): the kept indices, int64, by descending
+    score.  On the device (ops.nms; one 4-byte read for the variable length - ops.nms(padded=True) avoids it)."""
+    return ops.nms(boxes, scores, iou_threshold)
+
+
+def batched_nms(boxes, scores, idxs, iou_threshold):
+    """detectron2/layers/nms.py:10-29 on the device (ops.batched_nms)."""
+    assert boxes.shape[-1] == 4
+    return ops.batched_nms(boxes, scores, idxs, iou_threshold)
 
 
 def to_nhwc(x, dtype=None, cpad_to=None):

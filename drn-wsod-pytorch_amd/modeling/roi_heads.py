@@ -63,9 +63,9 @@ def padded_detections(boxes, scores, nper, image_sizes, output_sizes, score_thre
 
 # ------------------------------------------------------------------------------------------------
 class Matcher:
-    """Config holder with the reference's constructor checks (matcher.py:24-59).  The matching itself
-    (column arg-max over GT + threshold labelling, no low-quality matches on this path) runs inside
-    drn_oicr_targets."""
+    """The reference's constructor checks (matcher.py:24-59) and __call__ (matcher.py:61-103) without low-quality matches.  The
+    training path does not come through here: its matching (column arg-max over GT + threshold labelling) runs inside
+    drn_oicr_targets / drn_label_proposals; __call__ is the same rule as a stand-alone device op (ops.match)."""
 
     def __init__(self, thresholds: List[float], labels: List[int], allow_low_quality_matches: bool = False):
         thresholds = thresholds[:]
@@ -80,6 +80,10 @@ class Matcher:
         self.thresholds = thresholds
         self.labels = labels
         self.allow_low_quality_matches = allow_low_quality_matches
+
+    def __call__(self, match_quality_matrix):
+        """[N, M] qualities (N ground-truth rows, M predictions) -> (matches [M] int64, match_labels [M] int8)"""
+        return ops.match(match_quality_matrix, self.thresholds[1:-1], self.labels)
 
 
 class Box2BoxTransform:
@@ -662,8 +666,12 @@ class OICRROIHeads(ROIHeads):
                 all_boxes.append(b.unsqueeze(0))
             return results, all_scores, all_boxes
         for p, s, b in zip(proposals, probs.split(nper), boxes.split(nper)):
-            ob, os_, oc, _ = ops.detect_topk(b, s, p.image_size, last.test_score_thresh, last.test_nms_thresh,
-                                             last.test_topk_per_image)
+            if 1 <= last.test_topk_per_image <= 1024:
+                ob, os_, oc, _ = ops.detect_topk(b, s, p.image_size, last.test_score_thresh, last.test_nms_thresh,
+                                                 last.test_topk_per_image)
+            else:  # negative = every detection (fast_rcnn.py:65,133), or more than the one-wave kernel's 1024: the uncapped tail
+                ob, os_, oc, _ = ops.detect_all(b, s, p.image_size, last.test_score_thresh, last.test_nms_thresh,
+                                                last.test_topk_per_image)
             r = Instances(p.image_size)
             r.pred_boxes = Boxes(ob)
             r.scores = os_

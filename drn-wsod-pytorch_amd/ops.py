@@ -1385,6 +1385,143 @@ def detect_topk(boxes, scores, image_shape, score_thresh, nms_thresh, topk):
     return ob[:n], os_[:n], oc[:n].long(), orow[:n].long()
 
 
+NMS_MAX_N = 524288  # include/drn_wsod.h DRN_NMS_MAX_N
+
+
+def _device_f32(t, dev=None):
+    """fp32, contiguous, on the device (a host tensor goes to `dev` or the current device) - what the entry points read"""
+    if not t.is_cuda:
+        t = t.to(dev if dev is not None else torch.device("cuda", torch.cuda.current_device()))
+    return t.contiguous().float()
+
+
+def nms_workspace_bytes(n):
+    """bytes of scratch nms / batched_nms take for n boxes: DRN_NMS_WS_BYTES(n) = 104 n + 65536, linear in n"""
+    return int(C.lib().drn_nms_workspace_bytes(int(n)))
+
+
+def _nms(name, boxes, scores, idxs, iou_threshold, padded):
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or scores.dim() != 1 or scores.shape[0] != boxes.shape[0] or (
+            idxs is not None and (idxs.dim() != 1 or idxs.shape[0] != boxes.shape[0])):
+        raise C.DrnError("%s: boxes [n, 4], scores [n]%s expected, got %s, %s%s" % (
+            name, ", idxs [n]" if idxs is not None else "", tuple(boxes.shape), tuple(scores.shape),
+            ", %s" % (tuple(idxs.shape),) if idxs is not None else ""))
+    n = boxes.shape[0]
+    if n > NMS_MAX_N:
+        raise C.DrnError("%s: %d boxes, at most %d per call are built" % (name, n, NMS_MAX_N))
+    thr = float(iou_threshold)
+    if thr != thr:
+        raise C.DrnError("%s: the IoU threshold is NaN" % name)
+    if n == 0:  # nothing to launch: the empty result is known on the host
+        keep = torch.empty((0,), dtype=torch.int64, device=boxes.device)
+        return (keep, torch.zeros((1,), dtype=torch.int32, device=boxes.device)) if padded else keep
+    boxes = _device_f32(boxes)
+    dev = boxes.device
+    scores = _device_f32(scores, dev)
+    nbytes = nms_workspace_bytes(n)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    keep = torch.empty((n,), dtype=torch.int64, device=dev)
+    nk = torch.empty((1,), dtype=torch.int32, device=dev)
+    if idxs is None:
+        C.call("drn_nms", C.ptr(boxes), C.ptr(scores), n, thr, C.ptr(ws), nbytes, C.ptr(keep), C.ptr(nk), C.stream())
+    else:
+        idxs = idxs.to(device=dev, dtype=torch.int32).contiguous()
+        C.call("drn_batched_nms", C.ptr(boxes), C.ptr(scores), C.ptr(idxs), n, thr, C.ptr(ws), nbytes, C.ptr(keep), C.ptr(nk),
+               C.stream())
+    if padded:
+        return keep, nk
+    return keep[:int(nk.item())]
+
+
+def nms(boxes, scores, iou_threshold, padded=False):
+    """torchvision.ops.nms on the device (drn_nms): boxes [n, 4] XYXY, scores [n] -> the int64 indices of the kept boxes in
+    descending score order (equal scores in input order; a box is dropped iff its IoU with a kept earlier one is strictly above
+    the threshold; a NaN score is undefined).  padded=False returns the reference's variable-length tensor, at the price of ONE
+    4-byte read of the count; padded=True returns (keep [n] int64, count [1] int32) - keep[:count] is the result, the words behind it
+    are unspecified - and reads nothing back, so the call can be captured in a graph.  Input that is not fp32, not contiguous or
+    not on the device is converted.  More than NMS_MAX_N boxes raise DrnError before the library is touched."""
+    return _nms("nms", boxes, scores, None, iou_threshold, padded)
+
+
+def batched_nms(boxes, scores, idxs, iou_threshold, padded=False):
+    """detectron2.layers.batched_nms (nms.py:10-29) on the device (drn_batched_nms): boxes of different idxs never suppress each
+    other - below 40000 boxes by the reference's coordinate offset idx * (boxes.max() + 1), from 40000 on per class on the raw
+    boxes.  idxs: any integer dtype.  Result, padded= and limits as nms()."""
+    return _nms("batched_nms", boxes, scores, idxs, iou_threshold, padded)
+
+
+def detect_all(boxes, scores, image_shape, score_thresh, nms_thresh, topk=-1):
+    """detect_topk without the 1024 cap (drn_detect_all): topk < 0 returns every detection that survives the NMS
+    (fast_rcnn.py:65,133), topk >= 1 the first topk.  Same arguments and the same four results as detect_topk; ONE 4-byte read of the
+    count.  R * K above NMS_MAX_N or topk == 0 raise DrnError before the library is touched."""
+    if boxes.dim() != 2 or scores.dim() != 2 or scores.shape[0] != boxes.shape[0] or scores.shape[1] < 2:
+        raise C.DrnError("detect_all: boxes [R, 4 * nreg], scores [R, K + 1] expected, got %s, %s"
+                         % (tuple(boxes.shape), tuple(scores.shape)))
+    R, K = scores.shape[0], scores.shape[1] - 1
+    nreg = boxes.shape[1] // 4
+    topk = int(topk)
+    if topk == 0 or boxes.shape[1] != 4 * nreg or nreg not in (1, K):
+        raise C.DrnError("detect_all: topk = %d (negative = all, or >= 1), %d box columns for %d classes" % (topk, boxes.shape[1], K))
+    if R * K > NMS_MAX_N:
+        raise C.DrnError("detect_all: %d x %d entries, at most %d per call are built" % (R, K, NMS_MAX_N))
+    boxes = _device_f32(boxes)
+    dev = boxes.device
+    scores = _device_f32(scores, dev)
+    cap = max(R * K, 1)
+    nbytes = C.lib().drn_detect_all_workspace_bytes(cap)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    slots = cap if topk < 0 else min(topk, cap)
+    ob = torch.empty((slots, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((slots,), dtype=torch.float32, device=dev)
+    oc = torch.empty((slots,), dtype=torch.int32, device=dev)
+    orow = torch.empty((slots,), dtype=torch.int32, device=dev)
+    nk = torch.empty((1,), dtype=torch.int32, device=dev)
+    C.call("drn_detect_all", C.ptr(boxes), C.ptr(scores), R, K, nreg, float(image_shape[0]), float(image_shape[1]),
+           float(score_thresh), float(nms_thresh), topk, C.ptr(ws), nbytes, cap, C.ptr(ob), C.ptr(os_), C.ptr(oc), C.ptr(orow),
+           C.ptr(nk), C.stream())
+    n = int(nk.item())
+    return ob[:n], os_[:n], oc[:n].long(), orow[:n].long()
+
+
+def pairwise_iou(a, b):
+    """detectron2.structures.pairwise_iou (boxes.py:329-361) on tensors: a [N, 4], b [M, 4] XYXY -> [N, M] fp32 on the device, the
+    fp32 formula of label_proposals / proposal_recall.  An empty N or M launches nothing."""
+    if a.dim() != 2 or a.shape[1] != 4 or b.dim() != 2 or b.shape[1] != 4:
+        raise C.DrnError("pairwise_iou: boxes [N, 4] and [M, 4] expected, got %s, %s" % (tuple(a.shape), tuple(b.shape)))
+    N, M = a.shape[0], b.shape[0]
+    if N == 0 or M == 0:
+        return torch.empty((N, M), dtype=torch.float32, device=a.device)
+    a = _device_f32(a)
+    b = _device_f32(b, a.device)
+    out = torch.empty((N, M), dtype=torch.float32, device=a.device)
+    C.call("drn_pairwise_iou", C.ptr(a), C.ptr(b), N, M, C.ptr(out), C.stream())
+    return out
+
+
+def match(quality, thresholds, labels):
+    """Matcher.__call__ (matcher.py:61-103) without low-quality matches (drn_match): quality [N, M] -> (matches [M] int64: the row of
+    each column's maximum, the first row on ties; match_labels [M] int8: labels[t] of the interval thresholds[t - 1] <= max <
+    thresholds[t]).  thresholds: 1 .. 3 ascending values WITHOUT the infinities, labels one more, each -1 / 0 / 1.  N = 0: matches 0,
+    labels[0]."""
+    thresholds, labels = [float(t) for t in thresholds], [int(l) for l in labels]
+    if quality.dim() != 2 or not 1 <= len(thresholds) <= 3 or len(labels) != len(thresholds) + 1 or any(
+            l not in (-1, 0, 1) for l in labels):
+        raise C.DrnError("match: quality [N, M], 1 .. 3 thresholds and one label more (each -1, 0 or 1) expected, got %s, %s, %s"
+                         % (tuple(quality.shape), thresholds, labels))
+    N, M = quality.shape
+    if M == 0:
+        return (torch.empty((0,), dtype=torch.int64, device=quality.device),
+                torch.empty((0,), dtype=torch.int8, device=quality.device))
+    quality = _device_f32(quality)
+    dev = quality.device
+    matches = torch.empty((M,), dtype=torch.int64, device=dev)
+    mlab = torch.empty((M,), dtype=torch.int8, device=dev)
+    th, lb = C.host_floats(thresholds), C.host_ints(labels)
+    C.call("drn_match", C.ptr(quality) if N > 0 else None, N, M, ctypes.cast(th, ctypes.c_void_p), len(thresholds),
+           ctypes.cast(lb, ctypes.c_void_p), C.ptr(matches), C.ptr(mlab), C.stream())
+    return matches, mlab
+
+
 DETECT_MAX_IMAGES, DETECT_BATCH_MAX_ENTRIES = 16, 4194304  # include/drn_wsod.h DRN_DETECT_MAX_IMAGES / _BATCH_MAX_ENTRIES
 
 

@@ -1,7 +1,8 @@
 """Boxes / Instances / ImageList holders with the reference's interface
 (detectron2/structures/{boxes,instances,image_list}.py).  Plain Python field bags over device
 tensors: plumbing, no arithmetic on the hot path happens here (the IoU / matching / clipping the
-reference does with these classes is done inside the HIP head and inference-tail kernels)."""
+reference does with these classes is done inside the HIP head and inference-tail kernels;
+pairwise_iou is that IoU as a stand-alone device op)."""
 import itertools
 from typing import Any, Dict, List, Tuple, Union
 
@@ -70,6 +71,13 @@ class Boxes:
 
     def __iter__(self):
         yield from self.tensor
+
+
+def pairwise_iou(boxes1: Boxes, boxes2: Boxes) -> torch.Tensor:
+    """detectron2/structures/boxes.py:329-361: the [N, M] IoU matrix of two Boxes, on the device (ops.pairwise_iou)."""
+    from . import ops
+
+    return ops.pairwise_iou(boxes1.tensor, boxes2.tensor)
 
 
 class Instances:

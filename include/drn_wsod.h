@@ -751,6 +751,22 @@ int drn_detect_topk(const float* boxes, const float* scores, int R, int K, int n
 int drn_detect_gather(const void* workspace, long workspace_bytes, int cap, const int* keep_ids, const int* n_keep,
                       int topk, float* out_boxes, float* out_scores, int* out_classes, int* out_rows, void* stream);
 
+/* The single-image tail without the cap (fast_rcnn.py:88-141 with any topk_per_image; `topk < 0` = "return all detections",
+ * fast_rcnn.py:65,133): the candidate stages of drn_detect_topk (finite-row filter, background column dropped, clip,
+ * score > thresh, row-major compaction, stable descending sort), then the panelled NMS of drn_batched_nms over ALL sorted
+ * candidates (class offset by the largest clipped coordinate + 1 below 40000 candidates, per-class on the raw boxes from 40000
+ * on - decided by the candidate count on the device), then the gather.  topk < 0 keeps every survivor, topk >= 1 the first topk
+ * (no 1024 limit; later panels retire at once when topk is reached); topk == 0 is DRN_ERR_ARG.  Outputs are sized by the caller for
+ * cap entries: out_boxes [cap][4], out_scores / out_classes / out_rows [cap]; out_count [1] on the device; slots at and beyond
+ * the count are not written.  cap >= R, and cap = R * K is always enough; R * K and cap above DRN_NMS_MAX_N are
+ * DRN_ERR_UNSUPPORTED before any launch.  Workspace: 16-byte aligned, drn_detect_all_workspace_bytes(cap) bytes (linear in cap).
+ * Nothing is read back; the launch count depends on R * K and cap alone.  drn_detect_topk and the batched tails keep their form
+ * and their limits. */
+long drn_detect_all_workspace_bytes(int cap);
+int drn_detect_all(const float* boxes, const float* scores, int R, int K, int nreg, float img_h, float img_w,
+                   float score_thresh, float nms_thresh, int topk, void* workspace, long workspace_bytes, int cap,
+                   float* out_boxes, float* out_scores, int* out_classes, int* out_rows, int* out_count, void* stream);
+
 /* The batched, sync-free inference tail: all images of a call through ONE launch chain whose length does not depend on
  * n_images, and nothing is read back by the host.
  * boxes [M][4*nreg], scores [M][K+1] with the rows of image b contiguous: img_off_host [n_images + 1] (HOST, ascending from 0
@@ -781,6 +797,42 @@ int drn_detect_topk_batch(const float* boxes, const float* scores, const int* im
 int drn_detect_compact(const float* boxes, const float* scores, const int* classes, const int* count, const int* image_index,
                        int n_blocks, int topk, int* offsets, float* out_boxes, float* out_scores, int* out_classes,
                        int* out_images, int* out_n, void* stream);
+
+/* ---- stand-alone box operators: nms, batched_nms, pairwise_iou, Matcher ---------------------------------------------
+ * drn_nms: torchvision nms as oracle/roi_ops.c:223-252 states it.  boxes [n][4] fp32 XYXY, scores [n]; neither is written.
+ *   Order: descending score, stable - equal scores keep ascending input index (the tie rule of the inference tail).
+ *   Box j is suppressed by a kept earlier box i iff inter / (area_i + area_j - inter) > iou_thr in fp32 with exactly that operation
+ *   order, uncontracted; the comparison is strict; a NaN ratio (two zero-area boxes) compares false, so both stay.
+ *   keep [n] int64: keep[0 .. n_keep[0]) = original indices in descending-score order; words beyond n_keep[0] are unspecified.
+ *   A NaN score is undefined and stays undefined (nothing is read or written out of bounds).
+ * drn_batched_nms: detectron2/layers/nms.py:10-29 with idxs [n] int32.  n < 40000: every box is offset by
+ *   (float) idx * (max over all 4 n coordinates + 1.f) in fp32 - the maximum is reduced on the device (integer max of order-preserving
+ *   keys) - and the rule above runs on the offset boxes.  n >= 40000: boxes suppress only boxes of their own class, on the raw
+ *   coordinates; the result is in descending-score order with the same tie rule.
+ * Form: the package's stable radix passes, then per panel of 512 sorted rows one launch of 64 x 64 IoU tiles over many workgroups
+ * (64-bit suppression words) and one launch that resolves the panel in order and ORs the kept rows' words into a removed-bitmap;
+ * 12 + 2 * ceil(n / 512) launches (11 for drn_nms, and for n >= 40000), a function of n alone: capturable.  No host read, no
+ * allocation, no float atomics; everything on the caller's stream.  n = 0 launches one store of n_keep = 0 (the other pointers
+ * may be NULL).  Cap: n <= DRN_NMS_MAX_N, beyond it DRN_ERR_UNSUPPORTED before any launch.
+ * Workspace: 16-byte aligned, DRN_NMS_WS_BYTES(n) = drn_nms_workspace_bytes(n) bytes - a 512-row panel of n / 64 words plus the
+ * sort and the sorted boxes, linear in n (never n^2). */
+#define DRN_NMS_MAX_N 524288
+#define DRN_NMS_WS_BYTES(n) (104L * (n) + 65536L)
+long drn_nms_workspace_bytes(long n);
+int drn_nms(const float* boxes, const float* scores, long n, float iou_thr, void* workspace, long workspace_bytes,
+            long long* keep, int* n_keep, void* stream);
+int drn_batched_nms(const float* boxes, const float* scores, const int* idxs, long n, float iou_thr, void* workspace,
+                    long workspace_bytes, long long* keep, int* n_keep, void* stream);
+/* pairwise_iou (detectron2/structures/boxes.py:329-361): a [N][4], b [M][4] fp32 XYXY -> out [N][M] fp32, the fp32 formula of
+ * drn_label_proposals and drn_proposal_recall (inter > 0 ? inter / (area_a + area_b - inter) : 0, uncontracted).  An empty N or M
+ * launches nothing. */
+int drn_pairwise_iou(const float* a, const float* b, long N, long M, float* out, void* stream);
+/* Matcher.__call__ (detectron2/modeling/matcher.py:61-103) for allow_low_quality_matches = False: quality [N][M] fp32 on the
+ * device; thresholds [n_thr] and labels [n_thr + 1] (each -1, 0 or 1) are HOST arrays, n_thr <= 3 (DRN_ERR_UNSUPPORTED beyond).
+ * matches [M] int64 = the row of the column's maximum (the first row on ties), match_labels [M] int8 = labels[t] for the interval
+ * thresholds[t - 1] <= max < thresholds[t] over (-inf, thresholds.., +inf).  N = 0: matches = 0, match_labels = labels[0]. */
+int drn_match(const float* quality, long N, long M, const float* thresholds, int n_thr, const int* labels, long long* matches,
+              signed char* match_labels, void* stream);
 
 /* ---- test-time augmentation ------------------------------------------- */
 
